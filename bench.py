@@ -22,10 +22,16 @@ Launch: `python bench.py --gpus N`.  When N > 1 and no launcher set WORLD_SIZE, 
 Prints ONE JSON line on rank 0 (see the driver contract), with extra objects:
   roofline     : algorithmic bytes (input cells * sizeof + encoded bytes) / HIP-event time of the encode kernel
                  (events recorded on the stream the kernel is launched on, inside dcdf_encoder_run)
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line; these are null then):
   cpu_baseline : the CPU oracle (C++ restatement of the reference, 1 thread like the reference) on a bounded
                  sample of the same chunks, timed on this host (N = 1 only)
   gather       : the final host-side gather of {offsets, bytes, minmax} and the SHA-256 of the concatenation of all
                  chunks in chunk order (equal for every N)
+  also end_to_end_host_buffers, roofline.measured_copy, decode, also and the oracle spot check
+                 (config.bytes_verified_vs_oracle): see the options and the sections below
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's chunks) to DIR/*.npy, so that two builds can be
+compared output for output; the inputs are the same for the same arguments.
 """
 import argparse
 import hashlib
@@ -41,6 +47,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+# what the side measurements default to under --full; without it they are off (0 / '') unless given explicitly
+FULL_DEFAULTS = {"cpu_sample": 24, "verify": 4, "host_sample": 1024, "decode_queries": 200000, "also": "i64,f32,f64"}
+DUMP_SAMPLE_BYTES = 8 << 20  # encoded bytes in encoded_sample.npy (as float32: 32 MiB)
 
 
 def parse_args(argv=None):
@@ -57,9 +66,20 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", choices=["i32", "i64", "f32", "f64"], default="i32",
                     help="i32 (default): stored fixed-point integers; f32/f64: floats converted on the fly (to_fixed, --fbits)")
     ap.add_argument("--fbits", type=int, default=3, help="fractional bits of the float workloads")
-    ap.add_argument("--cpu-sample", type=int, default=24, help="chunks timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--verify", type=int, default=4, help="chunks compared byte-for-byte with the oracle (untimed)")
-    ap.add_argument("--no-gather", action="store_true", help="skip the host-side gather + SHA-256 (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (CPU baseline, oracle spot check, host-side "
+                         "gather + SHA-256, host-buffer end to end, device copy rate, decode sample, other element types). "
+                         "Without it a run sets up, warms up, times the steps and prints the line; the options below that "
+                         "default to 'with --full' are then off unless given explicitly")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's chunks) to DIR/<name>.npy: "
+                         "chunk_ids, chunk_results [status, bytes, snapshots, logs], minmax (per instant), chunk_sha256 (of "
+                         "each chunk's encoded bytes) and encoded_sample (the encoded bytes of a fixed, seeded sample of the "
+                         "chunks, listed in encoded_sample_chunks); float32/float64, well under 64 MB")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="chunks timed on the CPU oracle (default 24 with --full, else 0 = skip)")
+    ap.add_argument("--verify", type=int, default=None,
+                    help="chunks compared byte-for-byte with the oracle, untimed (default 4 with --full, else 0)")
+    ap.add_argument("--no-gather", action="store_true", help="skip the host-side gather + SHA-256 of --full (profiling runs)")
     ap.add_argument("--pad-elems", type=int, default=0, help="config1: extra elements between consecutive chunks in HBM")
     ap.add_argument("--dataset", choices=["model", "noise", "wide"], default="model",
                     help="model: the SURVEY 8(d) value model (default, the headline workload).  noise: iid U[0, 2^30) cells -- the "
@@ -67,15 +87,22 @@ def parse_args(argv=None):
                          "emission path and one-instant blocks; a throughput figure for that path, never the headline.  wide: the "
                          "model raster times 300 -- log differences need three bytes and the snapshots' ranges exceed 16 bits (no compact "
                          "copy), logs still win chunk.rs:62: the general path's LOG side")
-    ap.add_argument("--host-sample", type=int, default=1024, help="chunks pushed through the host-buffer entry point for the "
-                    "PCIe-inclusive end-to-end figure (0 = skip); 1024 chunks = 8.6 GB of int32 input: long enough for the pinned "
-                    "double buffers of the upload and of the download to reach their steady state")
-    ap.add_argument("--decode-queries", type=int, default=200000,
+    ap.add_argument("--host-sample", type=int, default=None, help="chunks pushed through the host-buffer entry point for the "
+                    "PCIe-inclusive end-to-end figure (default 1024 with --full, else 0 = skip); 1024 chunks = 8.6 GB of int32 input: "
+                    "long enough for the pinned double buffers of the upload and of the download to reach their steady state")
+    ap.add_argument("--decode-queries", type=int, default=None,
                     help="after the timed region (full configs[2] int32 raster, N = 1 only): this many configs[4] queries against the "
-                         "chunks the session left on the device -> the line's \"decode\" object (0 = skip)")
-    ap.add_argument("--also", default="i64,f32,f64", help="after the timed region (full configs[2] int32 raster, N = 1 only): short runs "
-                    "of the same raster in these element types -> the line's \"also\" object ('' = skip)")
-    return ap.parse_args(argv)
+                         "chunks the session left on the device -> the line's \"decode\" object (default 200000 with --full, else 0 = skip)")
+    ap.add_argument("--also", default=None, help="after the timed region (full configs[2] int32 raster, N = 1 only): short runs "
+                    "of the same raster in these element types -> the line's \"also\" object (default 'i64,f32,f64' with --full, "
+                    "else '' = skip)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else type(v)())
+    return args
 
 
 def spawn_ranks(n):
@@ -133,6 +160,35 @@ def source_sha():
         h.update(f.encode())
         h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, enc, ids):
+    """--dump-outputs: what the last timed step left for this rank's chunks (what a caller gets from dcdf_encoder_result and
+    dcdf_encoder_gather), as float32 / float64 .npy files.  Every chunk by length, counts, per-instant (min, max) and the
+    SHA-256 of its bytes; the bytes themselves for a fixed, seeded sample of whole chunks."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    buf, offs, lens, mm = enc.gather()
+    n = enc.n
+    out = {"chunk_ids": np.asarray(ids, dtype=np.float64),
+           "chunk_results": np.array([enc.result(i) for i in range(n)], dtype=np.float64).reshape(n, 4),
+           "minmax": mm.astype(np.float64),
+           "chunk_sha256": np.zeros((n, 32), dtype=np.float32)}
+    for i in range(n):
+        b = memoryview(buf[int(offs[i]):int(offs[i]) + int(lens[i])])
+        out["chunk_sha256"][i] = np.frombuffer(hashlib.sha256(b).digest(), dtype=np.uint8)
+    # whole chunks in a seeded order until the byte budget is spent (64 MB in all, the arrays above included)
+    budget = min(DUMP_SAMPLE_BYTES, max(0, (64_000_000 - sum(a.nbytes for a in out.values())) // 4 - 1024))
+    pick, total = [], 0
+    for i in np.random.default_rng(0xDCDF0007).permutation(n):
+        if total + int(lens[i]) <= budget:
+            pick.append(int(i))
+            total += int(lens[i])
+    parts = [buf[int(offs[i]):int(offs[i]) + int(lens[i])] for i in pick]
+    out["encoded_sample"] = (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)).astype(np.float32)
+    out["encoded_sample_chunks"] = out["chunk_ids"][pick]
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def main():
@@ -284,9 +340,12 @@ def main():
     out_bytes = enc.total_bytes()
     snaps = sum(enc.result(i)[2] for i in range(n))
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, enc, ids)
+
     # ---- the final host-side gather of {offsets, bytes, minmax} (untimed w.r.t. `value`; reported on its own) --------
     gather = None
-    if not args.no_gather:
+    if args.full and not args.no_gather:
         g0 = time.perf_counter()
         buf, goffs, glens, mm = enc.gather()  # device pack + one D2H copy per rank
         g1 = time.perf_counter()
@@ -407,7 +466,7 @@ def main():
 
     # ---- "also report against a measured device-to-device copy on the same GPU" ------------------------------
     copy_gbs = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         nb = 1 << 31
         a = torch.empty(nb, dtype=torch.uint8, device="cuda")
         b = torch.zeros(nb, dtype=torch.uint8, device="cuda")

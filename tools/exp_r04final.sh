@@ -9,7 +9,7 @@ bash tools/collect_query_profiles.sh r04 > $O/qcollect.log 2>&1 || { tail -20 $O
 cp gpurun_out/qprof_r04/query_traffic_latest.json profiles/query_traffic_latest.json
 timeout -k 10 600 python tools/bench_ingest.py > $O/ingest.json 2> $O/ingest.err || exit 1
 w0=$(date +%s.%N)
-timeout -k 10 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 w1=$(date +%s.%N)
 python3 -c "print('default bench wall s', $w1 - $w0)"
 cp profiles/traffic_latest.json profiles/query_traffic_latest.json $O/

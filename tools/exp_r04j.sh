@@ -6,7 +6,7 @@ bash tools/collect_query_profiles.sh r04 > $O/qprof.log 2>&1 || { tail -20 $O/qp
 tail -1 $O/qprof.log
 cp gpurun_out/qprof_r04/query_traffic_latest.json profiles/query_traffic_latest.json
 s=$(date +%s.%N)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 e=$(date +%s.%N)
 python3 -c "print(\"bench.py default wall: %.1f s\" % ($e - $s))"
 python - <<'PY'
