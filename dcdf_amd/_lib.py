@@ -55,6 +55,7 @@ SYMBOLS = [
     "dcdf_chunk_close", "dcdf_chunk_info", "dcdf_chunk_get", "dcdf_chunk_fill_cell", "dcdf_chunk_fill_window",
     "dcdf_chunk_search", "dcdf_query_fill_window_batch", "dcdf_query_search_batch", "dcdf_query_fill_window_batch_typed", "dcdf_query_search_batch_mem", "dcdf_query_get_batch", "dcdf_query_fill_cell_batch", "dcdf_chunk_open_batch", "dcdf_chunk_instant_layout", "dcdf_raster_create", "dcdf_raster_destroy", "dcdf_raster_fill_window_batch", "dcdf_raster_search_batch", "dcdf_suggest_fraction", "dcdf_encoder_object_sha256",
     "dcdf_synth_fill", "dcdf_calib_read", "dcdf_device_alloc", "dcdf_device_free", "dcdf_device_copy", "dcdf_strerror", "dcdf_device_name", "dcdf_abi_version", "dcdf_last_hip_error", "dcdf_device_pool_trim",
+    "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
 ]
 
 
@@ -78,8 +79,24 @@ def lib():
         L.dcdf_chunk_close.restype = None
         L.dcdf_free_superchunk.argtypes = [C.c_void_p]
         L.dcdf_free_superchunk.restype = None
+        # value search: the real-valued bounds are doubles (ctypes would pass a Python float as one only when told)
+        L.dcdf_value_bounds.restype = C.c_int
+        L.dcdf_value_bounds.argtypes = [C.c_int32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int32)]
+        L.dcdf_chunk_search_values.restype = C.c_int
+        L.dcdf_chunk_search_values.argtypes = [C.c_void_p, C.POINTER(Cube), C.c_double, C.c_double, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
+
+
+def value_bounds(encoding, fractional_bits, lower, upper):
+    """dcdf_value_bounds (host only, no GPU): (lo, hi, skip_zero) -- the stored integers of a chunk of this encoding and these
+    fractional bits whose typed value lies in [lower, upper], less 0 when skip_zero; lo > hi when none does."""
+    lo, hi, sz = C.c_int64(), C.c_int64(), C.c_int32()
+    check(lib().dcdf_value_bounds(int(encoding), int(fractional_bits), float(lower), float(upper), C.byref(lo), C.byref(hi), C.byref(sz)),
+          "value_bounds")
+    return lo.value, hi.value, bool(sz.value)
 
 
 def check(rc, what=""):

@@ -3,6 +3,7 @@
 Same names, argument meaning and error behaviour as the reference for this path:
   Chunk.build(buffer, shape, k)      chunk.rs:42     -> MMStruct3Build (mmstruct.rs:24-34)
   Chunk.get / fill_cell / fill_window / iter_search   chunk.rs:127,135,152,213
+  Chunk.search_values (real-valued bounds; the reference's float search is todo!(), mmarray.rs:407-417, 511-521)
   Chunk.shape / size / write_to / read_from           chunk.rs:119,272,235,247
   geom.Rect / geom.Cube (auto-reordered bounds)       geom.rs
 Panics of the reference surface as DcdfError (negative code)."""
@@ -260,6 +261,22 @@ class Chunk:
             L.check(rc, "Chunk::iter_search")
             return out[:n.value]
 
+    def search_values(self, bounds, lower, upper):
+        """Value search (dcdf_chunk_search_values): the cells whose typed value -- what fill_window returns -- lies in
+        [lower, upper] (real numbers; +-inf unbounded, NaN cells never match), as iter_search's sorted triples."""
+        c = bounds._c()
+        n = C.c_size_t()
+        cap = 1 << 16
+        while True:
+            out = np.zeros((cap, 3), dtype=np.uint32)
+            rc = L.lib().dcdf_chunk_search_values(self._h, C.byref(c), float(lower), float(upper), C.c_void_p(out.ctypes.data),
+                                                  C.c_size_t(cap), C.byref(n))
+            if rc == -11:  # DCDF_ERR_CAPACITY
+                cap = n.value
+                continue
+            L.check(rc, "Chunk::search_values")
+            return out[:n.value]
+
 
 def _handles(chunks):
     return (C.c_void_p * len(chunks))(*[c._h for c in chunks])
@@ -314,6 +331,28 @@ def fill_window_batch(chunks, cubes, dtype=np.int64, out_device_ptr=None, out_of
                                                        _ENC[dtype], L.MEM_DEVICE, C.c_void_p(off.ctypes.data), C.byref(ms)),
             "fill_window_batch")
     return ms.value
+
+
+def search_values_batch(chunks, cubes, lower, upper, out_device_ptr=None, cap=None):
+    """Value search of many (chunk, Cube, lower, upper) in one launch (dcdf_query_search_values_batch): each query's real-valued
+    bounds are translated with its own chunk's encoding and fractional bits.  Returns (triples uint32[hits, 3] -- None when they
+    stay on the device at out_device_ptr --, offsets, counts, kernel ms); query q's sorted triples are triples[offsets[q]:][:counts[q]].
+    cap (triples) defaults to the cells of all cubes."""
+    n = len(cubes)
+    cub = (L.Cube * n)(*[c._c() for c in cubes])
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,)))
+    if cap is None:
+        cap = sum(c.instants() * c.rows() * c.cols() for c in cubes)
+    counts = np.zeros(n, dtype=np.uint64)
+    offs = np.zeros(n, dtype=np.uint64)
+    trip = None if out_device_ptr else np.empty((max(cap, 1), 3), dtype=np.uint32)
+    ms = C.c_float()
+    L.check(L.lib().dcdf_query_search_values_batch(_handles(chunks), cub, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data),
+                                                   C.c_size_t(n), C.c_void_p(out_device_ptr or trip.ctypes.data), C.c_size_t(cap),
+                                                   L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.c_void_p(counts.ctypes.data),
+                                                   C.c_void_p(offs.ctypes.data), C.byref(ms)), "search_values_batch")
+    return trip, offs, counts, ms.value
 
 
 # py-dcdf flavoured helpers (SURVEY 8b "Python shape")

@@ -127,6 +127,11 @@ K2R_HD int64_t inst_get(const uint8_t* b, const InstDesc* descs, uint32_t i, uin
     return log_get(b, descs[D.snap], D, row, col);
 }
 
+// from_fixed (fixed.rs:81-86) of a stored value v != 0 (0 is the NaN code), in the precision of the typed result: the one
+// definition store_typed and value_bounds share
+K2R_HD float from_fixed_f32(int64_t v, uint32_t fbits) { return (float)(v - 1) / (float)((int64_t)1 << (fbits + 1)); }
+K2R_HD double from_fixed_f64(int64_t v, uint32_t fbits) { return (double)(v - 1) / (double)((int64_t)1 << (fbits + 1)); }
+
 // MMBuffer3::set conversions (mmbuffer.rs:505,525,560,622; fixed.rs:81-86)
 K2R_HD void store_typed(void* out, int64_t off, int32_t dtype, int64_t v, uint32_t fbits) {
     switch (dtype) {
@@ -135,18 +140,105 @@ K2R_HD void store_typed(void* out, int64_t off, int32_t dtype, int64_t v, uint32
         case ENC_F32: {
             float f;
             if (v == 0) f = __builtin_nanf("");
-            else f = (float)(v - 1) / (float)((int64_t)1 << (fbits + 1));
+            else f = from_fixed_f32(v, fbits);
             ((float*)out)[off] = f;
             break;
         }
         default: {
             double f;
             if (v == 0) f = __builtin_nan("");
-            else f = (double)(v - 1) / (double)((int64_t)1 << (fbits + 1));
+            else f = from_fixed_f64(v, fbits);
             ((double*)out)[off] = f;
             break;
         }
     }
+}
+
+// ---- value search: real-valued bounds -> the stored integers that match --------------------------------------------------
+// A cell matches [lower, upper] iff the value the typed fill_window returns for it, v, satisfies lower <= v <= upper exactly:
+// v = from_fixed in the chunk's float type (NaN for stored 0: never a match) or the stored integer itself.  v is monotone
+// non-decreasing in the stored n (rounding is monotone), so the matching n form one interval [lo, hi], less n = 0 for floats
+// when the interval holds it (`hole`, normalised so that it is only set when lo < 0 < hi).  float32 collapses many n into one
+// value once |n - 1| > 2^24, so the ends are found by bisection with the decoder's own expression, not by a closed form.
+struct ValueRange {
+    int64_t lo, hi;
+    bool hole;   // stored 0 lies in [lo, hi] and is not a match
+    bool empty;  // nothing matches (lo > hi)
+};
+// v(n) >= x (ge) or v(n) > x (!ge), exactly: a float32 value converts to double exactly
+K2R_HD bool vb_above(int32_t enc, uint32_t fbits, int64_t n, double x, bool ge) {
+    const double v = enc == ENC_F32 ? (double)from_fixed_f32(n, fbits) : from_fixed_f64(n, fbits);
+    return ge ? v >= x : v > x;
+}
+// the smallest n of [INT64_MIN + 1, INT64_MAX] with vb_above(n) (the predicate is monotone in n); *none when there is none
+K2R_HD int64_t vb_first(int32_t enc, uint32_t fbits, double x, bool ge, bool* none) {
+    int64_t lo = INT64_MIN + 1, hi = INT64_MAX;  // (INT64_MIN - 1 overflows in from_fixed; to_fixed never stores INT64_MIN)
+    *none = !vb_above(enc, fbits, hi, x, ge);
+    if (*none) return 0;
+    while (lo < hi) {  // at most 64 steps
+        const int64_t mid = lo + (int64_t)(((uint64_t)hi - (uint64_t)lo) >> 1);
+        if (vb_above(enc, fbits, mid, x, ge)) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+// false: bad argument (a NaN bound, an unknown encoding, float fractional bits beyond what from_fixed defines: > 62, the
+// limit Chunk::build enforces).  Reversed bounds are swapped; +-inf is unbounded.
+K2R_HD bool value_bounds(int32_t enc, uint32_t fbits, double lower, double upper, ValueRange* r) {
+    r->lo = 1;
+    r->hi = 0;
+    r->hole = false;
+    r->empty = true;
+    if (lower != lower || upper != upper) return false;
+    if (enc != ENC_I32 && enc != ENC_I64 && enc != ENC_F32 && enc != ENC_F64) return false;
+    if ((enc == ENC_F32 || enc == ENC_F64) && fbits > 62) return false;
+    if (lower > upper) {
+        const double x = lower;
+        lower = upper;
+        upper = x;
+    }
+    int64_t lo, hi;
+    constexpr double two63 = 9223372036854775808.0;
+    if (enc == ENC_I32 || enc == ENC_I64) {  // n in [ceil(lower), floor(upper)]; n itself is never rounded to double
+        const double cl = __builtin_ceil(lower), fu = __builtin_floor(upper);
+        if (cl >= two63 || fu < -two63) return true;
+        lo = cl <= -two63 ? INT64_MIN : (int64_t)cl;
+        hi = fu >= two63 ? INT64_MAX : (int64_t)fu;
+        if (enc == ENC_I32) {
+            if (lo < INT32_MIN) lo = INT32_MIN;
+            if (hi > INT32_MAX) hi = INT32_MAX;
+        }
+    } else {
+        bool none = false;
+        if (lower == -__builtin_inf()) {
+            lo = INT64_MIN;
+        } else {
+            lo = vb_first(enc, fbits, lower, true, &none);  // min{n : v(n) >= lower}
+            if (none) return true;
+        }
+        if (upper == __builtin_inf()) {
+            hi = INT64_MAX;
+        } else {
+            const int64_t above = vb_first(enc, fbits, upper, false, &none);  // max{n : v(n) <= upper} = min{n : v(n) > upper} - 1
+            if (none) hi = INT64_MAX;
+            else if (above == INT64_MIN + 1) return true;
+            else hi = above - 1;
+        }
+        if (lo <= 0 && 0 <= hi) {  // the NaN code: only a hole strictly inside the interval stays a hole
+            if (lo == 0 && hi == 0) return true;
+            if (lo == 0) lo = 1;
+            else if (hi == 0) hi = -1;
+            else r->hole = true;
+        }
+    }
+    if (lo > hi) {
+        r->hole = false;
+        return true;
+    }
+    r->lo = lo;
+    r->hi = hi;
+    r->empty = false;
+    return true;
 }
 
 }  // namespace k2r

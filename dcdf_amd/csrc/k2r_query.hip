@@ -466,6 +466,10 @@ __device__ __forceinline__ bool search_child(const uint8_t* b, const InstDesc& S
     o->bs = 1 + rs * k2;
     return false;
 }
+// VALUE: a value search (dcdf_*_search_values): [lower, upper] are the stored integers value_bounds gave, the reference quirk is
+// off (the true values are searched) and SearchExtra::quirk carries the hole instead: stored 0 inside the range is no match, so
+// no subtree whose range holds 0 is taken whole.
+template <bool VALUE = false>
 __global__ void __launch_bounds__(256)
 k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ items, uint32_t n_items, const SearchExtra* __restrict__ sx,
               uint32_t* __restrict__ bits, uint32_t* __restrict__ counts) {
@@ -479,13 +483,22 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
         const ChunkRef C = chunks[I.chunk];
         const uint8_t* const b = C.bytes;
         const InstDesc& D = C.descs[I.inst];
-        const bool quirk = X.quirk != 0;
+        const bool quirk = !VALUE && X.quirk != 0;
         const bool has_log = D.is_log != 0 && !quirk;
         const InstDesc& S = D.is_log != 0 ? C.descs[D.snap] : D;
         const InstDesc* const L = has_log ? &D : nullptr;
         const uint32_t k = D.k, k2 = k * k;
         const uint32_t wtop = I.top, wbot = I.bottom, wleft = I.left, wright = I.right;
         const int64_t lower = X.lower, upper = X.upper;
+        // (the integer instantiation's tests are exactly the plain comparisons)
+        auto in_range = [&](int64_t v) {
+            if constexpr (VALUE) return lower <= v && v <= upper && !(X.quirk != 0 && v == 0);
+            else return lower <= v && v <= upper;
+        };
+        auto all_in = [&](int64_t mn, int64_t mx) {
+            if constexpr (VALUE) return mn >= lower && mx <= upper && !(X.quirk != 0 && mn <= 0 && 0 <= mx);
+            else return mn >= lower && mx <= upper;
+        };
         uint32_t cnt = 0;
         // I.out_off = bit index of cell (top, left) in the item's flat window bitmap, I.out_sr = the window's width
         auto mark = [&](uint32_t r, uint32_t c) {
@@ -516,7 +529,7 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
             const bool all_one = has_log ? (single_t && (single_s || !bmd_get(b, L->E, 0))) : single_s;
             if (all_one) {
                 const int64_t v = max_t0 + max_s0;
-                if (lower <= v && v <= upper) mark_wave(wtop, wbot, wleft, wright);
+                if (in_range(v)) mark_wave(wtop, wbot, wleft, wright);
                 done = true;
             }
         }
@@ -551,9 +564,9 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
                         if (r0 < r1 && c0 < c1) {
                             int64_t mn = 0, mx = 0;
                             const bool one = search_child(b, S, L, p, myc, k2, &o, &mn, &mx);
-                            if (one) fill = lower <= mx && mx <= upper;
+                            if (one) fill = in_range(mx);
                             else if (mx < lower || mn > upper) fill = false;      // nothing of this subtree is in range
-                            else if (mn >= lower && mx <= upper) fill = true;     // all of it is
+                            else if (all_in(mn, mx)) fill = true;                 // all of it is
                             else push = true;
                             org = (cr << 16) | cc;
                         }
@@ -600,13 +613,13 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
                     int64_t mn = 0, mx = 0;
                     const bool one = search_child(b, S, L, p, myc, k2, &o, &mn, &mx);
                     if (one || cs == 1) {  // (a cell is always a leaf of both trees)
-                        if (lower <= mx && mx <= upper)
+                        if (in_range(mx))
                             for (uint32_t r = r0; r < r1; r++)
                                 for (uint32_t c = c0; c < c1; c++) mark(r, c);
                         continue;
                     }
                     if (mx < lower || mn > upper) continue;
-                    if (mn >= lower && mx <= upper) {
+                    if (all_in(mn, mx)) {
                         for (uint32_t r = r0; r < r1; r++)
                             for (uint32_t c = c0; c < c1; c++) mark(r, c);
                         continue;
@@ -616,7 +629,7 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
                         for (uint32_t r = r0; r < r1; r++)
                             for (uint32_t c = c0; c < c1; c++) {
                                 const int64_t v = inst_get(b, C.descs, quirk ? D.snap : I.inst, r, c) + shift;
-                                if (lower <= v && v <= upper) mark(r, c);
+                                if (in_range(v)) mark(r, c);
                             }
                         continue;
                     }
@@ -625,7 +638,7 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
                             SearchSt oo{};
                             int64_t vn = 0, v = 0;
                             (void)search_child(b, S, L, o, (r - cr) * k + (c - cc), k2, &oo, &vn, &v);
-                            if (lower <= v && v <= upper) mark(r, c);
+                            if (in_range(v)) mark(r, c);
                         }
                 }
             }
@@ -817,7 +830,10 @@ typedef WaveQ2T<int64_t> WaveQ2;
 // MW = waves per SIMD the register allocator must leave room for (4 for the 32-bit walk; the 64-bit one's frontier leaves LDS
 // for 3 workgroups per CU, so it is built for 3); DENSE64: the batched form's output (int64, unit column stride);
 // SEARCH: mark matches (out = the bitmaps, sx = one SearchExtra per item) instead of storing values
-template <int MW, bool DENSE64, bool SEARCH = false, class V = int64_t, bool USE_TOP = true>
+// VALUE (with SEARCH): a value search, as in k_search_wave: no quirk, SearchExtra::quirk is the hole.  (A raster piece whose bounds
+// translate to no stored integer comes as [INT64_MAX, INT64_MIN]: every side-16 square is skipped at once.  An early exit for it
+// here costs 18 VGPRs and spills this walk's 64-bit form.)
+template <int MW, bool DENSE64, bool SEARCH = false, class V = int64_t, bool USE_TOP = true, bool VALUE = false>
 __global__ void __launch_bounds__(256, MW)
 k_window_wave2(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ items, uint32_t n_items, void* out, int32_t out_dtype,
                const SearchExtra* __restrict__ sx = nullptr) {
@@ -844,11 +860,12 @@ k_window_wave2(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ 
         const uint32_t wtop = I.top, wbot = I.bottom, wleft = I.left, wright = I.right, osr = I.out_sr;
         const int64_t obase = (int64_t)I.out_off - (int64_t)wtop * osr - (int64_t)wleft;  // element offset of chunk cell (0, 0)
         int64_t s_lo = 0, s_hi = 0;
-        bool quirk = false;
+        bool quirk = false, hole = false;
         if (SEARCH) {
             s_lo = sx[item].lower;
             s_hi = sx[item].upper;
-            quirk = __builtin_amdgcn_readfirstlane((int)sx[item].quirk) != 0;
+            if constexpr (VALUE) hole = __builtin_amdgcn_readfirstlane((int)sx[item].quirk) != 0;
+            else quirk = __builtin_amdgcn_readfirstlane((int)sx[item].quirk) != 0;
             rowbits[2 * lane] = 0;
             rowbits[2 * lane + 1] = 0;
             __builtin_amdgcn_wave_barrier();
@@ -856,7 +873,11 @@ k_window_wave2(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ 
         auto put = [&](uint32_t r, uint32_t c, int64_t v) {
             if (SEARCH) {
                 const uint32_t j = c - wleft;
-                if (s_lo <= v && v <= s_hi) atomicOr(&rowbits[2 * (r - wtop) + (j >> 5)], 1u << (j & 31u));
+                if constexpr (VALUE) {
+                    if (s_lo <= v && v <= s_hi && !(hole && v == 0)) atomicOr(&rowbits[2 * (r - wtop) + (j >> 5)], 1u << (j & 31u));
+                } else {
+                    if (s_lo <= v && v <= s_hi) atomicOr(&rowbits[2 * (r - wtop) + (j >> 5)], 1u << (j & 31u));
+                }
                 return;
             }
             const int64_t off = obase + (int64_t)(r * osr + c);
@@ -872,7 +893,9 @@ k_window_wave2(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ 
         };
         auto fill_wave = [&](uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, int64_t v) {
             if (SEARCH) {  // (v is wave-uniform) a rectangle of one value: whole row segments at once
-                if (s_lo <= v && v <= s_hi && (uint32_t)lane < r1 - r0 && c1 > c0) {
+                bool hit = s_lo <= v && v <= s_hi;
+                if constexpr (VALUE) hit = hit && !(hole && v == 0);
+                if (hit && (uint32_t)lane < r1 - r0 && c1 > c0) {
                     const uint32_t w1 = c1 - c0;
                     const uint64_t m = (w1 >= 64u ? ~0ull : ((1ull << w1) - 1ull)) << (c0 - wleft);
                     uint32_t* const rw = &rowbits[2 * (r0 - wtop + (uint32_t)lane)];
@@ -916,6 +939,7 @@ k_window_wave2(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ 
                 const int64_t vmin = m->vmin, vmax = m->vmax;
                 skip = vmax < s_lo || vmin > s_hi;
                 force = !skip && s_lo <= vmin && vmax <= s_hi;
+                if constexpr (VALUE) force = force && !(hole && vmin <= 0 && 0 <= vmax);  // (the hole is inside: descend)
             }
             const bool isfill = mine && !skip && !force && ebt == WQ_NONE && ebs == WQ_NONE;
             const bool push = mine && !skip && !force && !isfill;
@@ -1419,6 +1443,8 @@ __global__ void __launch_bounds__(256) k_slab_pack(const SlabItem* __restrict__ 
 // window bitmap.  The reference's search is a pruned descent whose result is exactly that set (its bounds are true bounds) --
 // except for the single-node-uniform-log shape of SearchExtra, which is evaluated here as the data it is: all cells, no cell, or
 // the cells with lower <= s(cell) + (c - max_s(root)) <= upper.
+// VALUE: a value search, as in k_search_wave (quirk[] holds the items' hole flags)
+template <bool VALUE = false>
 __global__ void __launch_bounds__(64)
 k_search_cells(const ChunkRef* __restrict__ chunks, const WinQuery* __restrict__ qs, const SearchItem* __restrict__ items,
                uint32_t n_items, const uint8_t* __restrict__ quirk, uint32_t* __restrict__ bits, uint32_t* __restrict__ counts) {
@@ -1436,7 +1462,9 @@ k_search_cells(const ChunkRef* __restrict__ chunks, const WinQuery* __restrict__
     bool all = false, none = false;
     int64_t shift = 0;
     uint32_t from = I.instant;
-    if (quirk[it]) {  // (log.rs:527-586 on this shape)
+    bool hole = false;
+    if constexpr (VALUE) hole = quirk[it] != 0;
+    if (!VALUE && quirk[it]) {  // (log.rs:527-586 on this shape)
         const InstDesc& S = C.descs[D.snap];
         const int64_t max_s0 = dacd_get(b, S.mx, 0), min_s0 = dacd_get(b, S.mn, 0), c1 = dacd_get(b, D.mx, 0) + max_s0;
         all = min_s0 >= Q.lower && c1 <= Q.upper;
@@ -1451,6 +1479,7 @@ k_search_cells(const ChunkRef* __restrict__ chunks, const WinQuery* __restrict__
             if (!all) {
                 const int64_t v = inst_get(b, C.descs, from, Q.top + e / wc, Q.left + e % wc) + shift;
                 hit = Q.lower <= v && v <= Q.upper;
+                if constexpr (VALUE) hit = hit && !(hole && v == 0);
             }
             if (hit) {
                 atomicOr(&bw[e >> 5], 1u << (e & 31u));
@@ -2158,9 +2187,13 @@ struct SearchCtx {  // a raster's view of its chunks (dcdf_raster_search_batch):
     bool wave_ok;              // every chunk has k * k <= 64 (k_search_wave for the arities the node walk does not take)
 };
 
+// vlower / vupper (value search, lower / upper unused): real-valued bounds, translated per query with the chunk's encoding and
+// fractional bits (value_bounds); the walks then run their VALUE instantiations
 static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper,
                        size_t nq, uint32_t* out, size_t cap, uint64_t* counts, uint64_t* offsets, size_t* total_out,
-                       float* kernel_ms, int out_mem = DCDF_MEM_HOST, const SearchCtx* ctx = nullptr) {
+                       float* kernel_ms, int out_mem = DCDF_MEM_HOST, const SearchCtx* ctx = nullptr,
+                       const double* vlower = nullptr, const double* vupper = nullptr) {
+    const bool value = vlower != nullptr;
     std::vector<uint32_t> cidx;
     std::vector<const dcdf_chunk*> uniq;
     if (!ctx) dedup_chunks(chunks, nq, cidx, uniq);
@@ -2194,8 +2227,26 @@ static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const 
             Q.out_off = (uint64_t)ctx->origin[3 * q + 1] | (uint64_t)ctx->origin[3 * q + 2] << 32;
         }
         Q.start = c.start; Q.end = c.end; Q.top = c.top; Q.bottom = c.bottom; Q.left = c.left; Q.right = c.right;
-        Q.lower = std::min(lower[q], upper[q]);  // helpers.rs:7-16 via chunk.rs:214
-        Q.upper = std::max(lower[q], upper[q]);
+        bool hole = false;
+        if (value) {
+            ValueRange vr;
+            if (!value_bounds(chunks[q]->encoding, chunks[q]->fbits, vlower[q], vupper[q], &vr)) return DCDF_ERR_BAD_ARG;
+            // a narrow chunk's values all lie in [-2^30, 2^30): its walk needs no more than the int32 part of the range
+            if (!vr.empty && chunks[q]->narrow32) {
+                vr.lo = std::max<int64_t>(vr.lo, INT32_MIN);
+                vr.hi = std::min<int64_t>(vr.hi, INT32_MAX);
+                vr.empty = vr.lo > vr.hi;
+            }
+            Q.lower = vr.lo;
+            Q.upper = vr.hi;
+            hole = vr.hole;
+            if (vr.empty) continue;  // no items: nothing can match
+        } else {
+            Q.lower = std::min(lower[q], upper[q]);  // helpers.rs:7-16 via chunk.rs:214
+            Q.upper = std::max(lower[q], upper[q]);
+        }
+        // the per-item flag of the walks: the reference quirk of the instant, or (value search) the hole
+        auto flag = [&](uint32_t i) -> uint8_t { return value ? (hole ? 1 : 0) : chunks[q]->search_quirk[i]; };
         const uint64_t cells = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
         if (cells == 0) continue;
         const uint32_t ncb = (c.right - c.left + 63u) >> 6;
@@ -2213,12 +2264,12 @@ static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const 
                         it.left = (uint16_t)cc;
                         it.right = (uint16_t)std::min(cc + 64, c.right);
                         witems.push_back(it);
-                        sx.push_back(SearchExtra{Q.lower, Q.upper, chunks[q]->search_quirk[i] ? 1u : 0u, 0u});
+                        sx.push_back(SearchExtra{Q.lower, Q.upper, flag(i) ? 1u : 0u, 0u});
                     }
             } else {
                 items.push_back(SearchItem{(uint32_t)q, i, bits_words, SI_FLAT, 0});
                 item_quirk.resize(items.size(), 0);
-                item_quirk.back() = chunks[q]->search_quirk[i];
+                item_quirk.back() = flag(i);
                 if (wave_search) {
                     if (witems.size() + 4096 > 0xffffff00u) return DCDF_ERR_CAPACITY;
                     const uint32_t wc = c.right - c.left;
@@ -2234,7 +2285,7 @@ static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const 
                             it.out_sr = wc;  // bit (r, c) of the item's bitmap = out_off + (r - top) * out_sr + (c - left)
                             it.out_off = bits_words * 32ull + (uint64_t)(it.top - c.top) * wc + (it.left - c.left);
                             witems.push_back(it);
-                            sx.push_back(SearchExtra{Q.lower, Q.upper, chunks[q]->search_quirk[i] ? 1u : 0u, (uint32_t)(items.size() - 1)});
+                            sx.push_back(SearchExtra{Q.lower, Q.upper, flag(i) ? 1u : 0u, (uint32_t)(items.size() - 1)});
                         }
                 }
                 bits_words += (cells + 31) / 32;
@@ -2275,18 +2326,29 @@ static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const 
         const hipEvent_t e0 = ev.e0, e1 = ev.e1;
         const uint32_t ni = (uint32_t)items.size();
         K2R_HIP(hipEventRecord(e0, 0));
+        const uint32_t gw = std::min<uint32_t>((nw + 3) / 4, 256u * 16u);
         if (nw && wave_search) {
-            hipLaunchKernelGGL(k_search_wave, dim3(std::min<uint32_t>((nw + 3) / 4, 256u * 16u)), dim3(256), 0, 0, d_refs.as<ChunkRef>(),
-                               d_witems.as<WinItem>(), nw, d_sx.as<SearchExtra>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
+            if (value)
+                hipLaunchKernelGGL(k_search_wave<true>, dim3(gw), dim3(256), 0, 0, d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw,
+                                   d_sx.as<SearchExtra>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
+            else
+                hipLaunchKernelGGL(k_search_wave<false>, dim3(gw), dim3(256), 0, 0, d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw,
+                                   d_sx.as<SearchExtra>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
         } else if (nw) {
             bool all_narrow = true;
             for (const dcdf_chunk* u : uniq) all_narrow = all_narrow && u->narrow32;
             if (ctx) all_narrow = ctx->all_narrow;
-            if (all_narrow)
-                hipLaunchKernelGGL((k_window_wave2<4, false, true, int32_t>), dim3(std::min<uint32_t>((nw + 3) / 4, 256u * 16u)), dim3(256), 0, 0,
+            if (all_narrow && value)
+                hipLaunchKernelGGL((k_window_wave2<4, false, true, int32_t, true, true>), dim3(gw), dim3(256), 0, 0,
+                                   d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
+            else if (value)
+                hipLaunchKernelGGL((k_window_wave2<3, false, true, int64_t, true, true>), dim3(gw), dim3(256), 0, 0,
+                                   d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
+            else if (all_narrow)
+                hipLaunchKernelGGL((k_window_wave2<4, false, true, int32_t>), dim3(gw), dim3(256), 0, 0,
                                    d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
             else
-                hipLaunchKernelGGL((k_window_wave2<3, false, true>), dim3(std::min<uint32_t>((nw + 3) / 4, 256u * 16u)), dim3(256), 0, 0,
+                hipLaunchKernelGGL((k_window_wave2<3, false, true>), dim3(gw), dim3(256), 0, 0,
                                    d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
             hipLaunchKernelGGL(k_search_count, dim3((ni + 63) / 64), dim3(64), 0, 0, d_wbits.as<uint32_t>(), d_items.as<SearchItem>(),
                                d_qs.as<WinQuery>(), ni, d_counts.as<uint32_t>());
@@ -2295,8 +2357,12 @@ static int search_impl(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const 
             item_quirk.resize(items.size(), 0);
             K2R_HIP(d_quirk.alloc(items.size()));
             K2R_HIP(hipMemcpy(d_quirk.p, item_quirk.data(), items.size(), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_search_cells, dim3(ni), dim3(64), 0, 0, d_refs.as<ChunkRef>(), d_qs.as<WinQuery>(),
-                               d_items.as<SearchItem>(), ni, d_quirk.as<uint8_t>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
+            if (value)
+                hipLaunchKernelGGL(k_search_cells<true>, dim3(ni), dim3(64), 0, 0, d_refs.as<ChunkRef>(), d_qs.as<WinQuery>(),
+                                   d_items.as<SearchItem>(), ni, d_quirk.as<uint8_t>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
+            else
+                hipLaunchKernelGGL(k_search_cells<false>, dim3(ni), dim3(64), 0, 0, d_refs.as<ChunkRef>(), d_qs.as<WinQuery>(),
+                                   d_items.as<SearchItem>(), ni, d_quirk.as<uint8_t>(), d_bits.as<uint32_t>(), d_counts.as<uint32_t>());
         }
         K2R_HIP(hipEventRecord(e1, 0));
         K2R_HIP(hipGetLastError());
@@ -2352,6 +2418,30 @@ extern "C" int dcdf_chunk_search(const dcdf_chunk* h, const dcdf_cube* cube, int
     const int rc = search_impl(&hp, cube, &lower, &upper, 1, out, cap, &cnt, &off, &total, nullptr);
     *n = total;
     return rc;
+}
+
+// value search (real-valued bounds, translated per chunk by value_bounds on the host; see dcdf_k2r.h)
+extern "C" int dcdf_chunk_search_values(const dcdf_chunk* h, const dcdf_cube* cube, double lower, double upper, uint32_t* out, size_t cap,
+                                        size_t* n) {
+    if (!h || !cube || !n || (!out && cap)) return DCDF_ERR_BAD_ARG;
+    if (lower != lower || upper != upper) return DCDF_ERR_BAD_ARG;
+    if (!Runtime::get().ok) return DCDF_ERR_NO_DEVICE;
+    dcdf_chunk* hp = const_cast<dcdf_chunk*>(h);
+    uint64_t cnt = 0, off = 0;
+    size_t total = 0;
+    const int rc = search_impl(&hp, cube, nullptr, nullptr, 1, out, cap, &cnt, &off, &total, nullptr, DCDF_MEM_HOST, nullptr, &lower, &upper);
+    *n = total;
+    return rc;
+}
+extern "C" int dcdf_value_bounds(int32_t encoding, uint32_t fractional_bits, double lower, double upper, int64_t* lo, int64_t* hi,
+                                 int32_t* skip_zero) {
+    if (!lo || !hi || !skip_zero) return DCDF_ERR_BAD_ARG;
+    ValueRange vr;
+    if (!value_bounds(encoding, fractional_bits, lower, upper, &vr)) return DCDF_ERR_BAD_ARG;
+    *lo = vr.lo;
+    *hi = vr.hi;
+    *skip_zero = vr.hole ? 1 : 0;
+    return DCDF_OK;
 }
 
 extern "C" int dcdf_query_search_batch(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const int64_t* lower,
@@ -2456,6 +2546,15 @@ extern "C" int dcdf_query_search_batch_mem(dcdf_chunk* const* chunks, const dcdf
     size_t total = 0;
     return search_impl(chunks, cubes, lower, upper, nq, out, cap, counts, offsets, &total, kernel_ms, out_mem);
 }
+extern "C" int dcdf_query_search_values_batch(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const double* lower, const double* upper,
+                                              size_t nq, uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets,
+                                              float* kernel_ms) {
+    if (!chunks || !cubes || !lower || !upper || !counts || !offsets || nq == 0 || (!out && cap)) return DCDF_ERR_BAD_ARG;
+    if (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) return DCDF_ERR_BAD_ARG;
+    if (!Runtime::get().ok) return DCDF_ERR_NO_DEVICE;
+    size_t total = 0;
+    return search_impl(chunks, cubes, nullptr, nullptr, nq, out, cap, counts, offsets, &total, kernel_ms, out_mem, nullptr, lower, upper);
+}
 extern "C" int dcdf_query_fill_window_batch(dcdf_chunk* const* chunks, const dcdf_cube* cubes, size_t nq, int64_t* out,
                                             const uint64_t* out_offset, float* kernel_ms) {
     return fill_window_batch_impl(chunks, cubes, nq, out, (int32_t)DCDF_I64, DCDF_MEM_HOST, out_offset, kernel_ms);
@@ -2481,7 +2580,9 @@ struct dcdf_raster {
     uint32_t T = 0, R = 0, C = 0, tile = 0, cs = 0, nseg = 0, nti = 0, ntj = 0;
     DevBuf d_refs;
     DevBuf d_quirk;  // [chunk][chunk_size]: dcdf_chunk::search_quirk of every instant (k_raster_search_expand)
+    DevBuf d_enc;    // [chunk]: the chunk's encoding (value search translates its bounds per piece on the device)
     bool all_wave = true, all_node = true, all_narrow = true;
+    bool bad_fbits = false;  // a float chunk with fractional bits value_bounds does not take (> 62)
 };
 extern "C" int dcdf_raster_create(dcdf_chunk* const* chunks, size_t n_chunks, const uint32_t shape[3], uint32_t tile, uint32_t chunk_size,
                                   dcdf_raster** out) {
@@ -2518,6 +2619,13 @@ extern "C" int dcdf_raster_create(dcdf_chunk* const* chunks, size_t n_chunks, co
         for (size_t t = 0; t < chunks[i]->search_quirk.size() && t < chunk_size; t++) quirk[i * chunk_size + t] = chunks[i]->search_quirk[t];
     K2R_HIP(r->d_quirk.alloc(quirk.size()));
     K2R_HIP(hipMemcpy(r->d_quirk.p, quirk.data(), quirk.size(), hipMemcpyHostToDevice));
+    std::vector<uint8_t> enc(n_chunks);
+    for (size_t i = 0; i < n_chunks; i++) {
+        enc[i] = (uint8_t)chunks[i]->encoding;
+        if ((enc[i] == DCDF_F32 || enc[i] == DCDF_F64) && chunks[i]->fbits > 62) r->bad_fbits = true;
+    }
+    K2R_HIP(r->d_enc.alloc(n_chunks));
+    K2R_HIP(hipMemcpy(r->d_enc.p, enc.data(), n_chunks, hipMemcpyHostToDevice));
     *out = r.release();
     return DCDF_OK;
 }
@@ -2659,11 +2767,18 @@ extern "C" int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cu
 // ---- search of dataset-level cubes with everything but a count per cube on the device ---------------------------------
 // One thread per cube writes what search_impl builds on the host: a WinQuery per chunk-level piece (with the chunk's origin
 // for the emit kernel), a SearchItem per (piece, instant), a WinItem + SearchExtra per <= 64 x 64 part of it.
-__global__ void __launch_bounds__(256)
-k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __restrict__ lower, const int64_t* __restrict__ upper,
-                       const uint32_t* __restrict__ sb, const uint32_t* __restrict__ ib, const uint32_t* __restrict__ wb, uint32_t nq, RasterGeom g,
-                       const uint8_t* __restrict__ quirk, WinQuery* __restrict__ qs, SearchItem* __restrict__ items, WinItem* __restrict__ witems,
-                       SearchExtra* __restrict__ sx) {
+// VALUE: the cube's bounds are real values (vlower / vupper); each piece translates them with its chunk's encoding (enc) and
+// fractional bits (value_bounds, the definition the host uses), the per-item flag is the hole instead of the reference quirk, and
+// a piece whose range is empty (or, narrow: misses the int32 range its walk covers) gets [INT64_MAX, INT64_MIN]: nothing matches
+// and the walk's side-16 table prunes every square of it.
+template <bool VALUE>
+__device__ __forceinline__ void raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __restrict__ lower,
+                                                     const int64_t* __restrict__ upper, const double* __restrict__ vlower,
+                                                     const double* __restrict__ vupper, const uint32_t* __restrict__ sb,
+                                                     const uint32_t* __restrict__ ib, const uint32_t* __restrict__ wb, uint32_t nq, RasterGeom g,
+                                                     const uint8_t* __restrict__ quirk, const ChunkRef* __restrict__ refs,
+                                                     const uint8_t* __restrict__ enc, bool narrow, WinQuery* __restrict__ qs,
+                                                     SearchItem* __restrict__ items, WinItem* __restrict__ witems, SearchExtra* __restrict__ sx) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
     dcdf_cube c = cubes[q];
@@ -2671,7 +2786,11 @@ k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __res
     if (c.top > c.bottom) { const uint32_t x = c.top; c.top = c.bottom; c.bottom = x; }
     if (c.left > c.right) { const uint32_t x = c.left; c.left = c.right; c.right = x; }
     if ((uint64_t)(c.end - c.start) * (c.bottom - c.top) * (c.right - c.left) == 0) return;
-    const int64_t lo = min(lower[q], upper[q]), hi = max(lower[q], upper[q]);  // helpers.rs:7-16 via chunk.rs:214
+    int64_t lo = 0, hi = 0;
+    if (!VALUE) {
+        lo = min(lower[q], upper[q]);  // helpers.rs:7-16 via chunk.rs:214
+        hi = max(lower[q], upper[q]);
+    }
     uint32_t s = sb[q], it = ib[q], w = wb[q];
     for (uint32_t seg = c.start / g.cs; seg <= (c.end - 1) / g.cs; seg++)
         for (uint32_t ti = c.top / g.tile; ti <= (c.bottom - 1) / g.tile; ti++)
@@ -2680,6 +2799,19 @@ k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __res
                 const uint32_t ls = max(c.start, t0) - t0, le = min(c.end, t0 + g.cs) - t0, lt = max(c.top, r0) - r0, lb = min(c.bottom, r0 + g.tile) - r0,
                                ll = max(c.left, c0) - c0, lr = min(c.right, c0 + g.tile) - c0;
                 const uint32_t cid = (seg * g.nti + ti) * g.ntj + tj;
+                bool hole = false;
+                if (VALUE) {
+                    ValueRange vr;
+                    (void)value_bounds((int32_t)enc[cid], refs[cid].fbits, vlower[q], vupper[q], &vr);  // (the host checked the arguments)
+                    if (!vr.empty && narrow) {
+                        vr.lo = max(vr.lo, (int64_t)INT32_MIN);
+                        vr.hi = min(vr.hi, (int64_t)INT32_MAX);
+                        vr.empty = vr.lo > vr.hi;
+                    }
+                    lo = vr.empty ? INT64_MAX : vr.lo;
+                    hi = vr.empty ? INT64_MIN : vr.hi;
+                    hole = !vr.empty && vr.hole;
+                }
                 WinQuery Q;
                 Q.chunk = cid;
                 Q.start = ls; Q.end = le; Q.top = lt; Q.bottom = lb; Q.left = ll; Q.right = lr;
@@ -2691,7 +2823,7 @@ k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __res
                 const uint32_t ncb = (lr - ll + 63u) >> 6;
                 for (uint32_t t = ls; t < le; t++) {
                     items[it++] = SearchItem{s, t, 0, w, ncb};
-                    const uint32_t qk = quirk[(size_t)cid * g.cs + t];
+                    const uint32_t qk = VALUE ? (hole ? 1u : 0u) : quirk[(size_t)cid * g.cs + t];
                     for (uint32_t rr = lt; rr < lb; rr += 64)
                         for (uint32_t cc = ll; cc < lr; cc += 64) {
                             WinItem wi;
@@ -2710,6 +2842,20 @@ k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __res
                 }
                 s++;
             }
+}
+__global__ void __launch_bounds__(256)
+k_raster_search_expand(const dcdf_cube* __restrict__ cubes, const int64_t* __restrict__ lower, const int64_t* __restrict__ upper,
+                       const uint32_t* __restrict__ sb, const uint32_t* __restrict__ ib, const uint32_t* __restrict__ wb, uint32_t nq, RasterGeom g,
+                       const uint8_t* __restrict__ quirk, WinQuery* __restrict__ qs, SearchItem* __restrict__ items, WinItem* __restrict__ witems,
+                       SearchExtra* __restrict__ sx) {
+    raster_search_expand<false>(cubes, lower, upper, nullptr, nullptr, sb, ib, wb, nq, g, quirk, nullptr, nullptr, false, qs, items, witems, sx);
+}
+__global__ void __launch_bounds__(256)
+k_raster_search_values_expand(const dcdf_cube* __restrict__ cubes, const double* __restrict__ lower, const double* __restrict__ upper,
+                              const uint32_t* __restrict__ sb, const uint32_t* __restrict__ ib, const uint32_t* __restrict__ wb, uint32_t nq,
+                              RasterGeom g, const ChunkRef* __restrict__ refs, const uint8_t* __restrict__ enc, uint32_t narrow,
+                              WinQuery* __restrict__ qs, SearchItem* __restrict__ items, WinItem* __restrict__ witems, SearchExtra* __restrict__ sx) {
+    raster_search_expand<true>(cubes, nullptr, nullptr, lower, upper, sb, ib, wb, nq, g, nullptr, refs, enc, narrow != 0, qs, items, witems, sx);
 }
 // exclusive prefix sum of n uint32 counts into uint64 offsets: block sums, their scan by one block, the offsets
 constexpr uint32_t kScanPer = 2048;  // elements per 256-thread block
@@ -2789,8 +2935,11 @@ __global__ void __launch_bounds__(256) k_raster_query_counts(const uint32_t* __r
     counts[q] = ob - oa;
 }
 
+// vlower / vupper (value search, lower / upper unused): real-valued bounds, translated per piece on the device
 static int raster_search_device(const dcdf_raster* r, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper, size_t nq, uint32_t* out,
-                                size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms) {
+                                size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms,
+                                const double* vlower = nullptr, const double* vupper = nullptr) {
+    const bool value = vlower != nullptr;
     std::vector<uint32_t> sb(nq + 1), ib(nq + 1), wb(nq + 1);
     uint64_t ns = 0, ni = 0, nw = 0;
     for (size_t q = 0; q < nq; q++) {
@@ -2818,8 +2967,8 @@ static int raster_search_device(const dcdf_raster* r, const dcdf_cube* cubes, co
     K2R_HIP(d_ib.alloc((nq + 1) * 4));
     K2R_HIP(d_wb.alloc((nq + 1) * 4));
     K2R_HIP(hipMemcpy(d_cubes.p, cubes, nq * sizeof(dcdf_cube), hipMemcpyHostToDevice));
-    K2R_HIP(hipMemcpy(d_lo.p, lower, nq * 8, hipMemcpyHostToDevice));
-    K2R_HIP(hipMemcpy(d_hi.p, upper, nq * 8, hipMemcpyHostToDevice));
+    K2R_HIP(hipMemcpy(d_lo.p, value ? (const void*)vlower : (const void*)lower, nq * 8, hipMemcpyHostToDevice));  // (8 bytes either way)
+    K2R_HIP(hipMemcpy(d_hi.p, value ? (const void*)vupper : (const void*)upper, nq * 8, hipMemcpyHostToDevice));
     K2R_HIP(hipMemcpy(d_sb.p, sb.data(), (nq + 1) * 4, hipMemcpyHostToDevice));
     K2R_HIP(hipMemcpy(d_ib.p, ib.data(), (nq + 1) * 4, hipMemcpyHostToDevice));
     K2R_HIP(hipMemcpy(d_wb.p, wb.data(), (nq + 1) * 4, hipMemcpyHostToDevice));
@@ -2839,11 +2988,23 @@ static int raster_search_device(const dcdf_raster* r, const dcdf_cube* cubes, co
     K2R_HIP(ev.create());
     const RasterGeom g{r->T, r->R, r->C, r->tile, r->cs, r->nti, r->ntj, 64u};
     const uint32_t nw32 = (uint32_t)nw, ni32 = (uint32_t)ni, nq32 = (uint32_t)nq;
-    hipLaunchKernelGGL(k_raster_search_expand, dim3((nq32 + 255) / 256), dim3(256), 0, 0, d_cubes.as<dcdf_cube>(), d_lo.as<int64_t>(), d_hi.as<int64_t>(),
-                       d_sb.as<uint32_t>(), d_ib.as<uint32_t>(), d_wb.as<uint32_t>(), nq32, g, r->d_quirk.as<uint8_t>(), d_qs.as<WinQuery>(),
-                       d_items.as<SearchItem>(), d_witems.as<WinItem>(), d_sx.as<SearchExtra>());
+    if (value)
+        hipLaunchKernelGGL(k_raster_search_values_expand, dim3((nq32 + 255) / 256), dim3(256), 0, 0, d_cubes.as<dcdf_cube>(), d_lo.as<double>(),
+                           d_hi.as<double>(), d_sb.as<uint32_t>(), d_ib.as<uint32_t>(), d_wb.as<uint32_t>(), nq32, g, r->d_refs.as<ChunkRef>(),
+                           r->d_enc.as<uint8_t>(), r->all_narrow ? 1u : 0u, d_qs.as<WinQuery>(), d_items.as<SearchItem>(), d_witems.as<WinItem>(),
+                           d_sx.as<SearchExtra>());
+    else
+        hipLaunchKernelGGL(k_raster_search_expand, dim3((nq32 + 255) / 256), dim3(256), 0, 0, d_cubes.as<dcdf_cube>(), d_lo.as<int64_t>(), d_hi.as<int64_t>(),
+                           d_sb.as<uint32_t>(), d_ib.as<uint32_t>(), d_wb.as<uint32_t>(), nq32, g, r->d_quirk.as<uint8_t>(), d_qs.as<WinQuery>(),
+                           d_items.as<SearchItem>(), d_witems.as<WinItem>(), d_sx.as<SearchExtra>());
     K2R_HIP(hipEventRecord(ev.e0, 0));
-    if (r->all_narrow)
+    if (value && r->all_narrow)
+        hipLaunchKernelGGL((k_window_wave2<4, false, true, int32_t, true, true>), dim3(std::min<uint32_t>((nw32 + 3) / 4, 256u * 16u)), dim3(256), 0, 0,
+                           r->d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw32, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
+    else if (value)
+        hipLaunchKernelGGL((k_window_wave2<3, false, true, int64_t, true, true>), dim3(std::min<uint32_t>((nw32 + 3) / 4, 256u * 16u)), dim3(256), 0, 0,
+                           r->d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw32, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
+    else if (r->all_narrow)
         hipLaunchKernelGGL((k_window_wave2<4, false, true, int32_t>), dim3(std::min<uint32_t>((nw32 + 3) / 4, 256u * 16u)), dim3(256), 0, 0,
                            r->d_refs.as<ChunkRef>(), d_witems.as<WinItem>(), nw32, d_wbits.p, (int32_t)DCDF_I64, d_sx.as<SearchExtra>());
     else
@@ -2878,18 +3039,20 @@ static int raster_search_device(const dcdf_raster* r, const dcdf_cube* cubes, co
     return DCDF_OK;
 }
 
-extern "C" int dcdf_raster_search_batch(const dcdf_raster* r, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper, size_t nq,
-                                        uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms) {
-    if (!r || !cubes || !lower || !upper || !counts || !offsets || nq == 0 || (!out && cap)) return DCDF_ERR_BAD_ARG;
-    if (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) return DCDF_ERR_BAD_ARG;
+// search of dataset-level cubes; vlower / vupper: a value search (lower / upper unused)
+static int raster_search(const dcdf_raster* r, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper, const double* vlower,
+                         const double* vupper, size_t nq, uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets,
+                         float* kernel_ms) {
+    const bool value = vlower != nullptr;
     // k = 2 chunks: pieces, items, counts, offsets and triples all stay on the device; other arities take the host-built form below
     if (r->all_node && nq <= 0x7fffffffu && !std::getenv("K2R_SEARCH_DFS") && !std::getenv("K2R_RASTER_HOST"))
-        return raster_search_device(r, cubes, lower, upper, nq, out, cap, out_mem, counts, offsets, kernel_ms);
+        return raster_search_device(r, cubes, lower, upper, nq, out, cap, out_mem, counts, offsets, kernel_ms, vlower, vupper);
     std::vector<dcdf_chunk*> sch;
     std::vector<dcdf_cube> scube;
     std::vector<int64_t> slo, shi;
+    std::vector<double> svlo, svhi;
     std::vector<uint32_t> sorg, scid, first(nq + 1, 0);
-    sch.reserve(2 * nq); scube.reserve(2 * nq); slo.reserve(2 * nq); shi.reserve(2 * nq); sorg.reserve(6 * nq); scid.reserve(2 * nq);
+    sch.reserve(2 * nq); scube.reserve(2 * nq); sorg.reserve(6 * nq); scid.reserve(2 * nq);
     for (size_t q = 0; q < nq; q++) {
         const dcdf_cube c = norm_cube(cubes[q]);
         if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
@@ -2898,8 +3061,13 @@ extern "C" int dcdf_raster_search_batch(const dcdf_raster* r, const dcdf_cube* c
                 sch.push_back(r->chunks[cid]);
                 scid.push_back(cid);
                 scube.push_back(l);
-                slo.push_back(lower[q]);
-                shi.push_back(upper[q]);
+                if (value) {
+                    svlo.push_back(vlower[q]);
+                    svhi.push_back(vupper[q]);
+                } else {
+                    slo.push_back(lower[q]);
+                    shi.push_back(upper[q]);
+                }
                 sorg.push_back(t0);
                 sorg.push_back(r0);
                 sorg.push_back(c0);
@@ -2913,12 +3081,29 @@ extern "C" int dcdf_raster_search_batch(const dcdf_raster* r, const dcdf_cube* c
     // the pieces of one query follow each other (segments, then tile rows, then tile columns) and search_impl emits in
     // query order, so a query's triples are contiguous; each is moved to raster coordinates as it is written
     const SearchCtx ctx{&r->d_refs, scid.data(), sorg.data(), r->all_node, r->all_narrow, r->all_wave};
-    const int rc = search_impl(sch.data(), scube.data(), slo.data(), shi.data(), sch.size(), out, cap, scnt.data(), soff.data(), &total, kernel_ms,
-                               out_mem, &ctx);
+    const int rc = search_impl(sch.data(), scube.data(), value ? nullptr : slo.data(), value ? nullptr : shi.data(), sch.size(), out, cap,
+                               scnt.data(), soff.data(), &total, kernel_ms, out_mem, &ctx, value ? svlo.data() : nullptr,
+                               value ? svhi.data() : nullptr);
     if (rc != DCDF_OK) return rc;
     for (size_t q = 0; q < nq; q++) {
         offsets[q] = first[q] < sch.size() ? soff[first[q]] : total;
         for (uint32_t k = first[q]; k < first[q + 1]; k++) counts[q] += scnt[k];
     }
     return DCDF_OK;
+}
+extern "C" int dcdf_raster_search_batch(const dcdf_raster* r, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper, size_t nq,
+                                        uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms) {
+    if (!r || !cubes || !lower || !upper || !counts || !offsets || nq == 0 || (!out && cap)) return DCDF_ERR_BAD_ARG;
+    if (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) return DCDF_ERR_BAD_ARG;
+    return raster_search(r, cubes, lower, upper, nullptr, nullptr, nq, out, cap, out_mem, counts, offsets, kernel_ms);
+}
+// value search of dataset-level cubes (dcdf_k2r.h): the same routing; k = 2 rasters translate the bounds per piece on the device
+extern "C" int dcdf_raster_search_values_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
+                                               uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms) {
+    if (!r || !cubes || !lower || !upper || !counts || !offsets || nq == 0 || (!out && cap)) return DCDF_ERR_BAD_ARG;
+    if (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) return DCDF_ERR_BAD_ARG;
+    if (r->bad_fbits) return DCDF_ERR_BAD_ARG;
+    for (size_t q = 0; q < nq; q++)
+        if (lower[q] != lower[q] || upper[q] != upper[q]) return DCDF_ERR_BAD_ARG;
+    return raster_search(r, cubes, nullptr, nullptr, lower, upper, nq, out, cap, out_mem, counts, offsets, kernel_ms);
 }

@@ -7,6 +7,7 @@ What is mirrored, and from where:
   Span: append / update / find_span, queries routed over the time axis               span.rs:50-275
   Superchunk node: tile routing, elided tiles answered from the max Dac               superchunk.rs:313-633, :672-768
   Variable.get / cell / window / __getitem__ with py-dcdf's slicing rules            py-dcdf __init__.py:272-350
+  Variable.search_values: real-valued search for every dtype (the reference's is todo!(), mmarray.rs:407-417, 511-521)
   Coordinate.time / range                                                            py-dcdf __init__.py:150-243
 
 What runs where: the encode of every appended slice is dcdf_superchunk_build (tile min/max, fractional bits, every
@@ -23,6 +24,7 @@ import struct
 
 import numpy as np
 
+from . import _lib
 from . import chunk as _chunk
 from .chunk import Chunk, Cube
 from .superchunk import Superchunk
@@ -281,6 +283,30 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             self._route_search(cid, a0, a1, top, bottom, left, right, lower, upper, start + o0 - a0, 0, 0, hits)
         return np.array(sorted(hits), dtype=np.int64).reshape(-1, 3)
 
+    def search_values(self, start, stop, top, bottom, left, right, lower, upper):
+        """(instant, row, col) of the cells whose value -- what window() returns for them -- lies in [lower, upper], sorted, as an
+        int64 [n, 3] array.  Real-valued bounds for every dtype: each chunk translates them into its own fixed-point integers
+        (dcdf_value_bounds); NaN cells never match, +-inf is unbounded, reversed bounds are swapped, a NaN bound is a ValueError.
+        Tiles whose stored min / max miss the range at every instant are skipped without opening them (superchunk.rs:464-500),
+        elided tiles are tested on the host, and every chunk piece goes through ONE search_values_batch launch."""
+        self._check(start, stop, top, bottom, left, right)
+        lower, upper = float(lower), float(upper)
+        if np.isnan(lower) or np.isnan(upper):
+            raise ValueError("search_values: a NaN bound (%r, %r)" % (lower, upper))
+        lower, upper = min(lower, upper), max(lower, upper)
+        jobs, parts = [], []
+        for cid, a0, a1, o0 in self._time_pieces(start, stop):
+            self._route_values(cid, a0, a1, top, bottom, left, right, lower, upper, start + o0 - a0, 0, 0, jobs, parts)
+        if jobs:
+            trip, _, counts, _ = _chunk.search_values_batch([j[0] for j in jobs], [j[1] for j in jobs], lower, upper)
+            counts = counts.astype(np.int64)
+            n = int(counts.sum())
+            if n:  # (the pieces' triples follow each other in piece order)
+                org = np.repeat(np.array([j[2] for j in jobs], dtype=np.int64), counts, axis=0)
+                parts.append(trip[:n].astype(np.int64) + org)
+        hits = np.concatenate(parts) if parts else np.zeros((0, 3), dtype=np.int64)
+        return hits[np.lexsort((hits[:, 2], hits[:, 1], hits[:, 0]))]
+
     def __getitem__(self, key):
         """NumPy-style basic indexing with up to three integers / unit-stride slices; the answer is lazy (`.data` decodes).
         Every axis is first reduced to a half-open range plus a "drop this axis" mark; the pattern of marks then picks the
@@ -412,6 +438,48 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
                         hits.extend((t + dt, org_r + r, org_c + c) for r in range(r0, r1) for c in range(c0, c1))
             else:
                 self._route_search(self._sub(node, ref[1])[0], a0, a1, r0, r1, c0, c1, lower, upper, dt, org_r, org_c, hits)
+
+    def _stored_bits(self, cid):
+        """Fractional bits of a stored sub-object, read from its header: a sub-chunk is not opened on the GPU for it."""
+        obj = self._resolver.objects[cid]
+        if obj[6] == NODE_MMSTRUCT3 and obj[7] == NODE_SUBCHUNK:
+            return obj[9]  # Chunk::write_to: encoding u8, fractional_bits u8 (chunk.rs:235-243)
+        return self._resolver.node(cid).fractional_bits
+
+    def _route_values(self, cid, a0, a1, top, bottom, left, right, lower, upper, dt, dr, dc_, jobs, parts):
+        node = self._resolver.node(cid)
+        if isinstance(node, Chunk):
+            jobs.append((node, Cube(a0, a1, top, bottom, left, right), (dt, dr, dc_)))
+            return
+        # the node's stored min / max and elided values are integers in the NODE's encoding and bits
+        lo, hi, hole = _lib.value_bounds(node.encoding, node.fractional_bits, lower, upper)
+        stride, cs, ss = node.subsidelen * node.subsidelen, node.chunks_sidelen, node.subsidelen
+        ts = np.arange(a0, a1)
+        for ch, (r0, r1, c0, c1), _ in self._tiles(node, top, bottom, left, right):
+            ref = node.references[ch]
+            org_r, org_c = dr + (ch // ss) * cs, dc_ + (ch % ss) * cs
+            mx = node.max[ch + ts * stride]
+            if ref is None:  # elided: one value per instant, node.max (what window() returns), tested in integer space
+                hit_t = ts[(mx >= lo) & (mx <= hi) & ~(hole & (mx == 0))]
+                if len(hit_t):
+                    rr, cc = np.meshgrid(np.arange(r0, r1) + org_r, np.arange(c0, c1) + org_c, indexing="ij")
+                    cells = np.stack([rr.ravel(), cc.ravel()], axis=1)
+                    parts.append(np.concatenate([np.repeat(hit_t + dt, len(cells))[:, None], np.tile(cells, (len(hit_t), 1))], axis=1))
+                continue
+            sub = self._resolver.node(node.external_cid)[ref[1]]
+            # has_cells (superchunk.rs:464-500): prune where the node's min / max are exact values of the sub-object -- integers,
+            # values stored without rounding, or the same fractional bits (round=True may store a tile with fewer bits than the node).
+            # A float tile's min or max is 0, the NaN code, when a NaN reached its reduction first (it is then no bound at all):
+            # such an instant is never pruned.
+            integer = node.encoding in (MMEncoding.I32, MMEncoding.I64)
+            if integer or self._round is None or self._stored_bits(sub) == node.fractional_bits:
+                mn = node.min[ch + ts * stride]
+                live = (mx >= lo) & (mn <= hi)
+                if not integer:
+                    live |= (mn == 0) | (mx == 0)
+                if not live.any():
+                    continue
+            self._route_values(sub, a0, a1, r0, r1, c0, c1, lower, upper, dt, org_r, org_c, jobs, parts)
 
     # ---- growth: Variable::append and friends (dataset.rs:834-986) -----------------------------------------------------
     def _with_cid(self, cid):

@@ -93,6 +93,26 @@ class EncodedRaster:
                                                  C.c_void_p(offs.ctypes.data), C.byref(ms)), "raster_search_batch")
         return trip, offs, counts, ms.value
 
+    def search_values_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
+        """Value search of dataset-level cubes through dcdf_raster_search_values_batch: real-valued [lower, upper] per cube,
+        translated on the device per piece with the piece's chunk's encoding and fractional bits.  Returns what search_flat
+        returns (triples uint32[hits, 3] in raster coordinates or None, offsets, counts, kernel ms)."""
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (len(q),)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (len(q),)))
+        counts = np.zeros(len(q), dtype=np.uint64)
+        offs = np.zeros(len(q), dtype=np.uint64)
+        if cap is None:
+            cap = int(np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).sum())
+        ms = C.c_float()
+        trip = None if out_device_ptr else np.empty((max(cap, 1), 3), dtype=np.uint32)
+        L.check(L.lib().dcdf_raster_search_values_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
+                                                        C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)),
+                                                        C.c_void_p(out_device_ptr or trip.ctypes.data), C.c_size_t(cap),
+                                                        L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.c_void_p(counts.ctypes.data),
+                                                        C.c_void_p(offs.ctypes.data), C.byref(ms)), "raster_search_values_batch")
+        return trip, offs, counts, ms.value
+
     @staticmethod
     def chunk_grid(shape, tile=256, chunk_size=32):
         """[(t0, t1, r0, r1, c0, c1)] of every chunk, in chunk-id order (segment-major, then tile row, tile col)."""

@@ -242,6 +242,32 @@ int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cube* cubes, 
 int dcdf_raster_search_batch(const dcdf_raster* r, const dcdf_cube* cubes, const int64_t* lower, const int64_t* upper, size_t nq,
                              uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets, float* kernel_ms);
 
+/* ---- value search: real-valued bounds (what replaces the todo!() of MMArray3F32::search / MMArray3F64::search,
+ * mmarray.rs:407-417 and 511-521: the bounds translated into each chunk's own fixed-point representation) ----------
+ * A cell matches [lower, upper] iff the value the typed fill_window returns for it, v, satisfies lower <= v <= upper exactly:
+ * DCDF_F32 / F64 chunks: v = from_fixed in float / double, (n - 1) / 2^(fractional_bits + 1) (fixed.rs:81-86; stored 0 is NaN
+ * and never matches); DCDF_I32 / I64 chunks: v = n, i.e. n in [ceil(lower), floor(upper)].  Reversed bounds are swapped, +-inf
+ * is unbounded, a NaN bound is DCDF_ERR_BAD_ARG.  Value search returns the cells' TRUE values on the instants where the integer
+ * search reproduces the reference's quirk (log.rs:527-548).  The integer entry points above are unchanged. */
+
+/* The matching stored integers of one chunk: [*lo, *hi], less 0 when *skip_zero (set only when *lo < 0 < *hi).  DCDF_OK and
+ * *lo > *hi when nothing matches.  Pure host function; no GPU, no HIP call (so it is testable on a CPU-only machine).
+ * DCDF_ERR_BAD_ARG: a NaN bound, an unknown encoding, float fractional_bits > 62 (beyond what Chunk::build accepts). */
+int dcdf_value_bounds(int32_t encoding, uint32_t fractional_bits, double lower, double upper, int64_t* lo, int64_t* hi,
+                      int32_t* skip_zero);
+/* dcdf_chunk_search with real-valued bounds: sorted (instant,row,col) triples, cap / *n / DCDF_ERR_CAPACITY as there. */
+int dcdf_chunk_search_values(const dcdf_chunk* h, const dcdf_cube* cube, double lower, double upper, uint32_t* out, size_t cap,
+                             size_t* n);
+/* dcdf_query_search_batch_mem with real-valued bounds (each query's bounds translated with its chunk's encoding and bits). */
+int dcdf_query_search_values_batch(dcdf_chunk* const* chunks, const dcdf_cube* cubes, const double* lower, const double* upper,
+                                   size_t nq, uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets,
+                                   float* kernel_ms);
+/* dcdf_raster_search_batch with real-valued bounds: k = 2 rasters translate them per piece on the device, with the piece's
+ * chunk's encoding and fractional bits. */
+int dcdf_raster_search_values_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper,
+                                    size_t nq, uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets,
+                                    float* kernel_ms);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* fixed.rs:96-159 + mmbuffer.rs:596-613: per-tile suggest_fraction on the device; out_round = 1 for
  * Fraction::Round.  Host or device data per `mem`. */

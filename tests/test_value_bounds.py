@@ -1,0 +1,210 @@
+"""dcdf_value_bounds: real-valued search bounds -> the stored integers that match, checked on the host (no GPU) against a numpy
+brute force of the predicate value search is defined by: lower <= v <= upper, v = what the typed fill_window returns for the
+stored n (from_fixed in float32 / float64, NaN for n = 0; n itself for integer chunks)."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from dcdf_amd import _lib as L  # noqa: E402
+
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
+INF = float("inf")
+
+
+def value(enc, bits, n):
+    """The typed value of stored n, as store_typed computes it (None for the NaN code)."""
+    if enc == L.DCDF_F32:
+        return None if n == 0 else float(np.float32(np.int64(n - 1)) / np.float32(2.0 ** (bits + 1)))
+    if enc == L.DCDF_F64:
+        return None if n == 0 else float(np.float64(np.int64(n - 1)) / np.float64(2.0 ** (bits + 1)))
+    return n  # (a Python int: compared with a float exactly)
+
+
+def matches(enc, bits, n, lower, upper):
+    v = value(enc, bits, n)
+    return v is not None and lower <= v <= upper
+
+
+def domain(enc):
+    if enc == L.DCDF_I32:
+        return I32_MIN, I32_MAX
+    if enc == L.DCDF_I64:
+        return I64_MIN, I64_MAX
+    return I64_MIN + 1, I64_MAX  # (from_fixed of INT64_MIN overflows; to_fixed never stores it)
+
+
+def first(enc, bits, pred):
+    """Smallest n of the domain with pred(v(n)) for a monotone pred, by bisection over Python ints (None: there is none)."""
+    lo, hi = domain(enc)
+    f = (lambda n: pred(float(np.float32(np.int64(n - 1)) / np.float32(2.0 ** (bits + 1))))) if enc == L.DCDF_F32 else \
+        (lambda n: pred(float(np.float64(np.int64(n - 1)) / np.float64(2.0 ** (bits + 1))))) if enc == L.DCDF_F64 else \
+        (lambda n: pred(n))
+    if not f(hi):
+        return None
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if f(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def reference(enc, bits, lower, upper):
+    """(lo, hi, hole) or None when nothing matches, from the predicate alone."""
+    lower, upper = min(lower, upper), max(lower, upper)
+    dlo, dhi = domain(enc)
+    # -inf is unbounded: every stored integer, INT64_MIN included (which to_fixed never produces)
+    nlo = (I32_MIN if enc == L.DCDF_I32 else I64_MIN) if lower == -INF else first(enc, bits, lambda v: v >= lower)
+    if nlo is None:
+        return None
+    if upper == INF:
+        nhi = dhi
+    else:
+        above = first(enc, bits, lambda v: v > upper)
+        if above == dlo:  # every value lies above upper (no stored value is infinite)
+            return None
+        nhi = dhi if above is None else above - 1
+    if enc in (L.DCDF_F32, L.DCDF_F64) and nlo <= 0 <= nhi:
+        if nlo == nhi == 0:
+            return None
+        if nlo == 0:
+            nlo = 1
+        elif nhi == 0:
+            nhi = -1
+        else:
+            return nlo, nhi, True
+    return (nlo, nhi, False) if nlo <= nhi else None
+
+
+def check(enc, bits, lower, upper):
+    lo, hi, hole = L.value_bounds(enc, bits, lower, upper)
+    want = reference(enc, bits, lower, upper)
+    if want is None:
+        assert lo > hi and not hole, (enc, bits, lower, upper, lo, hi)
+        return
+    assert (lo, hi, hole) == want, (enc, bits, lower, upper)
+    a, b = min(lower, upper), max(lower, upper)
+    dlo, dhi = domain(enc)
+    # the ends match, the integers just outside them do not (stepping over the NaN code, which never matches)
+    assert (lo == I64_MIN or matches(enc, bits, lo, a, b)) and matches(enc, bits, hi, a, b)
+    below, above = lo - 1, hi + 1
+    if below == 0 and enc in (L.DCDF_F32, L.DCDF_F64):
+        below = -1
+    if above == 0 and enc in (L.DCDF_F32, L.DCDF_F64):
+        above = 1
+    if below >= dlo:
+        assert not matches(enc, bits, below, a, b)
+    if above <= dhi:
+        assert not matches(enc, bits, above, a, b)
+    if hole:
+        assert lo < 0 < hi and not matches(enc, bits, 0, a, b)
+        assert matches(enc, bits, -1, a, b) and matches(enc, bits, 1, a, b)
+
+
+FLOATS = [(L.DCDF_F32, b) for b in (0, 1, 2, 8, 16, 29, 34)] + [(L.DCDF_F64, b) for b in (0, 1, 2, 8, 16, 29, 34, 52)]
+
+
+def representable(enc, bits):
+    """Bounds that are exactly values of some stored n, and their nextafter neighbours."""
+    out = []
+    for n in (1, 2, 3, -1, -5, 1000, -(1 << 20), (1 << 24) + 1, (1 << 24) + 3, (1 << 40) + 12345, -(1 << 40) - 7):
+        v = value(enc, bits, n)
+        out += [v, math.nextafter(v, INF), math.nextafter(v, -INF)]
+    return out
+
+
+@pytest.mark.parametrize("enc,bits", FLOATS)
+def test_float_bounds_at_representable_values_and_neighbours(enc, bits):
+    vals = representable(enc, bits)
+    for i, x in enumerate(vals):
+        check(enc, bits, x, x)  # a point range: exactly the n whose value is x (or nothing)
+        for y in vals[i + 1:i + 6]:
+            check(enc, bits, x, y)
+
+
+@pytest.mark.parametrize("enc,bits", FLOATS)
+def test_float_zero_infinities_reversed_and_the_hole(enc, bits):
+    for lo, hi in [(0.0, 0.0), (-0.0, 0.0), (-0.0, -0.0), (0.0, 1.0), (-1.0, -0.0), (-INF, INF), (-INF, 0.0), (0.0, INF),
+                   (INF, INF), (-INF, -INF), (1.0, -1.0), (-2.5, 3.25), (5.0, 3.0), (1e-30, 2e-30), (-1e300, 1e300)]:
+        check(enc, bits, lo, hi)
+    # a range that straddles the NaN code's neighbourhood sets the hole; one on either side does not
+    lo, hi, hole = L.value_bounds(enc, bits, -1.0, 1.0)
+    assert hole and lo < 0 < hi
+    for a, b in [(0.0, 1.0), (-1.0, -0.5), (0.5, 1.0)]:
+        assert not L.value_bounds(enc, bits, a, b)[2]
+    assert L.value_bounds(enc, bits, 2.0, 1.0) == L.value_bounds(enc, bits, 1.0, 2.0)
+
+
+@pytest.mark.parametrize("enc,bits", FLOATS)
+def test_float_empty_ranges(enc, bits):
+    step = 2.0 ** -(bits + 1)
+    for lo, hi in [(0.25 * step, 0.75 * step), (-0.75 * step, -0.25 * step), (1e30, 1e31) if enc == L.DCDF_F32 else (1e300, INF),
+                   (INF, INF), (-INF, -INF)]:
+        a, b, hole = L.value_bounds(enc, bits, lo, hi)
+        want = reference(enc, bits, lo, hi)
+        check(enc, bits, lo, hi)
+        if want is None:
+            assert a > b and not hole
+
+
+def test_float32_collapses_many_stored_integers_into_one_value():
+    # at 29 bits every float32 value above ~0.016 stands for many stored n: the closed form ceil(lower * 2^30) + 1 is wrong
+    bits = 29
+    for x in (0.02, 1.0, 10.0, 20.0, 123.456):
+        lo, hi, _ = L.value_bounds(L.DCDF_F32, bits, x, x)
+        closed = math.ceil(x * 2.0 ** (bits + 1)) + 1
+        if lo <= hi:
+            assert hi > lo  # a whole run of n shares the value
+        check(L.DCDF_F32, bits, x, x)
+        check(L.DCDF_F32, bits, 10.0, x)
+        assert reference(L.DCDF_F32, bits, x, INF)[0] != closed or value(L.DCDF_F32, bits, closed - 1) < x
+
+
+def test_brute_force_small_bits():
+    # every n in a window around the bounds, directly against the predicate
+    for enc, bits in [(L.DCDF_F32, 0), (L.DCDF_F32, 2), (L.DCDF_F64, 1), (L.DCDF_I32, 0), (L.DCDF_I64, 0)]:
+        for lower, upper in [(-3.3, 4.1), (0.0, 2.0), (-2.0, 0.0), (1.0, 1.0), (-0.1, 0.1), (2.6, 2.4), (7.0, 7.0)]:
+            lo, hi, hole = L.value_bounds(enc, bits, lower, upper)
+            a, b = min(lower, upper), max(lower, upper)
+            for n in range(-64, 65):
+                got = lo <= n <= hi and not (hole and n == 0)
+                assert got == matches(enc, bits, n, a, b), (enc, bits, lower, upper, n)
+
+
+@pytest.mark.parametrize("enc", [L.DCDF_I32, L.DCDF_I64])
+def test_integer_bounds(enc):
+    cases = [(1.5, 2.5), (-1.5, 1.5), (0.0, 0.0), (-0.0, 0.0), (2.0, 2.0), (2.1, 2.9), (3.0, -3.0), (-INF, INF), (-INF, 5.0), (5.0, INF),
+             (INF, INF), (-INF, -INF), (2.0 ** 53 + 2, 2.0 ** 60), (-2.0 ** 62, -2.0 ** 54), (2.0 ** 63, 2.0 ** 64), (-2.0 ** 64, -2.0 ** 63),
+             (-2.0 ** 63, -2.0 ** 63), (2.0 ** 31, 2.0 ** 40), (-2.0 ** 40, -2.0 ** 31 - 1), (-2.0 ** 40, 2.0 ** 40)]
+    for lo, hi in cases:
+        check(enc, 0, lo, hi)
+        a, b, hole = L.value_bounds(enc, 0, lo, hi)
+        assert not hole  # zero is an ordinary value of an integer chunk
+    assert L.value_bounds(enc, 0, 0.0, 0.0)[:2] == (0, 0)
+    assert L.value_bounds(enc, 0, 1.5, 2.5)[:2] == (2, 2)
+    # beyond 2^53: the stored integer is never rounded to double
+    big = 2.0 ** 60
+    lo, hi, _ = L.value_bounds(L.DCDF_I64, 0, big, big)
+    assert lo == hi == 1 << 60
+    assert L.value_bounds(L.DCDF_I32, 0, -INF, INF)[:2] == (I32_MIN, I32_MAX)
+    assert L.value_bounds(L.DCDF_I64, 0, -INF, INF)[:2] == (I64_MIN, I64_MAX)
+
+
+def test_bad_arguments():
+    nan = float("nan")
+    for enc in (L.DCDF_I32, L.DCDF_I64, L.DCDF_F32, L.DCDF_F64):
+        for lo, hi in [(nan, 1.0), (1.0, nan), (nan, nan)]:
+            with pytest.raises(L.DcdfError) as e:
+                L.value_bounds(enc, 0, lo, hi)
+            assert e.value.code == -1  # DCDF_ERR_BAD_ARG
+    for enc, bits in [(7, 0), (L.DCDF_F32, 63), (L.DCDF_F64, 200)]:
+        with pytest.raises(L.DcdfError):
+            L.value_bounds(enc, bits, 0.0, 1.0)
+    assert L.value_bounds(L.DCDF_F64, 62, 0.0, 1.0)[0] == 1
