@@ -173,8 +173,8 @@ k_fill_window(const ChunkRef* __restrict__ chunks, const WinQuery* __restrict__ 
         for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
             const uint32_t c = (uint32_t)(e % wc), r = (uint32_t)((e / wc) % wr), t = (uint32_t)(e / ((uint64_t)wc * wr));
             const int64_t v = inst_get(C.bytes, C.descs, Q.start + t, Q.top + r, Q.left + c);
-            if (strided_single) store_typed(out, (int64_t)t * st + (int64_t)r * sr + (int64_t)c * sc, out_dtype, v, C.fbits);
-            else ((int64_t*)out)[Q.out_off + e] = v;
+            const int64_t off = strided_single ? (int64_t)t * st + (int64_t)r * sr + (int64_t)c * sc : (int64_t)(Q.out_off + e);
+            store_typed(out, off, out_dtype, v, C.fbits);
         }
     }
 }
@@ -2510,12 +2510,11 @@ static int fill_window_batch_impl(dcdf_chunk* const* chunks, const dcdf_cube* cu
         rc = launch_window_items(d_refs, items, d_dst, out_dtype, ev.e0, ev.e1, all_node, all_narrow);
         if (rc != DCDF_OK) return rc;
     } else {
-        // arities beyond the wave walk (k * k > 64): per-cell descents, int64 only
-        if (out_dtype != DCDF_I64) return DCDF_ERR_UNSUPPORTED;
+        // arities beyond the wave walk (k * k > 64): per-cell descents, typed at each query's out_off like the walks
         const uint32_t grid = (uint32_t)std::min<size_t>(nq, 1u << 20);
         K2R_HIP(hipEventRecord(ev.e0, 0));
         hipLaunchKernelGGL(k_fill_window, dim3(grid), dim3(256), 0, 0, d_refs.as<ChunkRef>(), d_qs.as<WinQuery>(),
-                           (uint32_t)nq, d_dst, (int32_t)DCDF_I64, (int64_t)0, (int64_t)0, (int64_t)0, 0);
+                           (uint32_t)nq, d_dst, out_dtype, (int64_t)0, (int64_t)0, (int64_t)0, 0);
         K2R_HIP(hipEventRecord(ev.e1, 0));
         K2R_HIP(hipGetLastError());
         K2R_HIP(hipDeviceSynchronize());

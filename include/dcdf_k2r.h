@@ -195,7 +195,8 @@ int dcdf_query_search_batch(dcdf_chunk* const* chunks, const dcdf_cube* cubes, c
 /* The same with a typed result and a result that may stay on the device: out_dtype = DCDF_I32 / I64 / F32 / F64 is the
  * element type written (MMBuffer3::set, mmbuffer.rs:292-299: integers as stored, floats through from_fixed, fixed.rs:81-86);
  * out_mem = DCDF_MEM_DEVICE: `out` is device memory, the decode kernel writes window q at out + out_offset[q] (ELEMENTS of
- * out_dtype) itself and nothing crosses PCIe.  An int32 result of int32 chunks moves half the bytes of the i64 form. */
+ * out_dtype) itself and nothing crosses PCIe.  An int32 result of int32 chunks moves half the bytes of the i64 form.  Every
+ * arity and output type: a batch holding any k * k > 64 chunk is decoded cell by cell, typed the same way. */
 int dcdf_query_fill_window_batch_typed(dcdf_chunk* const* chunks, const dcdf_cube* cubes, size_t nq, void* out,
                                        int32_t out_dtype, int out_mem, const uint64_t* out_offset, float* kernel_ms);
 /* dcdf_query_search_batch whose triples may stay on the device (out_mem = DCDF_MEM_DEVICE: `out` is device memory of `cap`
