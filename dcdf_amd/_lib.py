@@ -35,6 +35,11 @@ class Cube(C.Structure):
                 ("left", C.c_uint32), ("right", C.c_uint32)]
 
 
+class RasterTile(C.Structure):  # dcdf_raster_tile
+    _fields_ = [("chunk", C.c_void_p), ("row0", C.c_uint32), ("col0", C.c_uint32), ("values", C.c_void_p), ("minmax", C.c_void_p),
+                ("encoding", C.c_int32), ("fractional_bits", C.c_uint8), ("minmax_exact", C.c_uint8), ("_pad", C.c_uint8 * 2)]
+
+
 class DcdfError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
@@ -56,6 +61,7 @@ SYMBOLS = [
     "dcdf_chunk_search", "dcdf_query_fill_window_batch", "dcdf_query_search_batch", "dcdf_query_fill_window_batch_typed", "dcdf_query_search_batch_mem", "dcdf_query_get_batch", "dcdf_query_fill_cell_batch", "dcdf_chunk_open_batch", "dcdf_chunk_instant_layout", "dcdf_raster_create", "dcdf_raster_destroy", "dcdf_raster_fill_window_batch", "dcdf_raster_search_batch", "dcdf_suggest_fraction", "dcdf_encoder_object_sha256",
     "dcdf_synth_fill", "dcdf_calib_read", "dcdf_device_alloc", "dcdf_device_free", "dcdf_device_copy", "dcdf_strerror", "dcdf_device_name", "dcdf_abi_version", "dcdf_last_hip_error", "dcdf_device_pool_trim",
     "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
+    "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch",
 ]
 
 

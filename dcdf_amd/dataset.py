@@ -19,6 +19,7 @@ node encodings (dataset.rs:386-640) belong to the storage layer that is out of s
 that state by the SHA-256 of its canonical description, not by the reference's Dataset-node CID.
 
 No IPFS, no LRU cache: `Resolver` owns a dict."""
+import collections
 import hashlib
 import struct
 
@@ -121,6 +122,91 @@ class _SuperNode:
             raise ValueError("local sub-chunks are never written by Superchunk::build (superchunk.rs:245)")
         self.max, pos = _dac_values(obj, pos)
         self.min, pos = _dac_values(obj, pos)
+
+
+Leaf = collections.namedtuple("Leaf", "cid values row0 col0 minmax encoding fractional_bits exact")
+Leaf.__doc__ = """One leaf of leaf_grid: cid = the stored chunk object holding it (None: elided, `values` = its value per instant),
+(row0, col0) = where the leaf starts inside that chunk, minmax = [instants, 2] stored (min, max) of the node tile holding it,
+encoding / fractional_bits = that node's, exact = minmax are exact values of the chunk's stored integers."""
+
+
+def leaf_grid(objects, segment_cids, k2_levels, round_):
+    """Flattens the stored Superchunk trees of a variable (one per time segment, `segment_cids` in time order) into the leaves
+    dcdf_raster_create_tiles takes: returns (leaf size = 2^(last k2 level), [per segment: [Leaf] in (tile row, tile col) order]).
+    Pure host code over the stored bytes (objects: cid -> object); no chunk is opened.  Walks Links and nested nodes
+    (superchunk.rs:313-400): an elided tile gives every leaf it covers the node's max Dac entry per instant (superchunk.rs:330-334);
+    a chunk built at an upper level (superchunk.rs:153-163) gives several leaves, each with its offset inside the chunk.
+    `exact` = integer encoding, or no rounding (round_ false), or the chunk's fractional bits equal the node's (the rule of
+    Variable.search_values).  ValueError on trees this flattening cannot represent, saying which."""
+    leaf = 1 << int(k2_levels[-1])
+    nodes = {}
+
+    def node(cid):
+        n = nodes.get(cid)
+        if n is None:
+            obj = objects[cid]
+            if obj[6] == NODE_MMSTRUCT3 and obj[7] == NODE_SUPERCHUNK:
+                n = _SuperNode(obj)
+            elif obj[6] == NODE_LINKS:
+                (cnt,) = struct.unpack_from(">I", obj, 7)
+                n = [obj[11 + 36 * i:11 + 36 * i + 36] for i in range(cnt)]
+            elif obj[6] == NODE_MMSTRUCT3 and obj[7] == NODE_SUBCHUNK:
+                n = ("chunk", obj[8], obj[9])  # Chunk::write_to: encoding u8, fractional_bits u8 (chunk.rs:235-243)
+            else:
+                raise ValueError("leaf_grid: unexpected node type %d / %d" % (obj[6], obj[7]))
+            nodes[cid] = n
+        return n
+
+    segments, shape = [], None
+    for s, root in enumerate(segment_cids):
+        top = node(root)
+        if not isinstance(top, _SuperNode):
+            raise ValueError("leaf_grid: segment %d is not a Superchunk node" % s)
+        if shape is None:
+            shape = top.shape[1:]
+        elif top.shape[1:] != shape:
+            raise ValueError("leaf_grid: segment %d has shape %s, segment 0 %s" % (s, top.shape[1:], shape))
+        nti, ntj = -(-shape[0] // leaf), -(-shape[1] // leaf)
+        grid = [None] * (nti * ntj)
+        T = top.shape[0]
+        ts = np.arange(T)
+
+        def walk(n, r0, c0):
+            rows, cols = n.shape[1], n.shape[2]
+            cs, ss = n.chunks_sidelen, n.subsidelen
+            if cs % leaf:
+                raise ValueError("leaf_grid: a node's tiles of side %d are not made of %d x %d leaves" % (cs, leaf, leaf))
+            stride = ss * ss
+            for ch in range(stride):
+                tr, tc = (ch // ss) * cs, (ch % ss) * cs
+                if tr >= rows or tc >= cols:
+                    continue  # (outside the array: no leaf of the raster lies there)
+                mm = np.stack([n.min[ch + ts * stride], n.max[ch + ts * stride]], axis=1)
+                ref = n.references[ch]
+                sub = None
+                if ref is not None:
+                    if ref[0] != 2:
+                        raise ValueError("leaf_grid: only External references are stored by Superchunk::build (got tag %d)" % ref[0])
+                    sub_cid = node(n.external_cid)[ref[1]]
+                    sub = node(sub_cid)
+                    if isinstance(sub, _SuperNode):
+                        walk(sub, r0 + tr, c0 + tc)
+                        continue
+                h, w = min(cs, rows - tr), min(cs, cols - tc)
+                for i in range(0, h, leaf):
+                    for j in range(0, w, leaf):
+                        at = ((r0 + tr + i) // leaf) * ntj + (c0 + tc + j) // leaf
+                        if sub is None:  # elided: one value per instant, the node's max (superchunk.rs:330-334, 426-433)
+                            grid[at] = Leaf(None, mm[:, 1].copy(), 0, 0, mm, n.encoding, n.fractional_bits, True)
+                        else:
+                            exact = n.encoding in (MMEncoding.I32, MMEncoding.I64) or not round_ or sub[2] == n.fractional_bits
+                            grid[at] = Leaf(sub_cid, None, i, j, mm, n.encoding, n.fractional_bits, exact)
+
+        walk(top, 0, 0)
+        if any(g is None for g in grid):
+            raise ValueError("leaf_grid: segment %d leaves part of its %d x %d leaves uncovered" % (s, nti, ntj))
+        segments.append(grid)
+    return leaf, segments
 
 
 class Resolver:
@@ -341,6 +427,29 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return block.reshape([n for n, d in zip(block.shape, drop) if not d])
 
         return _Lazy(decode)
+
+    def raster(self):
+        """The variable as it is, as an EncodedRaster over its stored leaves (leaf_grid; dcdf_raster_create_tiles): its *_flat
+        queries answer dataset-level cubes, points and series in one launch each, elided tiles included.  Every chunk is opened
+        once, through the resolver's cache; the raster is cached on this (immutable) Variable."""
+        cached = self.__dict__.get("_raster_cache")
+        if cached is not None:
+            return cached
+        from .raster import EncodedRaster, RasterTile
+        T, R, Cc = self.shape
+        if T == 0:
+            raise ValueError("raster(): the variable holds no instants yet")
+        segs = self._time_pieces(0, T)
+        for i, (cid, a0, a1, _) in enumerate(segs):
+            n = a1 - a0
+            if a0 != 0 or (n != self.chunk_size and i != len(segs) - 1) or n > self.chunk_size:
+                raise ValueError("raster(): segment %d holds %d instants, not chunk_size %d" % (i, n, self.chunk_size))
+        leaf, grid = leaf_grid(self._resolver.objects, [s[0] for s in segs], self._k2_levels, self._round is not None)
+        tiles = [RasterTile(None if lf.cid is None else self._resolver.node(lf.cid), lf.row0, lf.col0, lf.values, lf.minmax, lf.encoding,
+                            lf.fractional_bits, lf.exact) for g in grid for lf in g]
+        r = EncodedRaster.from_tiles((T, R, Cc), tiles, leaf, self.chunk_size)
+        self.__dict__["_raster_cache"] = r
+        return r
 
     # ---- routing ----------------------------------------------------------------------------------------------------------
     def _root(self):

@@ -8,11 +8,19 @@ does that routing on the host -- vectorised over a whole batch of queries -- and
 through the batched C-ABI entry points (dcdf_query_fill_window_batch / dcdf_query_search_batch); the decoding itself is
 on the GPU.  BASELINE configs[4] is exactly this with tile = 256, chunk_size = 32.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib as L
+
+# One leaf of a raster over stored Superchunks (dcdf_raster_tile): chunk = an opened dcdf_amd.Chunk, or None for an elided leaf
+# whose value per instant is `values`; (row0, col0) = where the leaf starts inside its chunk; minmax = [instants, 2] stored
+# (min, max) of the node tile that holds the leaf (or None); encoding / fractional_bits = the node's (of values and minmax);
+# minmax_exact = minmax are exact values of the chunk's stored integers (value search may prune with them).
+RasterTile = collections.namedtuple("RasterTile", "chunk row0 col0 values minmax encoding fractional_bits minmax_exact",
+                                    defaults=(0, 0, None, None, L.DCDF_I64, 0, False))
 
 
 class EncodedRaster:
@@ -26,16 +34,43 @@ class EncodedRaster:
         if len(chunks) != self.nseg * self.nti * self.ntj:
             raise ValueError("expected %d chunks" % (self.nseg * self.nti * self.ntj))
         self.chunks = list(chunks)
-
+        self.tiles = None  # from_tiles: the RasterTile of every leaf
         self._native = None
+
+    @classmethod
+    def from_tiles(cls, shape, tiles, tile, chunk_size):
+        """A raster over stored Superchunks (dcdf_raster_create_tiles): tiles[(seg * nti + ti) * ntj + tj] = RasterTile, leaf size
+        `tile`.  The native queries (fill_windows_flat, search_flat, search_values_flat, get_flat, fill_cells_flat) take it; the
+        host-routed helpers (split and the methods built on it) refuse a raster with elided or offset leaves."""
+        r = cls(shape, list(tiles), tile, chunk_size)
+        r.tiles = [t if isinstance(t, RasterTile) else RasterTile(*t) for t in tiles]
+        r.chunks = [t.chunk for t in r.tiles]
+        r._handle()  # (bad tile tables fail here)
+        return r
 
     # ---- the same routing natively (dcdf_raster_*: split in C++, every piece decoded into its place by one launch) ---------
     def _handle(self):
         if self._native is None:
-            hs = (C.c_void_p * len(self.chunks))(*[c._h for c in self.chunks])
             shp = (C.c_uint32 * 3)(*self.shape)
             h = C.c_void_p()
-            L.check(L.lib().dcdf_raster_create(hs, C.c_size_t(len(self.chunks)), shp, self.tile, self.chunk_size, C.byref(h)), "raster_create")
+            if self.tiles is None:
+                hs = (C.c_void_p * len(self.chunks))(*[c._h for c in self.chunks])
+                L.check(L.lib().dcdf_raster_create(hs, C.c_size_t(len(self.chunks)), shp, self.tile, self.chunk_size, C.byref(h)), "raster_create")
+            else:
+                desc = (L.RasterTile * len(self.tiles))()
+                keep = []  # (values and minmax are copied by the call)
+                for d, t in zip(desc, self.tiles):
+                    d.chunk = t.chunk._h if t.chunk is not None else None
+                    d.row0, d.col0 = int(t.row0), int(t.col0)
+                    for name in ("values", "minmax"):
+                        a = getattr(t, name)
+                        if a is not None:
+                            a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+                            keep.append(a)
+                            setattr(d, name, a.ctypes.data)
+                    d.encoding, d.fractional_bits, d.minmax_exact = int(t.encoding), int(t.fractional_bits), 1 if t.minmax_exact else 0
+                L.check(L.lib().dcdf_raster_create_tiles(desc, C.c_size_t(len(desc)), shp, self.tile, self.chunk_size, C.byref(h)),
+                        "raster_create_tiles")
             self._native = h
         return self._native
 
@@ -113,6 +148,44 @@ class EncodedRaster:
                                                         C.c_void_p(offs.ctypes.data), C.byref(ms)), "raster_search_values_batch")
         return trip, offs, counts, ms.value
 
+    def get_flat(self, points, dtype=np.int64, out_device_ptr=None):
+        """Dataset-level points [n, 3] of (instant, row, col) through dcdf_raster_get_batch (Superchunk::get, superchunk.rs:313-352),
+        typed as fill_windows_flat.  Host form: returns (values of dtype [n], kernel ms); device form (out_device_ptr): value i is
+        written at element i there, returns kernel ms."""
+        from .chunk import _ENC
+        p = np.ascontiguousarray(np.asarray(points, dtype=np.uint32).reshape(-1, 3))
+        dtype = np.dtype(dtype)
+        ms = C.c_float()
+        out = None if out_device_ptr else np.empty(max(1, len(p)), dtype=dtype)
+        L.check(L.lib().dcdf_raster_get_batch(self._handle(), C.c_void_p(p.ctypes.data), C.c_size_t(len(p)),
+                                              C.c_void_p(out_device_ptr or out.ctypes.data), _ENC[dtype],
+                                              L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.byref(ms)), "raster_get_batch")
+        return ms.value if out_device_ptr else (out[:len(p)], ms.value)
+
+    def fill_cells_flat(self, cells, dtype=np.int64, out_device_ptr=None, out_offset=None):
+        """Dataset-level cell series [n, 4] of (start, end, row, col) through dcdf_raster_fill_cell_batch (Superchunk::fill_cell,
+        superchunk.rs:356-400).  Host form: returns (flat array of dtype, offsets uint64[n], kernel ms): series i is
+        flat[offsets[i]:offsets[i] + |end - start|].  Device form (out_device_ptr; out_offset in elements, None = one after the
+        other): returns kernel ms."""
+        from .chunk import _ENC
+        q = np.ascontiguousarray(np.asarray(cells, dtype=np.uint32).reshape(-1, 4))
+        dtype = np.dtype(dtype)
+        ms = C.c_float()
+        if out_device_ptr is None:
+            ln = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(ln)[:-1]
+            out = np.empty(max(1, int(ln.sum())), dtype=dtype)
+            L.check(L.lib().dcdf_raster_fill_cell_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(out.ctypes.data),
+                                                        _ENC[dtype], L.MEM_HOST, C.c_void_p(off.ctypes.data), C.byref(ms)), "raster_fill_cell_batch")
+            return out[:int(ln.sum())], off, ms.value
+        off = None if out_offset is None else np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_fill_cell_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(out_device_ptr),
+                                                    _ENC[dtype], L.MEM_DEVICE, None if off is None else C.c_void_p(off.ctypes.data), C.byref(ms)),
+                "raster_fill_cell_batch")
+        return ms.value
+
     @staticmethod
     def chunk_grid(shape, tile=256, chunk_size=32):
         """[(t0, t1, r0, r1, c0, c1)] of every chunk, in chunk-id order (segment-major, then tile row, tile col)."""
@@ -128,7 +201,10 @@ class EncodedRaster:
     def split(self, cubes):
         """cubes: int array [n, 6] of half-open (t0, t1, r0, r1, c0, c1), already inside the raster.  Returns
         sub[m, 8] = (query, chunk id, local t0, t1, r0, r1, c0, c1), ordered by query, then segment, tile row, tile col
-        (span.rs:190-216 over time, superchunk.rs:589-633 over rows/cols)."""
+        (span.rs:190-216 over time, superchunk.rs:589-633 over rows/cols).  Only for rasters whose every leaf is a whole chunk: the
+        chunk-level calls it feeds know nothing of elided or offset leaves (ValueError)."""
+        if self.tiles is not None and any(t.chunk is None or t.row0 or t.col0 for t in self.tiles):
+            raise ValueError("this raster has elided or offset leaves: the host-routed helpers cannot answer it; use the *_flat methods")
         q = np.asarray(cubes, dtype=np.int64)
         n = len(q)
         cs, tl = self.chunk_size, self.tile

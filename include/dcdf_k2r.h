@@ -269,6 +269,44 @@ int dcdf_raster_search_values_batch(const dcdf_raster* r, const dcdf_cube* cubes
                                     size_t nq, uint32_t* out, size_t cap, int out_mem, uint64_t* counts, uint64_t* offsets,
                                     float* kernel_ms);
 
+/* ---- rasters over stored Superchunks: elided tiles, nested levels, dataset-level get / fill_cell ----------------------------
+ * A variable stored through Superchunk::build is a tree per time segment: a tile whose value is uniform at every instant is
+ * elided (superchunk.rs:145-151; tiles outside the array too) and keeps one value per instant in its node's max Dac; a small
+ * remainder tile may be one chunk at an upper level (superchunk.rs:153-163).  A tiled raster takes that tree flattened into its
+ * leaves.  Leaves form the same grid as dcdf_raster_create's chunks: [(segment * nti + ti) * ntj + tj], leaf size `tile` =
+ * k^(last k2_level), each with the shape its place gives it. */
+typedef struct dcdf_raster_tile {
+    dcdf_chunk* chunk;        /* NULL: elided leaf (Reference::Elided)                                                      */
+    uint32_t row0, col0;      /* where the leaf starts inside `chunk` (non-zero only when one chunk spans several leaves)     */
+    const int64_t* values;    /* elided leaf: [instants] its value per instant = the eliding node's max Dac entry
+                                 (superchunk.rs:330-334, 426-433); NULL otherwise                                            */
+    const int64_t* minmax;    /* [instants][2] stored (min, max) of the node tile that holds this leaf (has_cells,
+                                 superchunk.rs:480-493); may be NULL                                                         */
+    int32_t encoding;         /* of values / minmax: the node's DCDF_I32 / I64 / F32 / F64                                   */
+    uint8_t fractional_bits;  /* of values / minmax: the node's                                                              */
+    uint8_t minmax_exact;     /* minmax are exact values of the chunk's stored integers (value search may prune)            */
+    uint8_t _pad[2];
+} dcdf_raster_tile;
+/* `values` and `minmax` are copied to the device here; no pointer is kept.  Lifetime and slab sharing as dcdf_raster_create.
+ * DCDF_ERR_BAD_ARG: a wrong tile count, a chunk leaf whose chunk does not cover [row0, row0 + leaf rows) x
+ * [col0, col0 + leaf cols) or has the wrong number of instants, an elided leaf without values, a bad encoding, float
+ * fractional_bits > 62.  A raster with no chunk leaf at all is valid.  dcdf_raster_fill_window_batch / search_batch /
+ * search_values_batch take tiled rasters: elided pieces are written (fill_window) or tested (search) on the device in the same
+ * call; the integer search of I32 / I64 rasters drops a piece whose leaf's minmax fails has_cells over the piece's instants
+ * (Superchunk::search), the value search prunes with minmax only where minmax_exact is set.  Searches of tiled rasters need
+ * k = 2 chunks (DCDF_ERR_UNSUPPORTED otherwise). */
+int dcdf_raster_create_tiles(const dcdf_raster_tile* tiles, size_t n_tiles, const uint32_t shape[3], uint32_t tile,
+                             uint32_t chunk_size, dcdf_raster** out);
+/* Dataset-level points {instant, row, col} (Superchunk::get, superchunk.rs:313-352) / series {start, end, row, col}
+ * (Superchunk::fill_cell, superchunk.rs:356-400) in raster coordinates, for every raster, plain or tiled.  One thread per point
+ * or series element; the result is typed like dcdf_query_fill_window_batch_typed (out_dtype, out_mem).  get: out[i] = point i.
+ * fill_cell: series i (reversed bounds swapped) at out + out_offset[i] (elements; out_offset NULL = the series one after the
+ * other).  DCDF_ERR_BOUNDS: a point or series outside the raster. */
+int dcdf_raster_get_batch(const dcdf_raster* r, const uint32_t* points, size_t n, void* out, int32_t out_dtype, int out_mem,
+                          float* kernel_ms);
+int dcdf_raster_fill_cell_batch(const dcdf_raster* r, const uint32_t* cells, size_t n, void* out, int32_t out_dtype,
+                                int out_mem, const uint64_t* out_offset, float* kernel_ms);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* fixed.rs:96-159 + mmbuffer.rs:596-613: per-tile suggest_fraction on the device; out_round = 1 for
  * Fraction::Round.  Host or device data per `mem`. */
