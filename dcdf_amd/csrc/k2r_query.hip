@@ -13,7 +13,9 @@
 #include <type_traits>
 #include <vector>
 
+#include "k2r_bulk.h"
 #include "k2r_decode.h"
+#include "k2r_query_types.h"
 #include "k2r_runtime.h"
 
 using namespace k2r;
@@ -79,21 +81,6 @@ struct EventPair {  // destroyed on every exit path
     }
 };
 
-struct TopEnt {  // the walk's state at one node (log.rs:360-361): both first-child indices NONE = its square has the one value mt + ms
-    uint32_t bt, bs;
-    int32_t mt, ms;  // (a chunk with a value beyond int32 gets no table: k_top_table reports it)
-};
-struct TopMM {  // smallest and largest value inside the same square (the reference's own pruning bounds: log.rs:573-574)
-    int32_t vmin, vmax;
-};
-struct ChunkRef {  // device-visible handle of an opened chunk
-    const uint8_t* bytes;
-    const InstDesc* descs;
-    uint32_t instants, rows, cols, fbits;
-    const TopEnt* top;  // [instant][top_g * top_g] or null
-    const TopMM* top_mm;  // the same squares' value ranges (search prunes with them)
-    uint32_t top_g, _pad;
-};
 
 // ---- host-side parser (chunk.rs:247-266, block.rs:99-109, snapshot.rs:62-81, log.rs:68-89,
 //      bitmap.rs:142-164, dac.rs:48-63): records byte offsets instead of materialising vectors ----
@@ -201,22 +188,9 @@ struct WinItem {
     uint64_t out_off;                    // element offset of cell (top, left) of this instant in `out`
 };
 constexpr int WQ_CAP = 192;             // frontier entries per wave: nodes of side >= k^2 meeting a 32 x 32 window, all levels
-constexpr uint32_t WQ_NONE = 0xffffffffu;
 struct WaveQ {
     uint32_t it[WQ_CAP], is[WQ_CAP], org[WQ_CAP];  // first child of the node in the log / snapshot tree (or NONE), origin row << 16 | col
     int64_t mt[WQ_CAP], ms[WQ_CAP];                 // log.rs:360-361 max_t, max_s
-};
-struct GpuExecScan {  // inclusive prefix sum over the 64 lanes (DPP), as GpuExec::wave_incl_scan
-    __device__ __forceinline__ static uint32_t incl(uint32_t v) {
-        int x = (int)v;
-        x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-        return (uint32_t)x;
-    }
 };
 // V = int64_t in general; int32_t for chunks whose stored values all lie in [-2^30, 2^30) (dcdf_chunk::narrow32: every node
 // extreme and every log difference then fits 32 bits), which halves the walk's arithmetic and its register footprint
@@ -650,101 +624,6 @@ k_search_wave(const ChunkRef* __restrict__ chunks, const WinItem* __restrict__ i
     }
 }
 
-// ---- k = 2, node-wise: one lane per frontier NODE, its four children share their loads ---------------------------------
-// Siblings are adjacent in every stream (children of a node sit at base .. base + 3): their four T bits and ranks come from
-// ONE 16-byte load of the rank block (+ its index word), their four Lmax bytes from ONE 4-byte load, their continuation bits
-// from the same kind of block load, the second bytes of the long ones from one more 4-byte load.  ~14 loads per node for both
-// trees instead of ~18 per CHILD.
-struct Blk16 {
-    uint32_t w[4];
-} __attribute__((aligned(1)));
-// The chunk bytes are global memory, but a pointer loaded from a table is "generic" to the compiler and every access through
-// it a FLAT instruction (slower, and counted in both wait counters): the node-wise walk uses address-space-1 pointers.
-typedef const __attribute__((address_space(1))) uint8_t* gbytes;
-__device__ __forceinline__ uint32_t gld32(gbytes p) {  // unaligned 4-byte load, native order
-    typedef uint32_t __attribute__((aligned(1))) u32u;
-    return *(const __attribute__((address_space(1))) u32u*)p;
-}
-__device__ __forceinline__ uint32_t gld_be32(gbytes p) { return __builtin_bswap32(gld32(p)); }
-__device__ __forceinline__ bool gbm_get(gbytes b, const BmDesc& d, uint32_t i) {
-    const uint32_t w = i >> 5;
-    if (w >= (d.len + 31) / 32) return false;
-    return (gld_be32(b + d.words_off + 4 * w) >> (31 - (i & 31))) & 1u;
-}
-// rank1(T, i) and the four bits i .. i+3 (bit i = 8), bits at or beyond d.len read as 0.  Needs d.k == 4 and i < d.len.
-__device__ __forceinline__ uint32_t rank_nib(gbytes b, const BmDesc& d, uint32_t i, uint32_t* nib) {
-    const uint32_t w0 = i >> 5, blk = w0 >> 2, sh = i & 31u;
-    uint32_t cnt = blk ? gld_be32(b + d.idx_off + 4 * (blk - 1)) : 0u;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(1)));
-    const u32x4 raw = *(const __attribute__((address_space(1))) u32x4*)(b + d.words_off + 16 * blk);
-    const uint32_t w[4] = {__builtin_bswap32(raw.x), __builtin_bswap32(raw.y), __builtin_bswap32(raw.z), __builtin_bswap32(raw.w)};
-    const uint32_t q0 = w0 & 3u;
-    uint32_t x = w[0], nx = w[1];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        if ((uint32_t)q < q0) cnt += popc32(w[q]);
-        if ((uint32_t)q == q0) {
-            x = w[q];
-            nx = q < 3 ? w[q + 1] : 0u;
-        }
-    }
-    if (q0 == 3 && sh > 28) nx = gld_be32(b + d.words_off + 4 * (w0 + 1));  // the group of four straddles the block's end (3 in 128)
-    if (sh) cnt += popc32(x >> (32 - sh));
-    uint32_t n4 = (uint32_t)(((((uint64_t)x << 32) | nx) >> (60 - sh)) & 15u);
-    const uint32_t valid = d.len - i;  // > 0
-    if (valid < 4) n4 &= (0xfu << (4 - valid)) & 0xfu;
-    *nib = n4;
-    return cnt;
-}
-// What the node-wise walk needs of one tree, copied out of its InstDesc once per item (wave-uniform: lives in SGPRs instead
-// of being re-fetched through a pointer the compiler must assume the output stores alias).
-struct TreeRef {
-    BmDesc T, E, c0, c1;      // T, eqB, continuation bitmaps of the Lmax Dac's planes 0 and 1
-    uint32_t by0, by1, nlev;  // Lmax plane-0 / plane-1 bytes, number of planes
-};
-typedef const __attribute__((address_space(1))) InstDesc* gdesc;
-__device__ __forceinline__ BmDesc bm_copy(const __attribute__((address_space(1))) BmDesc* p) { return BmDesc{p->len, p->k, p->idx_off, p->words_off}; }
-__device__ __forceinline__ TreeRef tree_ref(gdesc p) {
-    TreeRef t;
-    t.T = bm_copy(&p->T); t.E = bm_copy(&p->E); t.c0 = bm_copy(&p->mx.bm[0]); t.c1 = bm_copy(&p->mx.bm[1]);
-    t.by0 = p->mx.bytes_off[0]; t.by1 = p->mx.bytes_off[1]; t.nlev = p->mx.nlev;
-    return t;
-}
-__device__ __forceinline__ TreeRef tree_ref(const InstDesc& d) {
-    TreeRef t;
-    t.T = d.T; t.E = d.E; t.c0 = d.mx.bm[0]; t.c1 = d.mx.bm[1];
-    t.by0 = d.mx.bytes_off[0]; t.by1 = d.mx.bytes_off[1]; t.nlev = d.mx.nlev;
-    return t;
-}
-// the four Lmax values at index i .. i+3 (those at or beyond the Dac's length: 0); `full` = the whole Dac, for values of
-// three or more bytes (rare)
-template <class V>
-__device__ __forceinline__ void dac4(gbytes b, const TreeRef& t, const DacDesc& full, uint32_t i, V (&out)[4]) {
-    typedef typename std::conditional<sizeof(V) == 4, uint32_t, uint64_t>::type U;
-    const uint32_t len = t.c0.len;
-    const uint32_t b0 = gld32(b + t.by0 + i);
-    uint32_t cb = 0, r0 = 0;
-    if (t.nlev > 1) r0 = rank_nib(b, t.c0, i, &cb);
-    uint32_t cb1 = 0;
-    const uint32_t b1 = gld32(b + t.by1 + r0);  // (no branch: with a single plane by1 = r0 = 0, a harmless read of the chunk's first bytes)
-    if (t.nlev > 2 && cb) (void)rank_nib(b, t.c1, r0, &cb1);
-    uint32_t q = 0;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        U n = (b0 >> (8 * c)) & 0xffu;
-        const bool more = (cb >> (3 - c)) & 1u;
-        if (more) {
-            if ((cb1 >> (3 - q)) & 1u) {  // three or more bytes: the general walk
-                out[c] = i + c < len ? (V)dacd_get((const uint8_t*)b, full, i + c) : (V)0;
-                q++;
-                continue;
-            }
-            n |= (U)((b1 >> (8 * q)) & 0xffu) << 8;
-            q++;
-        }
-        out[c] = i + c < len ? (V)((n >> 1) ^ ((U)0 - (n & 1))) : (V)0;
-    }
-}
 template <class V>
 struct KidsT {
     NodeStT<V> st[4];
@@ -753,15 +632,6 @@ struct KidsT {
 };
 typedef KidsT<int64_t> Kids;
 // the four children of node p (log.rs:392-505 / snapshot.rs:281-299 for all of i, j at once)
-// bits i .. i + 3 of a bitmap (bit i = 8), bits beyond its words read as 0 like gbm_get; two loads, no branch
-__device__ __forceinline__ uint32_t gbm_get4(gbytes b, const BmDesc& d, uint32_t i) {
-    const uint32_t nw = (d.len + 31) / 32, w = i >> 5, sh = i & 31u;
-    const uint32_t w0 = w < nw ? w : 0u, w1 = w + 1 < nw ? w + 1 : 0u;
-    uint32_t x = gld_be32(b + d.words_off + 4 * w0), y = gld_be32(b + d.words_off + 4 * w1);
-    x = w < nw ? x : 0u;
-    y = w + 1 < nw ? y : 0u;
-    return (uint32_t)(((((uint64_t)x << 32) | y) >> (60 - sh)) & 15u);
-}
 template <class V>
 __device__ __forceinline__ void expand4(gbytes b, const TreeRef& S, const DacDesc& Sfull, const TreeRef& L, const DacDesc& Lfull,
                                         const NodeStT<V>& p, KidsT<V>* o) {
@@ -2983,6 +2853,155 @@ extern "C" int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cu
         }
     }
     if (rc != DCDF_OK) return rc;
+    if (!to_dev) {
+        if (dense) {
+            K2R_HIP(hipMemcpy((uint8_t*)out + out_offset[0] * es, d_o.p, total * es, hipMemcpyDeviceToHost));
+        } else {
+            std::vector<uint8_t> tmp(total * es);
+            K2R_HIP(hipMemcpy(tmp.data(), d_o.p, total * es, hipMemcpyDeviceToHost));
+            uint64_t run = 0;
+            for (size_t q = 0; q < nq; q++) {
+                const dcdf_cube c = norm_cube(cubes[q]);
+                const uint64_t cells = (uint64_t)(c.end - c.start) * (c.bottom - c.top) * (c.right - c.left);
+                if (cells) std::memcpy((uint8_t*)out + out_offset[q] * es, tmp.data() + run * es, cells * es);
+                run += cells;
+            }
+        }
+    }
+    float ms = 0.f;
+    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (kernel_ms) *kernel_ms = ms;
+    return DCDF_OK;
+}
+// ---- decompress: whole regions, block by block (k2r_bulk.hip) ---------------------------------------------------------------
+// The pieces of every cube, by the kind of leaf they fall on: a chunk with a side-16 table and 32-bit values becomes BulkUnits (a
+// workgroup per 64 x 64 region of the chunk's grid, looping over the piece's instants); any other chunk the wave items
+// dcdf_raster_fill_window_batch makes of it; an elided leaf a ConstPiece.  All three write the same output array.
+extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype, int out_mem,
+                                        const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu) return DCDF_ERR_BAD_ARG;
+    if (out_dtype != DCDF_I32 && out_dtype != DCDF_I64 && out_dtype != DCDF_F32 && out_dtype != DCDF_F64) return DCDF_ERR_BAD_ARG;
+    if (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) return DCDF_ERR_BAD_ARG;
+    if (!r->all_wave) return DCDF_ERR_UNSUPPORTED;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (nq == 0) return DCDF_OK;
+    const size_t es = (out_dtype == DCDF_I32 || out_dtype == DCDF_F32) ? 4 : 8;
+    const bool to_dev = out_mem == DCDF_MEM_DEVICE;
+    std::vector<uint64_t> base(nq);
+    uint64_t total = 0;
+    bool dense = true;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
+        dense = dense && out_offset[q] == total + out_offset[0];
+        base[q] = to_dev ? out_offset[q] : total;
+        total += (uint64_t)(c.end - c.start) * (c.bottom - c.top) * (c.right - c.left);
+    }
+    std::vector<BulkUnit> units;
+    std::vector<WinItem> items;
+    std::vector<ConstPiece> consts;
+    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells
+    uint32_t max_nt = 0;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
+        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
+            const uint64_t at = base[q] + ((uint64_t)(t0 + l.start - c.start) * wr + (r0 + l.top - c.top)) * wc + (c0 + l.left - c.left);
+            const uint64_t cells = (uint64_t)(l.end - l.start) * (l.bottom - l.top) * (l.right - l.left);
+            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
+            if (f.elided) {
+                consts.push_back(ConstPiece{cid, l.start, l.end, l.bottom - l.top, l.right - l.left, (uint32_t)wc, at, wr * wc});
+                n_const += cells;
+                return;
+            }
+            const dcdf_chunk* h = r->chunks[cid];
+            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
+            if (!(h->top_g && h->narrow32)) {
+                window_items(cid, k, at, items, r->all_node, wc, wr * wc);
+                n_walk += cells;
+                return;
+            }
+            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
+                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
+                    BulkUnit u{};
+                    u.chunk = cid;
+                    u.t0 = k.start;
+                    u.t1 = k.end;
+                    u.rr = (uint16_t)rr;
+                    u.rc = (uint16_t)rc;
+                    u.top = (uint16_t)std::max(rr, k.top);
+                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
+                    u.left = (uint16_t)std::max(rc, k.left);
+                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
+                    u.out_sr = (uint32_t)wc;
+                    u.out_st = wr * wc;
+                    u.out_off = at + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
+                    units.push_back(u);
+                }
+            max_nt = std::max(max_nt, k.end - k.start);
+            n_bulk += cells;
+        });
+        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || consts.size() > 0xfffffff0ull) return DCDF_ERR_CAPACITY;
+    }
+    if (stats) {
+        stats[0] = n_bulk;
+        stats[1] = n_walk;
+        stats[2] = n_const;
+    }
+    if (total == 0) return DCDF_OK;
+    // few units: a unit's instants in several workgroups (bulk_parts; each decodes its Snapshot again)
+    const uint32_t parts = bulk_parts(units.size(), max_nt, bulk_wanted_units());
+    if (parts > 1) {
+        std::vector<BulkUnit> split;
+        split.reserve(units.size() * parts);
+        for (const BulkUnit& u : units) {
+            const uint32_t nt = u.t1 - u.t0, np = bulk_parts(units.size(), nt, bulk_wanted_units());
+            for (uint32_t j = 0; j < np; j++) {
+                BulkUnit v = u;
+                v.t0 = bulk_part(u.t0, nt, np, j);
+                v.t1 = bulk_part(u.t0, nt, np, j + 1);
+                v.out_off = u.out_off + (uint64_t)(v.t0 - u.t0) * u.out_st;
+                if (v.t1 > v.t0) split.push_back(v);
+            }
+        }
+        units.swap(split);
+    }
+    DevBuf d_o, d_units, d_consts;
+    if (!to_dev) K2R_HIP(d_o.alloc_pooled(total * es));
+    void* const d_out = to_dev ? out : d_o.p;
+    if (!units.empty()) {
+        K2R_HIP(d_units.alloc_pooled(units.size() * sizeof(BulkUnit)));
+        K2R_HIP(hipMemcpy(d_units.p, units.data(), units.size() * sizeof(BulkUnit), hipMemcpyHostToDevice));
+    }
+    if (!consts.empty()) {
+        K2R_HIP(d_consts.alloc_pooled(consts.size() * sizeof(ConstPiece)));
+        K2R_HIP(hipMemcpy(d_consts.p, consts.data(), consts.size() * sizeof(ConstPiece), hipMemcpyHostToDevice));
+    }
+    DevBuf d_items;
+    if (!items.empty()) {
+        K2R_HIP(d_items.alloc_pooled(items.size() * sizeof(WinItem)));
+        K2R_HIP(hipMemcpy(d_items.p, items.data(), items.size() * sizeof(WinItem), hipMemcpyHostToDevice));
+    }
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    if (!consts.empty()) {
+        hipLaunchKernelGGL(k_raster_fill_const, dim3((uint32_t)std::min<uint64_t>(consts.size(), 256u * 64u)), dim3(256), 0, 0, d_consts.as<ConstPiece>(),
+                           (uint32_t)consts.size(), r->d_leaf.as<RasterLeaf>(), r->d_vals.as<int64_t>(), r->cs, d_out, out_dtype);
+        K2R_HIP(hipGetLastError());
+    }
+    const int rcb = launch_bulk_decode(r->d_refs.as<ChunkRef>(), d_units.as<BulkUnit>(), (uint32_t)units.size(), d_out, out_dtype);
+    if (rcb != DCDF_OK) return rcb;
+    if (!items.empty()) {
+        const int rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>(), (uint32_t)items.size(), d_out, out_dtype, nullptr, ev.e1, r->all_node,
+                                               r->all_narrow);
+        if (rc != DCDF_OK) return rc;
+    } else {
+        K2R_HIP(hipEventRecord(ev.e1, 0));
+        K2R_HIP(hipDeviceSynchronize());
+    }
     if (!to_dev) {
         if (dense) {
             K2R_HIP(hipMemcpy((uint8_t*)out + out_offset[0] * es, d_o.p, total * es, hipMemcpyDeviceToHost));

@@ -114,7 +114,7 @@ class _SuperNode:
             else:
                 self.references.append((tag, struct.unpack_from(">I", obj, pos)[0]))
                 pos += 4
-        self.external_cid = obj[pos:pos + 36]
+        self.external_cid = bytes(obj[pos:pos + 36])  # (a large node arrives as a view of the library's buffer: CIDs are keys)
         pos += 36
         (n_local,) = struct.unpack_from(">I", obj, pos)
         pos += 4
@@ -149,7 +149,7 @@ def leaf_grid(objects, segment_cids, k2_levels, round_):
                 n = _SuperNode(obj)
             elif obj[6] == NODE_LINKS:
                 (cnt,) = struct.unpack_from(">I", obj, 7)
-                n = [obj[11 + 36 * i:11 + 36 * i + 36] for i in range(cnt)]
+                n = [bytes(obj[11 + 36 * i:11 + 36 * i + 36]) for i in range(cnt)]
             elif obj[6] == NODE_MMSTRUCT3 and obj[7] == NODE_SUBCHUNK:
                 n = ("chunk", obj[8], obj[9])  # Chunk::write_to: encoding u8, fractional_bits u8 (chunk.rs:235-243)
             else:
@@ -242,7 +242,7 @@ class Resolver:
             kind = obj[6]
             if kind == NODE_LINKS:  # links.rs:65-76
                 (cnt,) = struct.unpack_from(">I", obj, 7)
-                n = [obj[11 + 36 * i:11 + 36 * i + 36] for i in range(cnt)]
+                n = [bytes(obj[11 + 36 * i:11 + 36 * i + 36]) for i in range(cnt)]
             elif kind == NODE_MMSTRUCT3 and obj[7] == NODE_SPAN:
                 n = _Span.parse(obj)
             elif kind == NODE_MMSTRUCT3 and obj[7] == NODE_SUPERCHUNK:
@@ -359,6 +359,17 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             for (ch, cu, dst), o in zip(jobs, off):
                 dst[...] = flat[int(o):int(o) + dst.size].reshape(dst.shape)
         return out
+
+    def decode(self, start=0, stop=None):
+        """The instants [start, stop) of the whole variable, decompressed: what window(start, stop, 0, rows, 0, cols) returns,
+        through raster().decode -- every chunk is decoded block by block in one call (dcdf_raster_decode_batch), elided tiles,
+        nested levels and offset leaves included."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        self._check(start, stop, 0, R, 0, Cc)
+        if start == stop:
+            return np.zeros((0, R, Cc), dtype=self.dtype)
+        return self.raster().decode(start, stop, dtype=self.dtype)
 
     def search(self, start, stop, top, bottom, left, right, lower, upper):
         """(instant, row, col) of the cells with lower <= stored value <= upper (mmarray.rs:206; span.rs:231-270): not in

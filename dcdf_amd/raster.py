@@ -40,7 +40,7 @@ class EncodedRaster:
     @classmethod
     def from_tiles(cls, shape, tiles, tile, chunk_size):
         """A raster over stored Superchunks (dcdf_raster_create_tiles): tiles[(seg * nti + ti) * ntj + tj] = RasterTile, leaf size
-        `tile`.  The native queries (fill_windows_flat, search_flat, search_values_flat, get_flat, fill_cells_flat) take it; the
+        `tile`.  The native queries (fill_windows_flat, decode_flat, search_flat, search_values_flat, get_flat, fill_cells_flat) take it; the
         host-routed helpers (split and the methods built on it) refuse a raster with elided or offset leaves."""
         r = cls(shape, list(tiles), tile, chunk_size)
         r.tiles = [t if isinstance(t, RasterTile) else RasterTile(*t) for t in tiles]
@@ -108,6 +108,44 @@ class EncodedRaster:
                                                       C.c_void_p(out_device_ptr), _ENC[dtype], L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
                                                       C.byref(ms)), "raster_fill_window_batch")
         return ms.value
+
+    def decode_flat(self, cubes, dtype=np.int64, out_device_ptr=None, out_offset=None):
+        """Decompress dataset-level cubes [n, 6] through dcdf_raster_decode_batch: the values fill_windows_flat returns, bit for
+        bit, decoded block by block (meant for whole tiles and long time ranges).  Host form: returns (flat array of dtype,
+        offsets uint64[n], kernel ms, stats); device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).
+        stats = uint64[3]: cells written by the bulk kernel, by the fallback walk, by the elided fill."""
+        from .chunk import _ENC
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        dtype = np.dtype(dtype)
+        ms = C.c_float()
+        stats = np.zeros(3, dtype=np.uint64)
+        if out_device_ptr is None:
+            vol = np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64)  # (reversed bounds are reordered, geom.rs:83-103)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = np.empty(max(1, int(vol.sum())), dtype=dtype)
+            L.check(L.lib().dcdf_raster_decode_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
+                                                     C.c_void_p(out.ctypes.data), _ENC[dtype], L.MEM_HOST, C.c_void_p(off.ctypes.data),
+                                                     C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_decode_batch")
+            return out, off, ms.value, stats
+        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_decode_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
+                                                 C.c_void_p(out_device_ptr), _ENC[dtype], L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
+                                                 C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_decode_batch")
+        return ms.value, stats
+
+    def decode(self, start=0, stop=None, dtype=np.int64):
+        """The instants [start, stop) of the whole raster, decompressed: ndarray [stop - start, rows, cols] of dtype."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        if start == stop:
+            return np.empty((0, R, Cc), dtype=np.dtype(dtype))
+        out, _, _, _ = self.decode_flat([[start, stop, 0, R, 0, Cc]], dtype)
+        return out[:(stop - start) * R * Cc].reshape(stop - start, R, Cc)
 
     def search_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
         """search of dataset-level cubes through dcdf_raster_search_batch: returns (triples uint32[hits, 3] in raster coordinates

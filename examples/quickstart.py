@@ -19,4 +19,8 @@ flat, offsets, _ = R.fill_windows_flat([(10, 20, 100, 140, 120, 200)], dtype=np.
 assert (flat.reshape(10, 40, 80) == a[10:20, 100:140, 120:200]).all()
 triples, offs, counts, _ = R.search_flat([(0, 32, 0, 256, 0, 256)], [100], [110])
 assert int(counts[0]) == len(hits)
+whole = R.decode(dtype=np.int32)
+assert whole.shape == a.shape and (whole == a).all()
+flat, offsets, _, stats = R.decode_flat([(0, 32, 0, 256, 0, 256)], dtype=np.int32)
+assert (flat.reshape(a.shape) == a).all() and int(stats[0]) == a.size
 print("readme example ok")

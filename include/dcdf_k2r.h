@@ -237,6 +237,13 @@ void dcdf_raster_destroy(dcdf_raster* r);
  * host or device memory.  k * k > 64 chunks: DCDF_ERR_UNSUPPORTED (use the per-chunk entry points). */
 int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype,
                                   int out_mem, const uint64_t* out_offset, float* kernel_ms);
+/* Decompress: the cubes of a raster (plain or tiled), dense [instants][rows][cols] of out_dtype at out + out_offset[q]
+ * (elements), host or device memory -- the same result, bit for bit, as dcdf_raster_fill_window_batch for the same
+ * arguments.  Meant for whole tiles and long time ranges: every chunk leaf that has a side-16 table is decoded block by
+ * block (one Snapshot visit per block and region); the others, and elided leaves, by the kernels fill_window uses.
+ * stats (may be NULL): cells written by {bulk kernel, fallback walk, elided fill}. */
+int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype,
+                             int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
 /* search of nq dataset-level cubes: (instant, row, col) triples in RASTER coordinates (span.rs:231-270 adds the segment offset,
  * superchunk.rs:516-585 the tile origin); query q's triples are out[3 * offsets[q] .. + 3 * counts[q]), ordered by piece
  * (segment, tile row, tile col), sorted inside a piece. */
