@@ -1,4 +1,4 @@
-// k2r_bulk.h -- the bulk decoder's work unit and launcher (k2r_bulk.hip), planned by dcdf_raster_decode_batch (k2r_query.hip).
+// k2r_bulk.h -- the bulk decoder's work unit and launcher (k2r_bulk.hip), planned by dcdf_raster_decode_batch (k2r_raster.hip).
 #pragma once
 #include "k2r_query_types.h"
 

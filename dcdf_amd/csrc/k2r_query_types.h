@@ -142,4 +142,153 @@ __device__ __forceinline__ uint32_t gbm_get4(gbytes b, const BmDesc& d, uint32_t
     return (uint32_t)(((((uint64_t)x << 32) | y) >> (60 - sh)) & 15u);
 }
 
+
+// ---- what the kernels of more than one translation unit, and the host code that feeds them, read ------------------------------------
+struct WinQuery {  // one fill_window / search request against one chunk
+    uint32_t chunk;
+    uint32_t start, end, top, bottom, left, right;
+    uint32_t _pad;
+    int64_t lower, upper;
+    uint64_t out_off;  // fill_window: first output element
+};
+// one (query, instant) of a search: its window bitmap
+struct SearchItem {
+    uint32_t query, instant;  // instant is absolute within the chunk
+    uint64_t bits_off;        // u32 words: the item's window bitmap, row-major over the query window (per-thread descent)
+    uint32_t w0, ncb;         // wave walk: first of the item's pieces (<= 64 x 64 cells from the window's origin, row-major; a bitmap
+                              // of 64 rows x 2 words each) and pieces per row; w0 == SI_FLAT: the flat bitmap above is the one in use
+};
+constexpr uint32_t SI_FLAT = 0xffffffffu;
+// one (chunk, instant, sub-window) of a wave walk: at most 32 x 32 cells (k_window_wave, k_search_wave) or 64 x 64 (k_window_wave2)
+struct WinItem {
+    uint32_t chunk, inst;
+    uint16_t top, bottom, left, right;  // sub-window, chunk coordinates, half-open
+    uint32_t out_sr;                     // output row stride in elements (column stride 1)
+    uint64_t out_off;                    // element offset of cell (top, left) of this instant in `out`
+};
+struct SearchExtra {
+    int64_t lower, upper;
+    // The reference's Log::search_window has no case for a single-node UNIFORM log over a multi-node snapshot (log.rs:527-548):
+    // it never reads eqB[0], seeds min_t with an empty Dac's 0 and descends the snapshot as if the log were "equal" with the
+    // root's difference.  Read as data, its result for such an instant is: every cell when min_s(root) >= lower and c <= upper
+    // (c = the instant's one value), no cell when min_s(root) > upper or c < lower, and otherwise the cells with
+    // lower <= s(cell) + (c - max_s(root)) <= upper.  quirk != 0 makes the walk do exactly that instead of the decode of the
+    // instant's true values.
+    uint32_t quirk, _pad;
+};
+struct PointQuery {  // get / fill_cell: one cell
+    uint32_t chunk, instant, row, col;
+};
+// counts of the (query, instant) items the wave walk marked: one thread each over the bitmaps of the item's pieces
+__device__ __forceinline__ uint32_t search_count_wave_item(const uint32_t* __restrict__ wbits, const SearchItem& I, const WinQuery& Q) {
+    const uint32_t nrb = (Q.bottom - Q.top + 63u) >> 6;
+    const uint4* w = (const uint4*)(wbits + (uint64_t)I.w0 * 128u);
+    uint32_t cnt = 0;
+    for (uint32_t i = 0; i < nrb * I.ncb * 32u; i++) {
+        const uint4 x = w[i];
+        cnt += popc32(x.x) + popc32(x.y) + popc32(x.z) + popc32(x.w);
+    }
+    return cnt;
+}
+// the triples of one wave-walk item: the pieces' bitmaps (64 rows x 2 words), rows in order, pieces left to right; the origin of
+// the chunk inside its raster (dcdf_raster_search_batch; zero for chunk-level searches) is added: a search does not use out_off /
+// _pad otherwise
+__device__ __forceinline__ void search_emit_wave_item(const SearchItem& I, const WinQuery& Q, const uint32_t* __restrict__ wbits,
+                                                      uint32_t* __restrict__ o) {
+    const uint32_t ot = Q._pad, orow = (uint32_t)Q.out_off, ocol = (uint32_t)(Q.out_off >> 32);
+    for (uint32_t r = Q.top; r < Q.bottom; r++) {
+        const uint32_t rb = (r - Q.top) >> 6, rr = (r - Q.top) & 63u;
+        for (uint32_t cw = 0; cw < 2u * I.ncb; cw++) {
+            uint32_t x = wbits[((uint64_t)I.w0 + rb * I.ncb + (cw >> 1)) * 128u + 2u * rr + (cw & 1u)];
+            while (x) {
+                const uint32_t j = (uint32_t)__builtin_ctz(x);
+                x &= x - 1;
+                o[0] = ot + I.instant;
+                o[1] = orow + r;
+                o[2] = ocol + Q.left + 32u * cw + j;
+                o += 3;
+            }
+        }
+    }
+}
+
+// ---- the node-wise walk's state and its step: shared by the query walks (k2r_query.hip) and the side-16 tables (k2r_open.hip) -------
+// V = int64_t in general; int32_t for chunks whose stored values all lie in [-2^30, 2^30) (dcdf_chunk::narrow32: every node
+// extreme and every log difference then fits 32 bits), which halves the walk's arithmetic and its register footprint
+template <class V>
+struct NodeStT {
+    uint32_t bt, bs;  // index of the node's FIRST CHILD in the log / snapshot tree (1 + rank(T, node) * k^2), or NONE
+    V mt, ms;         // log.rs:360-361 max_t, max_s
+};
+typedef NodeStT<int64_t> NodeSt;
+template <class V>
+struct KidsT {
+    NodeStT<V> st[4];
+    V val[4];
+    uint32_t fill;  // bit c: child c's whole square has the single value val[c]
+};
+typedef KidsT<int64_t> Kids;
+// the four children of node p (log.rs:392-505 / snapshot.rs:281-299 for all of i, j at once)
+template <class V>
+__device__ __forceinline__ void expand4(gbytes b, const TreeRef& S, const DacDesc& Sfull, const TreeRef& L, const DacDesc& Lfull,
+                                        const NodeStT<V>& p, KidsT<V>* o) {
+    // Every read below is unconditional (a side that has nothing to read reads index 0 and drops the result): behind
+    // `if (has_t)` / `if (has_s)` / per-child branches the log's chain of dependent loads, the snapshot's and up to four eqB
+    // reads ran one after the other; this way they are in flight together.
+    const bool has_t = p.bt != WQ_NONE, has_s = p.bs != WQ_NONE;
+    const bool cells_t = !has_t || p.bt >= L.T.len, cells_s = !has_s || p.bs >= S.T.len;  // the children are beyond T: cells
+    V dt[4], ds[4];
+    dac4(b, L, Lfull, has_t ? p.bt : 0u, dt);
+    dac4(b, S, Sfull, has_s ? p.bs : 0u, ds);
+    uint32_t tt = 0, ts = 0;  // T nibbles (bit c = 8 >> c) and rank of the first child
+    uint32_t rt = rank_nib(b, L.T, cells_t ? 0u : p.bt, &tt), rs = rank_nib(b, S.T, cells_s ? 0u : p.bs, &ts);
+    if (cells_t) { tt = 0; rt = 0; }
+    if (cells_s) { ts = 0; rs = 0; }
+    // eqB bits of the children with T = 0 (log.rs:452-467): child c's is eqB[p.bt + c - rank(T, p.bt + c)] = the (zeros among the
+    // children before c)-th bit from eqB[p.bt - rt] on -- four consecutive bits at most
+    const uint32_t eq4 = gbm_get4(b, L.E, cells_t ? 0u : p.bt - rt);
+    V vt[4], vs[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        vt[c] = has_t ? dt[c] : p.mt;
+        vs[c] = has_s ? ds[c] : (V)0;
+    }
+    o->fill = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const bool bit_t = (tt >> (3 - c)) & 1u, bit_s = (ts >> (3 - c)) & 1u;
+        const bool leaf_t = !has_t || cells_t || !bit_t, leaf_s = !has_s || cells_s || !bit_s;
+        const uint32_t before_t = popc32(tt >> (4 - c));
+        const uint32_t rtc = rt + before_t, rsc = rs + popc32(ts >> (4 - c));  // rank(T, base + c)
+        const V mt_ = vt[c], ms_ = has_s ? p.ms - vs[c] : p.ms;
+        o->val[c] = mt_ + ms_;
+        NodeStT<V>& n = o->st[c];
+        n.mt = mt_;
+        n.ms = ms_;
+        n.bt = WQ_NONE;
+        n.bs = WQ_NONE;
+        if (leaf_t && leaf_s) {
+            o->fill |= 1u << c;
+        } else if (leaf_s) {
+            n.bt = 1 + rtc * 4;
+        } else if (leaf_t) {
+            const bool eq = (eq4 >> (3 - ((uint32_t)c - before_t))) & 1u;
+            if (has_t && !cells_t && !eq) o->fill |= 1u << c;  // uniform, not "equal" (log.rs:452-467)
+            else n.bs = 1 + rsc * 4;
+        } else {
+            n.bt = 1 + rtc * 4;
+            n.bs = 1 + rsc * 4;
+        }
+    }
+}
+// (k = 2, items of at most 64 x 64 cells: they meet at most 5 x 5 nodes of side 16, 9 x 9 of side 8, 17 x 17 of side 4 -- 395
+//  frontier entries below the top table; walking from the root adds at most 1 + 4 + 4 + 9 above them)
+constexpr int WQ2_CAP = 448;
+template <class V>
+struct WaveQ2T {
+    uint32_t it[WQ2_CAP], is[WQ2_CAP], org[WQ2_CAP];
+    V mt[WQ2_CAP], ms[WQ2_CAP];
+};
+typedef WaveQ2T<int64_t> WaveQ2;
+
 }  // namespace k2r

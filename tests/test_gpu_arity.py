@@ -25,7 +25,7 @@ def dc():
     return dcdf_amd
 
 
-# ---- which kernel a chunk reaches (k2r_query.hip: wave_kernel_ok / node_kernel_ok) --------------------------------------
+# ---- which kernel a chunk reaches (k2r_query_host.h: wave_kernel_ok / node_kernel_ok) --------------------------------------
 def window_kernel(k, sidelen):
     if k == 2 and sidelen >= 4:
         return "k_window_wave2"

@@ -81,7 +81,7 @@ def query_source_sha():
     """Identifies the decode kernels' sources a committed PMC profile belongs to (roofline.traffic is only quoted for them)."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("k2r_common.h", "k2r_decode.h", "k2r_query.hip"):
+    for f in ("k2r_common.h", "k2r_decode.h", "k2r_query_types.h", "k2r_query_host.h", "k2r_open.hip", "k2r_query.hip", "k2r_raster.hip"):
         h.update(f.encode())
         h.update(open(os.path.join(ROOT, "dcdf_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]

@@ -61,7 +61,7 @@ def audit_kernels(obj):
 # one of which faults when it lands in LDS at 4-byte alignment -- is excluded per kernel: a kernel with LDS state must reach
 # it with ds_ instructions, and must not keep more than MAX_SCRATCH_OTHER bytes of scratch per lane (the universal encoder's
 # per-thread level cursors are the largest today, 560 B).
-OTHER_OBJECTS = ["k2r_query.o", "k2r_bulk.o", "k2r_generic.o", "k2r_superchunk.o", "k2r_cid.o", "k2r_suggest.o", "k2r_synth.o"]
+OTHER_OBJECTS = ["k2r_open.o", "k2r_query.o", "k2r_raster.o", "k2r_bulk.o", "k2r_generic.o", "k2r_superchunk.o", "k2r_cid.o", "k2r_suggest.o", "k2r_synth.o"]
 MAX_SCRATCH_OTHER = 1024
 
 

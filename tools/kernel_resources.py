@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Per-kernel resources of built objects, from the gfx950 code object's notes: VGPRs, AGPRs, SGPRs, scratch bytes per lane,
-LDS bytes, and how many ds_ / flat_ instructions the kernel has.  One JSON object per object file on stdout:
+LDS bytes, how many ds_ / flat_ instructions the kernel has, and a hash of its instruction text (the disassembly without the
+address and encoding columns and without the s_nop / zero padding behind its end, which depends on what follows the kernel in its
+object: equal hashes = the same instructions).  One JSON object per object file on stdout:
 
-    tools/kernel_resources.py dcdf_amd/csrc/_build/k2r_query.o dcdf_amd/csrc/_build/k2r_bulk.o
+    tools/kernel_resources.py dcdf_amd/csrc/_build/k2r_open.o dcdf_amd/csrc/_build/k2r_query.o dcdf_amd/csrc/_build/k2r_raster.o
 
 Two builds are compared by diffing the output (the query kernels before and after the bulk decoder)."""
+import hashlib
 import json
 import os
 import re
@@ -33,6 +36,7 @@ def resources(obj):
                      "scratch": f.get("private_segment_fixed_size"), "lds": f.get("group_segment_fixed_size"),
                      "vgpr_spill": f.get("vgpr_spill_count", 0), "sgpr_spill": f.get("sgpr_spill_count", 0), "ds": 0, "flat": 0}
     cur = None
+    text = {name: [] for name in out}
     for line in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
         if m:
@@ -40,6 +44,11 @@ def resources(obj):
         elif cur in out:
             out[cur]["ds"] += bool(re.search(r"\sds_", line))
             out[cur]["flat"] += bool(re.search(r"\sflat_(load|store|atomic)", line))
+            text[cur].append(line.split("//")[0].strip())
+    for name, lines in text.items():
+        while lines and lines[-1] in ("", "s_nop 0", "..."):
+            lines.pop()
+        out[name]["text_sha"] = hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16]
     return out
 
 
