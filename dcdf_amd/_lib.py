@@ -18,7 +18,7 @@ class TileDesc(C.Structure):
 
 class Encoded(C.Structure):
     _fields_ = [("bytes", C.POINTER(C.c_uint8)), ("len", C.c_size_t), ("snapshots", C.c_uint32), ("logs", C.c_uint32),
-                ("status", C.c_int32), ("_pad", C.c_int32), ("minmax", C.POINTER(C.c_int64))]
+                ("status", C.c_int32), ("kernel", C.c_int32), ("minmax", C.POINTER(C.c_int64))]
 
 
 class StoredObject(C.Structure):
@@ -55,7 +55,7 @@ _lib = None
 
 # every symbol include/dcdf_k2r.h declares
 SYMBOLS = [
-    "dcdf_chunk_build_batch", "dcdf_chunk_build", "dcdf_free_encoded", "dcdf_encoder_create", "dcdf_encoder_run",
+    "dcdf_chunk_build_batch", "dcdf_chunk_build", "dcdf_free_encoded", "dcdf_encoder_create", "dcdf_encoder_tile_kernel", "dcdf_encoder_run",
     "dcdf_encoder_result", "dcdf_encoder_fetch", "dcdf_encoder_gather_size", "dcdf_encoder_gather", "dcdf_encoder_total_bytes", "dcdf_encoder_destroy", "dcdf_superchunk_build", "dcdf_free_superchunk", "dcdf_chunk_open",
     "dcdf_chunk_close", "dcdf_chunk_info", "dcdf_chunk_get", "dcdf_chunk_fill_cell", "dcdf_chunk_fill_window",
     "dcdf_chunk_search", "dcdf_query_fill_window_batch", "dcdf_query_search_batch", "dcdf_query_fill_window_batch_typed", "dcdf_query_search_batch_mem", "dcdf_query_get_batch", "dcdf_query_fill_cell_batch", "dcdf_chunk_open_batch", "dcdf_chunk_instant_layout", "dcdf_raster_create", "dcdf_raster_destroy", "dcdf_raster_fill_window_batch", "dcdf_raster_search_batch", "dcdf_suggest_fraction", "dcdf_encoder_object_sha256",
@@ -103,6 +103,16 @@ def value_bounds(encoding, fractional_bits, lower, upper):
     check(lib().dcdf_value_bounds(int(encoding), int(fractional_bits), float(lower), float(upper), C.byref(lo), C.byref(hi), C.byref(sz)),
           "value_bounds")
     return lo.value, hi.value, bool(sz.value)
+
+
+def unpack_kernel(word):
+    """dcdf_encoded.kernel as Encoder.tile_kernel returns it: (log2_sidelen, padded, loader, generic_key); None for a
+    rejected tile."""
+    if word == 0:
+        return None
+    if word < (1 << 24):
+        return (-1, -1, -1, word)
+    return (word & 0xff, (word >> 8) & 0xff, (word >> 16) & 0xff, 0)
 
 
 def check(rc, what=""):

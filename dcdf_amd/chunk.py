@@ -62,6 +62,7 @@ class MMStruct3Build:  # mmstruct.rs:24-34
         self.snapshots = snapshots
         self.logs = logs
         self.minmax = minmax  # [instants, 2] stored (min, max) per instant
+        self.kernel = None    # build_batch: (log2_sidelen, padded, loader, generic_key), see Encoder.tile_kernel
 
 
 def _desc(a, fractional_bits, round_):
@@ -79,7 +80,8 @@ def _desc(a, fractional_bits, round_):
 
 def build_batch(arrays, k=2, fractional_bits=0, round=False):
     """Chunk::build for many independent tiles in one GPU launch.  Returns a list of MMStruct3Build
-    (or DcdfError instances for tiles the reference would have panicked on)."""
+    (or DcdfError instances for tiles the reference would have panicked on); either carries `.kernel`, the kernel the
+    staged tile was queued for (Encoder.tile_kernel; None for a tile rejected before any kernel)."""
     arrays = [np.asarray(a) for a in arrays]
     n = len(arrays)
     descs = (L.TileDesc * n)()
@@ -94,10 +96,12 @@ def build_batch(arrays, k=2, fractional_bits=0, round=False):
             e = out[i]
             if e.status != 0:
                 res.append(L.DcdfError(e.status, "Chunk::build"))
+                res[-1].kernel = L.unpack_kernel(e.kernel)
                 continue
             data = C.string_at(e.bytes, e.len)
             mm = np.ctypeslib.as_array(e.minmax, shape=(arrays[i].shape[0], 2)).copy()
             res.append(MMStruct3Build(Chunk(data, lazy=True), e.len, e.snapshots, e.logs, mm))
+            res[-1].kernel = L.unpack_kernel(e.kernel)
     finally:
         L.lib().dcdf_free_encoded(out, C.c_size_t(n))
     return res

@@ -196,6 +196,9 @@ struct dcdf_encoder {
     // (k2r_generic.hip); key = k << 8 | H
     std::vector<std::pair<uint32_t, std::vector<uint32_t>>> generic_groups;
     std::vector<uint8_t> is_generic;
+    // per tile: its index into `classes`, or -1 and the universal kernel's key in tile_gkey (dcdf_encoder_tile_kernel)
+    std::vector<int32_t> tile_class;
+    std::vector<uint32_t> tile_gkey;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t minmax_total = 0;
@@ -258,6 +261,8 @@ extern "C" int dcdf_encoder_create(const dcdf_tile_desc* tiles, size_t n, int k,
     e->slot_cap.resize(n);
     e->minmax_off.resize(n);
     e->is_generic.assign(n, 0);
+    e->tile_class.assign(n, -1);
+    e->tile_gkey.assign(n, 0);
     uint64_t out_total = 0, mm_total = 0;
     for (size_t i = 0; i < n; i++) {
         const dcdf_tile_desc& t = tiles[i];
@@ -269,6 +274,7 @@ extern "C" int dcdf_encoder_create(const dcdf_tile_desc* tiles, size_t n, int k,
         if (st != DCDF_OK) continue;
         if (gkey) {
             e->is_generic[i] = 1;
+            e->tile_gkey[i] = gkey;
             size_t gi = 0;
             for (; gi < e->generic_groups.size(); gi++)
                 if (e->generic_groups[gi].first == gkey) break;
@@ -283,6 +289,7 @@ extern "C" int dcdf_encoder_create(const dcdf_tile_desc* tiles, size_t n, int k,
                 e->class_tiles.emplace_back();
             }
             e->class_tiles[ci].push_back((uint32_t)i);
+            e->tile_class[i] = (int32_t)ci;
         }
         uint64_t cap = out_cap_per_tile ? out_cap_per_tile : (uint64_t)t.instants * t.rows * t.cols * 4 + 4096;
         cap = (cap + 255) & ~255ull;
@@ -411,6 +418,18 @@ extern "C" int dcdf_encoder_create(const dcdf_tile_desc* tiles, size_t n, int k,
                           hipMemcpyHostToDevice));
     K2R_HIP(hipMemcpy(e->d_args.p, e->args.data(), e->args.size() * sizeof(TileArgs), hipMemcpyHostToDevice));
     *enc_out = e.release();
+    return DCDF_OK;
+}
+
+extern "C" int dcdf_encoder_tile_kernel(const dcdf_encoder* e, size_t i, int32_t* log2_sidelen, int32_t* padded, int32_t* loader,
+                                        uint32_t* generic_key) {
+    if (!e || i >= e->desc.size()) return DCDF_ERR_BAD_ARG;
+    if (e->pre_status[i] != DCDF_OK) return e->pre_status[i];
+    const int32_t ci = e->tile_class[i];
+    if (log2_sidelen) *log2_sidelen = ci < 0 ? -1 : (int32_t)e->classes[ci].log2s;
+    if (padded) *padded = ci < 0 ? -1 : (int32_t)e->classes[ci].padded;
+    if (loader) *loader = ci < 0 ? -1 : (int32_t)e->classes[ci].vec;
+    if (generic_key) *generic_key = e->tile_gkey[i];
     return DCDF_OK;
 }
 
@@ -1069,6 +1088,13 @@ static int build_group(const dcdf_tile_desc* tiles, size_t n, int k, int mem, dc
         out[i].minmax = nullptr;
         out[i].snapshots = ns;
         out[i].logs = nl;
+        {
+            int32_t lg = -1, pd = -1, ld = -1;
+            uint32_t gk = 0;
+            out[i].kernel = 0;
+            if (dcdf_encoder_tile_kernel(e, i, &lg, &pd, &ld, &gk) == DCDF_OK)
+                out[i].kernel = gk ? (int32_t)gk : (int32_t)((1u << 24) | ((uint32_t)ld << 16) | ((uint32_t)pd << 8) | (uint32_t)lg);
+        }
         if (st != DCDF_OK) continue;
         out[i].bytes = (uint8_t*)std::malloc(len ? len : 1);
         out[i].minmax = (int64_t*)std::malloc(16ull * tiles[i].instants);

@@ -160,6 +160,9 @@ K2R_HD void store_typed(void* out, int64_t off, int32_t dtype, int64_t v, uint32
 // non-decreasing in the stored n (rounding is monotone), so the matching n form one interval [lo, hi], less n = 0 for floats
 // when the interval holds it (`hole`, normalised so that it is only set when lo < 0 < hi).  float32 collapses many n into one
 // value once |n - 1| > 2^24, so the ends are found by bisection with the decoder's own expression, not by a closed form.
+// 62 fractional bits: from_fixed's divisor (int64_t)1 << 63 is -2^63 (the reference's too, fixed.rs:84), so the decoded
+// value is -(n - 1) / 2^63, non-INCREASING in n.  The matching n still form one interval: the bisection runs on -v(n), which
+// is non-decreasing, against the mirrored bounds [-upper, -lower].
 struct ValueRange {
     int64_t lo, hi;
     bool hole;   // stored 0 lies in [lo, hi] and is not a match
@@ -167,7 +170,8 @@ struct ValueRange {
 };
 // v(n) >= x (ge) or v(n) > x (!ge), exactly: a float32 value converts to double exactly
 K2R_HD bool vb_above(int32_t enc, uint32_t fbits, int64_t n, double x, bool ge) {
-    const double v = enc == ENC_F32 ? (double)from_fixed_f32(n, fbits) : from_fixed_f64(n, fbits);
+    double v = enc == ENC_F32 ? (double)from_fixed_f32(n, fbits) : from_fixed_f64(n, fbits);
+    if (fbits == 62) v = -v;  // (the wrapped divisor: see above; x is a mirrored bound then)
     return ge ? v >= x : v > x;
 }
 // the smallest n of [INT64_MIN + 1, INT64_MAX] with vb_above(n) (the predicate is monotone in n); *none when there is none
@@ -209,6 +213,11 @@ K2R_HD bool value_bounds(int32_t enc, uint32_t fbits, double lower, double upper
             if (hi > INT32_MAX) hi = INT32_MAX;
         }
     } else {
+        if (fbits == 62) {  // v(n) = -(n - 1) / 2^63: lower <= v <= upper  <=>  -upper <= -v <= -lower
+            const double x = -upper;
+            upper = -lower;
+            lower = x;
+        }
         bool none = false;
         if (lower == -__builtin_inf()) {
             lo = INT64_MIN;

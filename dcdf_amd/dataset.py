@@ -48,9 +48,16 @@ def _cid(obj):  # testing.rs:172-183 (MemoryMapper): CIDv1, codec 0x12, sha2-256
     return bytes([0x01, 0x12, 0x12, 0x20]) + hashlib.sha256(obj).digest()
 
 
-def _from_fixed(n, bits, dtype):  # fixed.rs:81-86: 0 is NaN, else (n - 1) / 2^(bits + 1)
+def _fixed_divisor(bits):
+    """from_fixed's divisor 1 << (bits + 1) as the reference and the device decode compute it, in i64 (fixed.rs:84): at 62
+    fractional bits it wraps to -2^63 and the decoded value changes sign."""
+    d = 1 << (bits + 1)
+    return float(d - (1 << 64) if d >= 1 << 63 else d)
+
+
+def _from_fixed(n, bits, dtype):  # fixed.rs:81-86: 0 is NaN, else (n - 1) / (1 << (bits + 1))
     if dtype in (np.float32, np.float64):
-        return dtype(np.nan) if n == 0 else dtype((n - 1) / float(1 << (bits + 1)))
+        return dtype(np.nan) if n == 0 else dtype((n - 1) / _fixed_divisor(bits))
     return dtype(n)
 
 
@@ -495,7 +502,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
     def _typed(self, stored, fbits):
         if self.dtype in (np.float32, np.float64):
             s = np.asarray(stored, dtype=np.int64)
-            out = ((s - 1) / float(1 << (fbits + 1))).astype(self.dtype)
+            out = ((s - 1) / _fixed_divisor(fbits)).astype(self.dtype)
             out[s == 0] = np.nan
             return out
         return np.asarray(stored).astype(self.dtype)

@@ -26,6 +26,15 @@ class Encoder:
         L.check(L.lib().dcdf_encoder_create(self._descs, C.c_size_t(n), int(k), C.c_size_t(out_cap_per_tile),
                                             C.byref(self._h)), "encoder_create")
 
+    def tile_kernel(self, i):
+        """dcdf_encoder_tile_kernel: (log2_sidelen, padded, loader, generic_key) the session chose for tile i -- a fused
+        kernel k_encode<L, PADDED, VEC> (generic_key 0; loader 0 = generic, 1..4 = the int32 / float32 / int64 / float64
+        row loader) or the universal kernel (generic_key = k << 8 | levels, the rest -1)."""
+        lg, pd, ld, gk = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint32()
+        L.check(L.lib().dcdf_encoder_tile_kernel(self._h, C.c_size_t(i), C.byref(lg), C.byref(pd), C.byref(ld), C.byref(gk)),
+                "encoder_tile_kernel")
+        return lg.value, pd.value, ld.value, gk.value
+
     def run(self):
         ms = C.c_float()
         L.check(L.lib().dcdf_encoder_run(self._h, C.byref(ms)), "encoder_run")

@@ -66,7 +66,9 @@ typedef struct dcdf_encoded {
     uint32_t snapshots;   /* chunk.rs:93-94                                                            */
     uint32_t logs;
     int32_t status;       /* per-tile DCDF_* code; bytes == NULL when != 0                             */
-    int32_t _pad;
+    int32_t kernel;       /* dcdf_encoder_tile_kernel of the tile as the batch staged it (host tiles are packed dense): */
+                          /* 1 << 24 | loader << 16 | padded << 8 | log2_sidelen, or the universal kernel's key          */
+                          /* (< 1 << 24); 0 for a rejected tile.  (Was padding, always 0: same layout, ABI 3.)           */
     int64_t* minmax;      /* [instants][2] stored-value (min,max) per instant = root of each k2 tree;  */
                           /* what Superchunk::build recomputes at superchunk.rs:144 (mmbuffer.rs:366)  */
 } dcdf_encoded;
@@ -90,6 +92,15 @@ void dcdf_free_encoded(dcdf_encoded* out, size_t n);
  * per tile (0 = library default = raw tile bytes + 4 KiB). */
 typedef struct dcdf_encoder dcdf_encoder;
 int dcdf_encoder_create(const dcdf_tile_desc* tiles, size_t n, int k, size_t out_cap_per_tile, dcdf_encoder** enc);
+/* Which kernel dcdf_encoder_create chose for tile i, from the session's own tables (what the tests assert instead of restating
+ * the rule).  A fused-kernel tile: *log2_sidelen = 4..8, *padded = 0 / 1 (rows or cols below the sidelen), *loader = 0 (the
+ * generic strided loader) or 1..4 (the 16-byte row loader of int32 / float32 / int64 / float64 tiles: dense rows, 16-byte
+ * aligned base, row and instant strides), *generic_key = 0.  A tile of the universal kernel: *generic_key = k << 8 | levels, the
+ * other three -1.  Any out pointer may be NULL.  Returns the tile's validation code (then nothing is written) when create
+ * rejected it.  A fused tile whose values turn out beyond the fused kernel's 2^30 contract is re-encoded by the universal
+ * kernel at run time; this still reports the fused class it was queued for. */
+int dcdf_encoder_tile_kernel(const dcdf_encoder* enc, size_t i, int32_t* log2_sidelen, int32_t* padded, int32_t* loader,
+                             uint32_t* generic_key);
 /* Launches the encode kernels on the session's stream and waits.  kernel_ms (may be NULL) receives
  * the HIP-event time of the encode kernel alone. */
 int dcdf_encoder_run(dcdf_encoder* enc, float* kernel_ms);

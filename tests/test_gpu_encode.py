@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import encode_cases as E
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -68,27 +69,9 @@ def test_reference_fixtures(dc):  # testing.rs:200-249 (array8 cycled / tiled), 
 def test_random_kinds_all_sidelens(dc):
     arrays = []
     for shape in [(5, 8, 8), (7, 16, 16), (6, 32, 32), (5, 64, 64), (4, 128, 128), (3, 256, 256)]:
-        for kind in ["small", "wide", "noise", "const", "sparse"]:
+        for kind in E.INT_KINDS:  # small, wide, noise, const, sparse: the fields of tests/encode_cases.py
             rng = np.random.default_rng(hash((shape, kind)) & 0xFFFF)
-            T, R, Cc = shape
-            if kind == "small":
-                a = rng.integers(-3, 4, size=shape)
-            elif kind == "wide":
-                a = rng.integers(-(2 ** 29), 2 ** 29, size=shape)
-                a[1] = a[0] + rng.integers(-300, 300, size=(R, Cc))
-            elif kind == "noise":
-                a = rng.integers(0, 70000, size=shape)
-            elif kind == "const":
-                a = np.zeros(shape, dtype=np.int64) + 5
-                a[2:] += 1
-            else:
-                base = rng.integers(-100, 100, size=(R, Cc))
-                a = np.stack([base.copy() for _ in range(T)])
-                for i in range(1, T):
-                    for _ in range(3):
-                        a[i, rng.integers(R), rng.integers(Cc)] += rng.integers(-500, 500)
-                    if i == 3 % T:
-                        a[i, : R // 2, : Cc // 2] += 7
+            a = E.int_field(kind, shape, rng)
             arrays += [a.astype(np.int64), a.astype(np.int32)]
     assert_same(dc, arrays)
 
@@ -211,8 +194,12 @@ def test_int32_rows_value_range_contract(dc):
 @pytest.mark.parametrize("dtype", [np.int32, np.int64, np.float32, np.float64])
 def test_row_loader_selection_aligned_and_not(dc, dtype):
     """Every element type has a 16-byte row loader for aligned, unit-stride tiles and falls back to the generic loader
-    otherwise (misaligned base, odd row stride, transposed view): all of them must give the oracle's bytes."""
+    otherwise (misaligned base, odd row stride, transposed view): all of them must give the oracle's bytes.  From HOST
+    arrays the batch packs every tile dense at an aligned staging offset, so all four views take the row loader; the same
+    four views of DEVICE memory are encoded where they lie, and there the last three do fall back.  Which kernel ran is the
+    library's own answer both ways."""
     from dcdf_amd import synth
+    from dcdf_amd.encoder import DeviceBuffer, Encoder
     fb = 3 if np.dtype(dtype).kind == "f" else 0
     big = synth.cells(11, 0, 5, 0, 66, 0, 70, np.int32)
     big = (big / 8.0).astype(dtype) if fb else big.astype(dtype)
@@ -221,7 +208,38 @@ def test_row_loader_selection_aligned_and_not(dc, dtype):
     shifted = big[:, 1:65, 1:65]           # base not 16-byte aligned, row stride 70
     odd = np.ascontiguousarray(big[:, :64, :67])[:, :, :64]  # row stride 67 elements
     transposed = np.ascontiguousarray(big[:, :64, :64].transpose(0, 2, 1)).transpose(0, 2, 1)  # column stride != 1
-    assert_same(dc, [aligned, shifted, odd, transposed], fractional_bits=fb)
+    views = [aligned, shifted, odd, transposed]
+    assert_same(dc, views, fractional_bits=fb)
+    loader = E.LOADER[np.dtype(dtype)]
+    for r in dc.build_batch(views, fractional_bits=fb):
+        assert r.kernel == (6, 0, loader, 0)  # staged dense and aligned: the row loader, whatever the host strides were
+        r.data.close()
+    # the device-view variant: each view's backing array in device memory, the view described by its own strides
+    esz = np.dtype(dtype).itemsize
+    bufs, descs = [], []
+    for v in views:
+        backing = v if v.base is None else v.base
+        while backing.base is not None:
+            backing = backing.base
+        assert backing.flags["C_CONTIGUOUS"]
+        off = v.ctypes.data - backing.ctypes.data
+        lo, hi = E.extent(off, [s // esz for s in v.strides], v.shape, esz)
+        assert 0 <= lo and hi <= backing.nbytes
+        b = DeviceBuffer(backing.nbytes)
+        b.write(0, backing)
+        bufs.append(b)
+        descs.append((b.ptr + off, O.ENC[np.dtype(dtype)], tuple(s // esz for s in v.strides), v.shape, fb, False))
+    enc = Encoder(descs, k=2)
+    enc.run()
+    assert [enc.tile_kernel(i) for i in range(4)] == [(6, 0, loader, 0), (6, 0, 0, 0), (6, 0, 0, 0), (6, 0, 0, 0)]
+    for i, v in enumerate(views):
+        ref, rs, rl, _ = O.chunk_build(v, want_snapshots=True, fractional_bits=fb)
+        st, ln, ns, nl = enc.result(i)
+        assert st == 0 and (ns, nl) == (rs, rl)
+        assert enc.fetch(i) == ref, i
+    enc.close()
+    for b in bufs:
+        b.free()
 
 
 _SHA_SCRIPT = r"""

@@ -385,3 +385,33 @@ def test_cpc_precipitation_between_10_and_20_mm(ds):
     assert len(want) > 0 and np.array_equal(got, want)
     for lo, hi in [(0.0, 0.0), (0.1, 0.2), (50.0, INF), (-INF, INF)]:
         check_var(v, lo, hi, (0, 1, 40, 300, 100, 650))
+
+
+def test_62_fractional_bits_follow_the_decoders_wrapped_divisor(dc):
+    """At 62 fractional bits from_fixed's divisor, 1 << 63 in i64, is -2^63 (fixed.rs:84): the decoded value is the negated input,
+    falling as the stored integer rises.  A 16 x 16 float64 chunk of multiples of 2^-62 in (-1, 1): the typed fill_window equals
+    the oracle's, and value search the brute force over what fill_window returned."""
+    rng = np.random.default_rng(62)
+    T, side = 3, 16
+    m = rng.integers(-(1 << 62) + 1, 1 << 62, size=(T, side, side))
+    x = m.astype(np.float64) / 2.0 ** 62
+    x[0, 0, :6] = [0.25, -0.25, 0.5, -0.5, 0.0, 2.0 ** -62]
+    x[1, 3, 3:6] = np.nan
+    x[2] = x[1]
+    x[2, 5, 5] = 0.25
+    assert (np.abs(x[np.isfinite(x)]) < 1).all()
+    b = dc.Chunk.build(x, fractional_bits=62)
+    ref = O.chunk_build(x, fractional_bits=62)
+    assert b.data.write_to() == ref
+    ch = b.data
+    w = ch.fill_window(dc.Cube(0, T, 0, side, 0, side))
+    want = O.Chunk(ref).fill_window(0, T, 0, side, 0, side)
+    assert w.dtype == np.float64
+    np.testing.assert_array_equal(w, want)
+    np.testing.assert_array_equal(w, -x)  # the reference's quirk, kept
+    v0 = float(w[1, 7, 7])
+    for lo, hi in [(0.1, 0.5), (-0.5, -0.1), (0.25, 0.25), (-0.25, -0.25), (-1.0, 1.0), (-INF, INF), (0.0, 0.0), (-INF, 0.0), (0.0, INF),
+                   (v0, v0), (math.nextafter(v0, INF), INF), (-INF, math.nextafter(v0, -INF)), (0.5, 0.1), (2.0, 3.0)]:
+        check_chunk(ch, dc.Cube(0, T, 0, side, 0, side), lo, hi, w)
+        check_chunk(ch, dc.Cube(1, T, 2, side - 1, 1, side - 3), lo, hi, w)
+    assert len(ch.search_values(dc.Cube(0, T, 0, side, 0, side), 0.1, 0.5)) == int(((w >= 0.1) & (w <= 0.5)).sum()) > 0

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import encode_cases as E
 import oracle_lib as O
 import sim_lib as S
 from dcdf_amd import synth
@@ -46,26 +47,7 @@ def test_reference_fixture_tiled(n, dtype):  # testing.rs:242-249
 @pytest.mark.parametrize("kind", ["small", "wide", "noise", "const", "sparse"])
 def test_random_unpadded(shape, kind):
     rng = np.random.default_rng(hash((shape, kind)) & 0xFFFF)
-    T, R, Cc = shape
-    if kind == "small":
-        a = rng.integers(-3, 4, size=shape)
-    elif kind == "wide":  # forces 2-4 byte DAC values
-        a = rng.integers(-(2 ** 29), 2 ** 29, size=shape)
-        a[1] = a[0] + rng.integers(-300, 300, size=(R, Cc))
-    elif kind == "noise":
-        a = rng.integers(0, 70000, size=shape)
-    elif kind == "const":
-        a = np.zeros(shape, dtype=np.int64) + 5
-        a[2:] += 1
-    else:
-        base = rng.integers(-100, 100, size=(R, Cc))
-        a = np.stack([base.copy() for _ in range(T)])
-        for i in range(1, T):
-            for _ in range(3):
-                a[i, rng.integers(R), rng.integers(Cc)] += rng.integers(-500, 500)
-            if i == 3:
-                a[i, : R // 2, : Cc // 2] += 7  # "equal" quadrant (eqB = 1)
-    a = a.astype(np.int64)
+    a = E.int_field(kind, shape, rng)  # the fields of tests/encode_cases.py ("wide" forces 2-4 byte DAC values, "sparse" eqB = 1)
     check(a)
     check(a.astype(np.int32))
     check(a.astype(np.int32), force_novec=True)

@@ -17,12 +17,18 @@ I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 INF = float("inf")
 
 
+def divisor(bits):
+    """from_fixed's divisor (int64_t)1 << (bits + 1) (fixed.rs:84): wrapped to -2^63 at 62 fractional bits."""
+    d = 1 << (bits + 1)
+    return d - (1 << 64) if d >= 1 << 63 else d
+
+
 def value(enc, bits, n):
     """The typed value of stored n, as store_typed computes it (None for the NaN code)."""
     if enc == L.DCDF_F32:
-        return None if n == 0 else float(np.float32(np.int64(n - 1)) / np.float32(2.0 ** (bits + 1)))
+        return None if n == 0 else float(np.float32(np.int64(n - 1)) / np.float32(divisor(bits)))
     if enc == L.DCDF_F64:
-        return None if n == 0 else float(np.float64(np.int64(n - 1)) / np.float64(2.0 ** (bits + 1)))
+        return None if n == 0 else float(np.float64(np.int64(n - 1)) / np.float64(divisor(bits)))
     return n  # (a Python int: compared with a float exactly)
 
 
@@ -40,11 +46,11 @@ def domain(enc):
 
 
 def first(enc, bits, pred):
-    """Smallest n of the domain with pred(v(n)) for a monotone pred, by bisection over Python ints (None: there is none)."""
+    """Smallest n of the domain with pred(w(n)) for a monotone pred, by bisection over Python ints (None: there is none).
+    w(n) = v(n), the typed value, where that is non-decreasing in n; -v(n) at 62 fractional bits, where the divisor is negative."""
     lo, hi = domain(enc)
-    f = (lambda n: pred(float(np.float32(np.int64(n - 1)) / np.float32(2.0 ** (bits + 1))))) if enc == L.DCDF_F32 else \
-        (lambda n: pred(float(np.float64(np.int64(n - 1)) / np.float64(2.0 ** (bits + 1))))) if enc == L.DCDF_F64 else \
-        (lambda n: pred(n))
+    sign = -1.0 if divisor(bits) < 0 else 1.0
+    f = (lambda n: pred(n)) if enc in (L.DCDF_I32, L.DCDF_I64) else (lambda n: pred(sign * value(enc, bits, n if n != 0 else 1)))
     if not f(hi):
         return None
     while lo < hi:
@@ -59,6 +65,8 @@ def first(enc, bits, pred):
 def reference(enc, bits, lower, upper):
     """(lo, hi, hole) or None when nothing matches, from the predicate alone."""
     lower, upper = min(lower, upper), max(lower, upper)
+    if enc in (L.DCDF_F32, L.DCDF_F64) and divisor(bits) < 0:  # lower <= v <= upper  <=>  -upper <= -v <= -lower
+        lower, upper = -upper, -lower
     dlo, dhi = domain(enc)
     # -inf is unbounded: every stored integer, INT64_MIN included (which to_fixed never produces)
     nlo = (I32_MIN if enc == L.DCDF_I32 else I64_MIN) if lower == -INF else first(enc, bits, lambda v: v >= lower)
@@ -108,13 +116,14 @@ def check(enc, bits, lower, upper):
         assert matches(enc, bits, -1, a, b) and matches(enc, bits, 1, a, b)
 
 
-FLOATS = [(L.DCDF_F32, b) for b in (0, 1, 2, 8, 16, 29, 34)] + [(L.DCDF_F64, b) for b in (0, 1, 2, 8, 16, 29, 34, 52)]
+FLOATS = [(L.DCDF_F32, b) for b in (0, 1, 2, 8, 16, 29, 34, 62)] + [(L.DCDF_F64, b) for b in (0, 1, 2, 8, 16, 29, 34, 52, 61, 62)]
 
 
 def representable(enc, bits):
     """Bounds that are exactly values of some stored n, and their nextafter neighbours."""
     out = []
-    for n in (1, 2, 3, -1, -5, 1000, -(1 << 20), (1 << 24) + 1, (1 << 24) + 3, (1 << 40) + 12345, -(1 << 40) - 7):
+    for n in (1, 2, 3, -1, -5, 1000, -(1 << 20), (1 << 24) + 1, (1 << 24) + 3, (1 << 40) + 12345, -(1 << 40) - 7,
+              (1 << 61) + 1, -(1 << 61) + 1, (1 << 62) + 12345):
         v = value(enc, bits, n)
         out += [v, math.nextafter(v, INF), math.nextafter(v, -INF)]
     return out
@@ -137,7 +146,9 @@ def test_float_zero_infinities_reversed_and_the_hole(enc, bits):
     # a range that straddles the NaN code's neighbourhood sets the hole; one on either side does not
     lo, hi, hole = L.value_bounds(enc, bits, -1.0, 1.0)
     assert hole and lo < 0 < hi
-    for a, b in [(0.0, 1.0), (-1.0, -0.5), (0.5, 1.0)]:
+    # (value 0 is stored 1: a range that ends at 0 on the side of the stored integers above it has no hole -- the positive
+    # values, except at 62 bits, where the negative divisor puts the negative values there)
+    for a, b in [(0.0, 1.0) if divisor(bits) > 0 else (-1.0, 0.0), (-1.0, -0.5), (0.5, 1.0)]:
         assert not L.value_bounds(enc, bits, a, b)[2]
     assert L.value_bounds(enc, bits, 2.0, 1.0) == L.value_bounds(enc, bits, 1.0, 2.0)
 
@@ -178,6 +189,31 @@ def test_brute_force_small_bits():
                 assert got == matches(enc, bits, n, a, b), (enc, bits, lower, upper, n)
 
 
+@pytest.mark.parametrize("enc,bits", [(L.DCDF_F32, 62), (L.DCDF_F64, 62), (L.DCDF_F64, 61)])
+def test_brute_force_top_bits(enc, bits):
+    """61 and 62 fractional bits: every stored n of windows around 0, around the stored integers of +-0.25 and +-0.5 and at
+    both ends of int64, directly against the predicate.  At 62 bits the decoder's divisor is -2^63 (the reference's too), so
+    the value falls as n rises: stored -2^61 + 1 decodes to +0.25."""
+    assert divisor(61) == 1 << 62 and divisor(62) == -(1 << 63)
+    if bits == 62:
+        assert value(enc, bits, -(1 << 61) + 1) == 0.25 and value(enc, bits, (1 << 62) + 1) == -0.5
+    q = 1 << (bits - 1)  # |n - 1| of a value of magnitude 0.25
+    centres = [0, q, -q, 2 * q, -2 * q, I64_MAX - 70, I64_MIN + 71]
+    step = 2.0 ** -(bits + 1)
+    for lower, upper in [(0.1, 0.5), (-0.5, -0.1), (0.25, 0.25), (-0.25, 0.25), (-3 * step, 5 * step), (0.0, 0.0), (0.5, 0.25),
+                         (-INF, 0.25), (-0.25, INF), (-INF, INF), (-40 * step, -2 * step), (0.9999, 2.0), (-2.0, -0.9999)]:
+        lo, hi, hole = L.value_bounds(enc, bits, lower, upper)
+        a, b = min(lower, upper), max(lower, upper)
+        hits = 0
+        for c in centres:
+            for n in range(max(c - 70, I64_MIN + 1), min(c + 70, I64_MAX) + 1):
+                got = lo <= n <= hi and not (hole and n == 0)
+                assert got == matches(enc, bits, n, a, b), (enc, bits, lower, upper, n)
+                hits += got
+        if (lower, upper) in [(0.1, 0.5), (-0.5, -0.1), (0.25, 0.25)]:
+            assert hits > 0 and lo <= hi  # the range the 62-bit search used to report as empty
+
+
 @pytest.mark.parametrize("enc", [L.DCDF_I32, L.DCDF_I64])
 def test_integer_bounds(enc):
     cases = [(1.5, 2.5), (-1.5, 1.5), (0.0, 0.0), (-0.0, 0.0), (2.0, 2.0), (2.1, 2.9), (3.0, -3.0), (-INF, INF), (-INF, 5.0), (5.0, INF),
@@ -207,4 +243,27 @@ def test_bad_arguments():
     for enc, bits in [(7, 0), (L.DCDF_F32, 63), (L.DCDF_F64, 200)]:
         with pytest.raises(L.DcdfError):
             L.value_bounds(enc, bits, 0.0, 1.0)
-    assert L.value_bounds(L.DCDF_F64, 62, 0.0, 1.0)[0] == 1
+    # 62 bits is the most Chunk::build accepts; the divisor is -2^63 there, so [0, 1] is stored 1 (value 0) and everything below
+    assert L.value_bounds(L.DCDF_F64, 61, 0.0, 1.0)[0] == 1
+    assert L.value_bounds(L.DCDF_F64, 62, 0.0, 1.0) == (I64_MIN + 1, 1, True)
+    assert L.value_bounds(L.DCDF_F64, 62, -1.0, 0.0)[0] == 1
+
+
+def test_python_decode_mirrors_use_the_wrapped_divisor():
+    """dataset._from_fixed / Variable._typed decode elided fills on the host: the same value as the device decode and the
+    reference (the oracle's from_fixed), 62 fractional bits and its sign flip included."""
+    import oracle_lib as O
+    from dcdf_amd import dataset
+    assert [dataset._fixed_divisor(b) for b in range(63)] == [float(divisor(b)) for b in range(63)]
+    var = dataset.Variable.__new__(dataset.Variable)
+    ns = [1, 2, -1, 9, -(1 << 61) + 1, (1 << 61) + 1, (1 << 62) + 1, -(1 << 62) + 1, 12345678901, I64_MAX, I64_MIN + 1]
+    for bits in (0, 3, 52, 61, 62):
+        for dtype, ftype in ((np.float64, "f64"), (np.float32, "f32")):
+            var.encoding = dataset.MMEncoding.F64 if dtype is np.float64 else dataset.MMEncoding.F32
+            assert var.dtype is dtype
+            want = np.array([O.from_fixed(n, bits, ftype) for n in ns], dtype=dtype)
+            got = np.array([dataset._from_fixed(n, bits, dtype) for n in ns], dtype=dtype)
+            assert (got == want).all(), (bits, ftype)
+            assert (var._typed(np.array(ns, dtype=np.int64), bits) == want).all(), (bits, ftype)
+            assert np.isnan(dataset._from_fixed(0, bits, dtype)) and np.isnan(var._typed([0], bits)[0])
+    assert dataset._from_fixed(-(1 << 61) + 1, 62, np.float64) == 0.25
