@@ -62,7 +62,10 @@ SYMBOLS = [
     "dcdf_synth_fill", "dcdf_calib_read", "dcdf_device_alloc", "dcdf_device_free", "dcdf_device_copy", "dcdf_strerror", "dcdf_device_name", "dcdf_abi_version", "dcdf_last_hip_error", "dcdf_device_pool_trim",
     "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
+    "dcdf_raster_reduce_time_batch",
 ]
+# dcdf_raster_reduce_time_batch: the statistics, in plane order
+REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
 
 
 def lib():

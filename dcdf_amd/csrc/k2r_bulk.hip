@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "k2r_bulk.h"
+#include "k2r_reduce.h"
 #include "k2r_runtime.h"
 
 namespace k2r {
@@ -291,6 +292,264 @@ int launch_bulk_decode(const ChunkRef* d_refs, const BulkUnit* d_units, uint32_t
         case DCDF_F64: hipLaunchKernelGGL((k_bulk_decode<int32_t, ENC_F64>), grid, block, 0, 0, d_refs, d_units, n, d_out); break;
         default: return DCDF_ERR_BAD_ARG;
     }
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- reduction over time (k2r_reduce.h): the decode kernel with its stores replaced by per-cell accumulators ---------------
+// Four cells of one row of a state plane: p = element of chunk column c0 (a multiple of 4), clipped to [left, right).  Two
+// 16-byte accesses when the four cells are inside and p is aligned, single elements otherwise (bulk_store4's rule).
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void plane_load4(const double* p, double (&v)[4], uint32_t c0, uint32_t left, uint32_t right) {
+    if (c0 >= left && c0 + 4u <= right && ((uintptr_t)p & 15u) == 0) {
+        const f64x2 a = *(const __attribute__((address_space(1))) f64x2*)p, b = *(const __attribute__((address_space(1))) f64x2*)(p + 2);
+        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (c0 + (uint32_t)e >= left && c0 + (uint32_t)e < right) v[e] = ((const __attribute__((address_space(1))) double*)p)[e];
+    }
+}
+__device__ __forceinline__ void plane_store4(double* p, const double (&v)[4], uint32_t c0, uint32_t left, uint32_t right) {
+    if (c0 >= left && c0 + 4u <= right && ((uintptr_t)p & 15u) == 0) {
+        *(__attribute__((address_space(1))) f64x2*)p = f64x2{v[0], v[1]};
+        *(__attribute__((address_space(1))) f64x2*)(p + 2) = f64x2{v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (c0 + (uint32_t)e >= left && c0 + (uint32_t)e < right) ((__attribute__((address_space(1))) double*)p)[e] = v[e];
+    }
+}
+// One instant of four cells into their accumulators.  KIND 0: an integer chunk, x = (double)n.  KIND 1 / 2: a float32 / float64
+// chunk, stored 0 is NaN and skipped, x = from_fixed (k2r_decode.h) with the division by +-2^(fbits + 1) written as the product
+// with its reciprocal (inv / invf): both are exact, so the bits are from_fixed's.  lo / hi hold the extremes as stored integers
+// (from_fixed is monotone in n; sg = -1 mirrors n when the divisor is negative, fbits = 62) and are converted once per unit.
+template <uint32_t LIVE, int KIND>
+__device__ __forceinline__ void reduce_fold4(const int32_t (&v)[4], double (&s)[4], uint32_t (&cnt)[4], int32_t (&lo)[4], int32_t (&hi)[4],
+                                             double inv, float invf, int32_t sg) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int32_t n = v[e];
+        if constexpr (KIND == 0) {
+            if constexpr ((LIVE & RA_SUM) != 0) s[e] = s[e] + (double)n;
+            if constexpr ((LIVE & RA_MIN) != 0) lo[e] = n < lo[e] ? n : lo[e];
+            if constexpr ((LIVE & RA_MAX) != 0) hi[e] = n > hi[e] ? n : hi[e];
+        } else {
+            const bool ok = n != 0;
+            if constexpr ((LIVE & RA_SUM) != 0) {
+                const double x = KIND == 1 ? (double)((float)(n - 1) * invf) : (double)(n - 1) * inv;
+                const double a = s[e] + x;
+                s[e] = ok ? a : s[e];
+            }
+            if constexpr ((LIVE & RA_COUNT) != 0) cnt[e] += ok ? 1u : 0u;
+            const int32_t key = (n ^ sg) - sg;
+            if constexpr ((LIVE & RA_MIN) != 0) lo[e] = ok && key < lo[e] ? key : lo[e];
+            if constexpr ((LIVE & RA_MAX) != 0) hi[e] = ok && key > hi[e] ? key : hi[e];
+        }
+    }
+}
+
+// LIVE: the accumulators this instantiation carries (RA_*).  A thread owns the 16 cells k_bulk_decode stores per instant (two
+// groups of 2 rows x 4 columns); their accumulators stay in registers over the unit's instants.  SUM continues the chain of the
+// state plane: it is loaded before the first instant (0.0 when the unit starts its cube) and stored after the last.  COUNT, MIN
+// and MAX are merged into their planes at the end (identity NaN).  Cells outside the unit's rectangle are decoded as in
+// k_bulk_decode; their rows are not accumulated and nothing of them is written.
+template <uint32_t LIVE>
+__global__ void __launch_bounds__(256)
+k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const ReduceUnit* __restrict__ units, uint32_t n_units,
+              double* dst, double* scr, uint32_t ops) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const ReduceUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int32_t enc = (int32_t)encs[U.chunk];
+        const int kind = enc == ENC_F32 ? 1 : enc == ENC_F64 ? 2 : 0;
+        const int64_t div = (int64_t)1 << (C.fbits + 1u);  // from_fixed's divisor
+        const double inv = 1.0 / (double)div;
+        const float invf = 1.0f / (float)div;
+        const int32_t sg = kind != 0 && div < 0 ? -1 : 0;
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
+        const bool sq_in = r16 + qi < G && c16 + qj < G;
+        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        // accumulators of row 2 k + i of the thread's cells
+        double sum[4][4];
+        uint32_t cnt[4][4];
+        int32_t lo[4][4], hi[4][4];
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; a++) {
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) {
+                sum[a][e] = 0.0;
+                cnt[a][e] = 0u;
+                lo[a][e] = INT32_MAX;  // (beyond every stored value of a narrow32 chunk: "no value yet")
+                hi[a][e] = INT32_MIN;
+            }
+            if constexpr ((LIVE & RA_SUM) != 0) {
+                const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+                if (!U.init && r >= top && r < bottom && c0 + 4u > left && c0 < right)
+                    plane_load4(p_sum + (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left), sum[a], c0, left, right);
+            }
+        }
+        uint32_t cur_snap = 0xffffffffu;
+        for (uint32_t t = U.t0; t < U.t1; t++) {
+            const gdesc gD = (gdesc)C.descs + t;
+            const bool is_log = gD->is_log != 0;
+            const uint32_t snap = is_log ? gD->snap : t;
+            __syncthreads();  // (the previous instant's readers are done)
+            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
+                cur_snap = snap;
+                const TreeRef S = tree_ref((gdesc)C.descs + snap);
+                const DacDesc& Sfull = C.descs[snap].mx;
+                if (tid < 16u) {
+                    int32_t v = 0;
+                    uint32_t idx = WQ_NONE;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
+                        v = e.mt + e.ms;
+                        idx = e.bs;
+                    }
+                    pyr[BP_OFF[4] + tid] = v;
+                    nst[BN_OFF[4] + tid] = idx;
+                }
+                __syncthreads();
+                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+            }
+            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
+            const DacDesc& Lfull = C.descs[t].mx;
+            if (is_log) {
+                if (tid < 16u) {
+                    uint32_t st = BS_CONST;
+                    int32_t d = 0;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
+                        if (e.bt != WQ_NONE) {
+                            st = e.bt;
+                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
+                            st = BS_RES;
+                            d = e.mt;
+                        } else {
+                            d = e.mt + e.ms;
+                        }
+                    }
+                    nst[BN_OFF[4] + tid] = st;
+                    nd[BN_OFF[4] + tid] = d;
+                }
+                __syncthreads();
+                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+            }
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded where k_bulk_decode stores them ----
+#pragma unroll
+            for (uint32_t k = 0; k < 2u; k++) {
+                const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
+                if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
+                V v[2][4];
+#pragma unroll
+                for (uint32_t j = 0; j < 2u; j++) {
+                    const uint32_t n = rp * 32u + 2u * cg + j;
+                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
+                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
+                    if (!(st & BS_RES)) {
+                        V dt[4];
+                        dac4<V>(gb, L, Lfull, st, dt);
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
+                    } else {
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
+                    }
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < 2u; i++) {
+                    const uint32_t r = r0 + i, a = 2u * k + i;
+                    if (r < top || r >= bottom) continue;
+                    if (kind == 0) reduce_fold4<LIVE, 0>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                    else if (kind == 1) reduce_fold4<LIVE, 1>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                    else reduce_fold4<LIVE, 2>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                }
+            }
+        }
+        // ---- the unit's accumulators into the state planes ----
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; a++) {
+            const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+            if (r < top || r >= bottom || c0 + 4u <= left || c0 >= right) continue;
+            const int64_t at = (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left);
+            if constexpr ((LIVE & RA_SUM) != 0) plane_store4(p_sum + at, sum[a], c0, left, right);
+            if constexpr ((LIVE & RA_COUNT) != 0) {
+                double x[4], old[4] = {0.0, 0.0, 0.0, 0.0};
+                if (!U.init) plane_load4(p_cnt + at, old, c0, left, right);
+#pragma unroll
+                for (uint32_t e = 0; e < 4u; e++) x[e] = old[e] + (double)(kind != 0 ? cnt[a][e] : U.t1 - U.t0);
+                plane_store4(p_cnt + at, x, c0, left, right);
+            }
+            if constexpr ((LIVE & RA_MIN) != 0) {
+                double x[4], old[4];
+#pragma unroll
+                for (uint32_t e = 0; e < 4u; e++) {
+                    x[e] = lo[a][e] == INT32_MAX ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((lo[a][e] ^ sg) - sg));
+                    old[e] = __builtin_nan("");
+                }
+                if (!U.init) plane_load4(p_min + at, old, c0, left, right);
+#pragma unroll
+                for (uint32_t e = 0; e < 4u; e++) x[e] = fmin(old[e], x[e]);
+                plane_store4(p_min + at, x, c0, left, right);
+            }
+            if constexpr ((LIVE & RA_MAX) != 0) {
+                double x[4], old[4];
+#pragma unroll
+                for (uint32_t e = 0; e < 4u; e++) {
+                    x[e] = hi[a][e] == INT32_MIN ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((hi[a][e] ^ sg) - sg));
+                    old[e] = __builtin_nan("");
+                }
+                if (!U.init) plane_load4(p_max + at, old, c0, left, right);
+#pragma unroll
+                for (uint32_t e = 0; e < 4u; e++) x[e] = fmax(old[e], x[e]);
+                plane_store4(p_max + at, x, c0, left, right);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const ReduceUnit* d_units, uint32_t n, double* d_dst, double* d_scr,
+                       uint32_t ops) {
+    if (n == 0) return DCDF_OK;
+    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+#define K2R_REDUCE_CASE(L) \
+    case L: hipLaunchKernelGGL((k_bulk_reduce<L>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_dst, d_scr, ops); break;
+    switch (reduce_live(ops)) {
+        K2R_REDUCE_CASE(1) K2R_REDUCE_CASE(2) K2R_REDUCE_CASE(3) K2R_REDUCE_CASE(4) K2R_REDUCE_CASE(5)
+        K2R_REDUCE_CASE(6) K2R_REDUCE_CASE(7) K2R_REDUCE_CASE(8) K2R_REDUCE_CASE(9) K2R_REDUCE_CASE(10)
+        K2R_REDUCE_CASE(11) K2R_REDUCE_CASE(12) K2R_REDUCE_CASE(13) K2R_REDUCE_CASE(14) K2R_REDUCE_CASE(15)
+        default: return DCDF_ERR_BAD_ARG;
+    }
+#undef K2R_REDUCE_CASE
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

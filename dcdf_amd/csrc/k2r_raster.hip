@@ -8,6 +8,7 @@
 #include "k2r_bulk.h"
 #include "k2r_decode.h"
 #include "k2r_query_host.h"
+#include "k2r_reduce.h"
 
 using namespace k2r;
 
@@ -530,6 +531,276 @@ extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* c
         K2R_HIP(hipEventRecord(ev.e1, 0));
         K2R_HIP(hipDeviceSynchronize());
     }
+    const int rcf = W.finish();
+    if (rcf != DCDF_OK) return rcf;
+    float ms = 0.f;
+    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (kernel_ms) *kernel_ms = ms;
+    return DCDF_OK;
+}
+// ---- reduce over time: per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h) --------------------
+// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  What keeps the sum's order: within a
+// time segment every cell of a cube lies in exactly one piece (raster_pieces), so the work of one segment never shares a cell;
+// the segments are launched one after the other, in ascending order, on the null stream, and each piece continues the running
+// sum its cells' state plane holds.  The state planes are the output planes themselves (cube q's requested planes in ascending
+// bit order); SUM / COUNT kept for MEAN alone live in scratch planes.
+//
+// Pieces on chunks the bulk kernel does not take are decoded by the window walk as stored integers (DCDF_I64: store_typed
+// leaves n as it is) into a slab of a bounded number of cells, then folded by k_reduce_fold, which applies the leaf's own
+// encoding (reduce_widen: the conversions of store_typed, so the value is the typed fill_window's) -- one walk launch per slab
+// whatever mix of encodings its chunks have.  Elided pieces are folded by the same kernel straight from dcdf_raster::d_vals.
+__global__ void __launch_bounds__(256)
+k_reduce_fold(const FoldPiece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, double* dst,
+              double* scr, uint32_t ops) {
+    const uint32_t live = reduce_live(ops);
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const FoldPiece P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
+            const uint64_t at = e / P.cols * P.sr + e % P.cols;
+            double s = 0.0, c = 0.0, lo = __builtin_nan(""), hi = __builtin_nan("");
+            if (!P.init) {
+                if (live & RA_MIN) lo = p_min[at];
+                if (live & RA_MAX) hi = p_max[at];
+                if (live & RA_SUM) s = p_sum[at];
+                if (live & RA_COUNT) c = p_cnt[at];
+            }
+            for (uint32_t t = 0; t < P.nt; t++) {
+                const double x = reduce_widen(P.enc, P.fbits, P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e]);
+                if (x == x) {
+                    s = s + x;
+                    c = c + 1.0;
+                    lo = fmin(lo, x);
+                    hi = fmax(hi, x);
+                }
+            }
+            if (live & RA_MIN) p_min[at] = lo;
+            if (live & RA_MAX) p_max[at] = hi;
+            if (live & RA_SUM) p_sum[at] = s;
+            if (live & RA_COUNT) p_cnt[at] = c;
+        }
+    }
+}
+// the finishing kernel: MEAN = SUM / COUNT, NaN where nothing was counted
+__global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const MeanPiece P = ps[p];
+        const double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        const double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_mean = dst + P.o_off + (uint64_t)popc32(ops & RA_ALL) * P.psz;
+        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) {
+            const double c = p_cnt[e];
+            p_mean[e] = c == 0.0 ? __builtin_nan("") : p_sum[e] / c;
+        }
+    }
+}
+// cells of one fallback slab (K2R_REDUCE_SLAB_CELLS overrides: tests of the slab cut)
+static uint64_t reduce_slab_cells() {
+    const char* e = std::getenv("K2R_REDUCE_SLAB_CELLS");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : (uint64_t)1 << 22;
+}
+static int launch_reduce_fold(const FoldPiece* d_ps, uint32_t n, const int64_t* d_slab, const int64_t* d_vals, double* d_dst, double* d_scr,
+                              uint32_t ops) {
+    if (n == 0) return DCDF_OK;
+    hipLaunchKernelGGL(k_reduce_fold, dim3(std::min<uint32_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, n, d_slab, d_vals, d_dst, d_scr, ops);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
+                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || ops == 0 || ops > (RA_ALL | ROP_MEAN) ||
+        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE))
+        return DCDF_ERR_BAD_ARG;
+    if (!r->all_wave) return DCDF_ERR_UNSUPPORTED;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (nq == 0) return DCDF_OK;
+    const uint32_t live = reduce_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
+    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
+    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
+    std::vector<uint64_t> sbase(nq, 0);
+    uint64_t scr_total = 0;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
+        if (cube_cells(c) == 0) continue;
+        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
+        sbase[q] = scr_total;
+        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
+    }
+    WindowOut W(planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    // the plan, segment by segment
+    struct WalkPiece {  // a piece for the window walk: chunk, chunk-level cube, and its fold without the slab offset
+        uint32_t chunk;
+        dcdf_cube k;
+        FoldPiece f;
+    };
+    struct Segment {
+        std::vector<ReduceUnit> units;
+        std::vector<FoldPiece> consts;
+        std::vector<WalkPiece> walks;
+    };
+    std::vector<Segment> segs(r->nseg);
+    std::vector<MeanPiece> means;
+    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
+        means.push_back(MeanPiece{W.base[q], sbase[q], wr * wc});
+        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
+            Segment& S = segs[t0 / r->cs];
+            const uint64_t in_plane = (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
+            const uint32_t init = t0 + l.start == c.start;
+            const uint64_t cells = cube_cells(l);
+            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
+            FoldPiece p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, init, f.enc, f.fbits, 1u,
+                        (uint64_t)cid * r->cs + l.start, W.base[q] + in_plane, sbase[q] + in_plane, wr * wc};
+            if (f.elided) {
+                S.consts.push_back(p);
+                n_const += cells;
+                return;
+            }
+            const dcdf_chunk* h = r->chunks[cid];
+            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
+            if (!(h->top_g && h->narrow32)) {
+                p.enc = h->encoding;
+                p.fbits = h->fbits;
+                p.elided = 0;
+                S.walks.push_back(WalkPiece{cid, k, p});
+                n_walk += cells;
+                return;
+            }
+            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
+                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
+                    ReduceUnit u{};
+                    u.chunk = cid;
+                    u.t0 = k.start;
+                    u.t1 = k.end;
+                    u.rr = (uint16_t)rr;
+                    u.rc = (uint16_t)rc;
+                    u.top = (uint16_t)std::max(rr, k.top);
+                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
+                    u.left = (uint16_t)std::max(rc, k.left);
+                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
+                    u.sr = (uint32_t)wc;
+                    u.init = init;
+                    const uint64_t in_piece = (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
+                    u.o_off = p.o_off + in_piece;
+                    u.s_off = p.s_off + in_piece;
+                    u.psz = wr * wc;
+                    S.units.push_back(u);
+                }
+            n_bulk += cells;
+        });
+    }
+    if (stats) {
+        stats[0] = n_bulk;
+        stats[1] = n_walk;
+        stats[2] = n_const;
+    }
+    if (W.total == 0) return DCDF_OK;
+    // One upload of every segment's work.  The window walk's pieces are cut into slabs here: a slab holds whole pieces up to the
+    // cell bound; a piece beyond it is cut in time, each part a slab of its own (two parts of one piece share their cells, so
+    // they must not be folded by the same launch).
+    struct Slab {
+        size_t item0, item1, fold0, fold1;
+    };
+    struct SegRange {
+        size_t unit0, unit1, const0, const1, slab0, slab1;
+    };
+    std::vector<ReduceUnit> units;
+    std::vector<FoldPiece> folds;
+    std::vector<WinItem> items;
+    std::vector<Slab> slabs;
+    std::vector<SegRange> ranges;
+    const uint64_t slab_cap = reduce_slab_cells();
+    uint64_t slab_max = 0;
+    for (Segment& S : segs) {
+        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
+        SegRange g{units.size(), 0, folds.size(), 0, slabs.size(), 0};
+        units.insert(units.end(), S.units.begin(), S.units.end());
+        folds.insert(folds.end(), S.consts.begin(), S.consts.end());
+        g.unit1 = units.size();
+        g.const1 = folds.size();
+        Slab cur{items.size(), 0, folds.size(), 0};
+        uint64_t used = 0;
+        auto flush = [&] {
+            cur.item1 = items.size();
+            cur.fold1 = folds.size();
+            if (cur.fold1 > cur.fold0) slabs.push_back(cur);
+            slab_max = std::max(slab_max, used);
+            cur = Slab{items.size(), 0, folds.size(), 0};
+            used = 0;
+        };
+        for (const WalkPiece& w : S.walks) {
+            const uint64_t plane = (uint64_t)w.f.rows * w.f.cols;
+            const uint32_t nt = w.f.nt, step = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, slab_cap / plane));
+            if (step < nt || used + (uint64_t)nt * plane > slab_cap) flush();
+            for (uint32_t a = 0; a < nt; a += step) {
+                const uint32_t b = std::min(nt, a + step);
+                dcdf_cube k = w.k;
+                k.start = w.k.start + a;
+                k.end = w.k.start + b;
+                FoldPiece f = w.f;
+                f.nt = b - a;
+                f.init = w.f.init && a == 0;
+                f.src = used;
+                window_items(w.chunk, k, used, items, r->all_node);
+                folds.push_back(f);
+                used += (uint64_t)(b - a) * plane;
+                if (step < nt) flush();
+            }
+        }
+        flush();
+        g.slab1 = slabs.size();
+        ranges.push_back(g);
+        S = Segment{};
+        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || folds.size() > 0xfffffff0ull) return DCDF_ERR_CAPACITY;
+    }
+    DevBuf d_units, d_folds, d_items, d_means, d_slab, d_scr;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    double* const d_dst = (double*)W.dst();
+    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(double)));
+    if (!units.empty()) K2R_HIP(upload(d_units, units));
+    if (!folds.empty()) K2R_HIP(upload(d_folds, folds));
+    if (!items.empty()) K2R_HIP(upload(d_items, items));
+    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
+    if (ops & ROP_MEAN) K2R_HIP(upload(d_means, means));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    for (const SegRange& g : ranges) {
+        int rc = launch_reduce_fold(d_folds.as<FoldPiece>() + g.const0, (uint32_t)(g.const1 - g.const0), nullptr, r->d_vals.as<int64_t>(), d_dst,
+                                    d_scr.as<double>(), ops);
+        if (rc != DCDF_OK) return rc;
+        rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                d_dst, d_scr.as<double>(), ops);
+        if (rc != DCDF_OK) return rc;
+        for (size_t s = g.slab0; s < g.slab1; s++) {
+            const Slab& b = slabs[s];
+            rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), d_slab.p, DCDF_I64, nullptr,
+                                         nullptr, r->all_node, r->all_narrow);
+            if (rc != DCDF_OK) return rc;
+            rc = launch_reduce_fold(d_folds.as<FoldPiece>() + b.fold0, (uint32_t)(b.fold1 - b.fold0), d_slab.as<int64_t>(), nullptr, d_dst,
+                                    d_scr.as<double>(), ops);
+            if (rc != DCDF_OK) return rc;
+        }
+    }
+    if (ops & ROP_MEAN) {
+        uint64_t big = 0;
+        for (const MeanPiece& m : means) big = std::max(big, m.psz);
+        hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)),
+                           dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)means.size(), d_dst, d_scr.as<double>(), ops);
+        K2R_HIP(hipGetLastError());
+    }
+    K2R_HIP(hipEventRecord(ev.e1, 0));
+    K2R_HIP(hipDeviceSynchronize());
     const int rcf = W.finish();
     if (rcf != DCDF_OK) return rcf;
     float ms = 0.f;

@@ -378,6 +378,23 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return np.zeros((0, R, Cc), dtype=self.dtype)
         return self.raster().decode(start, stop, dtype=self.dtype)
 
+    def reduce_time(self, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """Per-cell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
+        [rows, cols] float64} for the names of `ops` ("min", "max", "sum", "count", "mean", or a DCDF_REDUCE_* bitmask), over the
+        values window() returns widened to float64, NaN cells skipped; the sum is sequential in instant order.  Through
+        raster().reduce_time: the encoded bytes are read once on the GPU and only the planes are written
+        (dcdf_raster_reduce_time_batch)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        bottom = R if bottom is None else bottom
+        right = Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            from .raster import EncodedRaster
+            names = EncodedRaster.reduce_ops(ops)[1]
+            return {n: np.full((bottom - top, right - left), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+        return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
+
     def search(self, start, stop, top, bottom, left, right, lower, upper):
         """(instant, row, col) of the cells with lower <= stored value <= upper (mmarray.rs:206; span.rs:231-270): not in
         py-dcdf, which never exposed search.  Integers only (stored values)."""

@@ -147,6 +147,69 @@ class EncodedRaster:
         out, _, _, _ = self.decode_flat([[start, stop, 0, R, 0, Cc]], dtype)
         return out[:(stop - start) * R * Cc].reshape(stop - start, R, Cc)
 
+    @staticmethod
+    def reduce_ops(ops):
+        """ops of reduce_time / reduce_time_flat as (bitmask, names in plane order): a DCDF_REDUCE_* bitmask, one name or an
+        iterable of "min" / "max" / "sum" / "count" / "mean"."""
+        if isinstance(ops, (int, np.integer)):
+            mask = int(ops)
+        else:
+            mask = 0
+            for name in ([ops] if isinstance(ops, str) else ops):
+                if name not in L.REDUCE_OPS:
+                    raise ValueError("reduce_time: unknown statistic %r (one of %s)" % (name, ", ".join(L.REDUCE_OPS)))
+                mask |= L.REDUCE_OPS[name]
+        if not 0 < mask < 32:
+            raise ValueError("reduce_time: ops %r is not a set of min, max, sum, count, mean" % (ops,))
+        return mask, [n for n, b in L.REDUCE_OPS.items() if mask & b]
+
+    def reduce_time_flat(self, cubes, ops, out_device_ptr=None, out_offset=None):
+        """Per-cell statistics over time of dataset-level cubes [n, 6] through dcdf_raster_reduce_time_batch: cube q yields one
+        [rows, cols] float64 plane per statistic of `ops` (reduce_ops), in the order min, max, sum, count, mean, over the values
+        decode_flat returns for it in the leaves' own dtype; the sum is sequential in instant order.  Host form: returns (flat
+        float64 array, offsets uint64[n], kernel ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device
+        form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk
+        kernel, by the fallback walk, from elided leaves."""
+        mask, names = self.reduce_ops(ops)
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        ms = C.c_float()
+        stats = np.zeros(3, dtype=np.uint64)
+        if out_device_ptr is None:
+            empty = (q[:, 1] == q[:, 0])
+            vol = np.abs((q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64) * np.uint64(len(names))
+            vol[empty] = 0  # (a cube without instants writes nothing)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = np.empty(max(1, int(vol.sum())), dtype=np.float64)
+            L.check(L.lib().dcdf_raster_reduce_time_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)), C.c_uint32(mask),
+                                                          C.c_void_p(out.ctypes.data), L.MEM_HOST, C.c_void_p(off.ctypes.data),
+                                                          C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_time_batch")
+            return out, off, ms.value, stats
+        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_reduce_time_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)), C.c_uint32(mask),
+                                                      C.c_void_p(out_device_ptr), L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
+                                                      C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_time_batch")
+        return ms.value, stats
+
+    def reduce_time(self, ops, start=0, stop=None, window=None):
+        """{statistic: ndarray [rows, cols] float64} over the instants [start, stop) of the whole raster, or of `window` =
+        (top, bottom, left, right).  Without instants: NaN planes, count 0 and sum 0."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
+        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
+            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        mask, names = self.reduce_ops(ops)
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            return {n: np.full((rows, cols), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+        out, _, _, _ = self.reduce_time_flat([[start, stop, top, bottom, left, right]], mask)
+        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+
     def search_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
         """search of dataset-level cubes through dcdf_raster_search_batch: returns (triples uint32[hits, 3] in raster coordinates
         -- or None when they stay on the device --, offsets, counts, kernel ms)."""

@@ -23,4 +23,9 @@ whole = R.decode(dtype=np.int32)
 assert whole.shape == a.shape and (whole == a).all()
 flat, offsets, _, stats = R.decode_flat([(0, 32, 0, 256, 0, 256)], dtype=np.int32)
 assert (flat.reshape(a.shape) == a).all() and int(stats[0]) == a.size
+maps = R.reduce_time(("mean", "max", "count"), 8, 24)
+assert list(maps) == ["max", "count", "mean"] and (maps["max"] == a[8:24].max(0)).all() and (maps["count"] == 16).all()
+assert (maps["mean"] == a[8:24].sum(0) / 16.0).all()
+flat, offsets, _, stats = R.reduce_time_flat([(0, 32, 10, 200, 0, 256)], ("min", "sum"))
+assert (flat.reshape(2, 190, 256) == np.stack([a[:, 10:200].min(0), a[:, 10:200].sum(0)])).all()
 print("readme example ok")

@@ -255,6 +255,21 @@ int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cube* cubes, 
  * stats (may be NULL): cells written by {bulk kernel, fallback walk, elided fill}. */
 int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype,
                              int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Reduce over time: per cell (row, col) of each cube, statistics over its instants of the values dcdf_raster_decode_batch returns
+ * when out_dtype is the encoding of the leaf that holds the cell, widened to double: x[t] = (double)n for DCDF_I32 / I64 leaves,
+ * (double)from_fixed in float for DCDF_F32 leaves, from_fixed in double for DCDF_F64 leaves, NaN for a stored 0 of a float leaf.
+ *   DCDF_REDUCE_MIN / MAX   fmin / fmax over the non-NaN x[t]; NaN when there is none
+ *   DCDF_REDUCE_SUM         s = 0.0; for t ascending: if x[t] is not NaN: s = s + x[t] -- sequential, in instant order, one IEEE
+ *                           double addition per instant, so the result does not depend on how the work is cut
+ *   DCDF_REDUCE_COUNT       the number of non-NaN x[t]
+ *   DCDF_REDUCE_MEAN        SUM / COUNT (one IEEE division); NaN when COUNT is 0
+ * Cube q writes popcount(ops) planes in ascending bit order, each dense [rows][cols] float64, from out + out_offset[q]
+ * (elements), host or device memory; a cube of zero volume writes nothing.  stats (may be NULL): cells READ by {bulk kernel,
+ * fallback walk, elided leaves}, the numbers dcdf_raster_decode_batch reports for the same cubes.  ops == 0 or a bit above 16:
+ * DCDF_ERR_BAD_ARG; k * k > 64 chunks: DCDF_ERR_UNSUPPORTED. */
+enum { DCDF_REDUCE_MIN = 1, DCDF_REDUCE_MAX = 2, DCDF_REDUCE_SUM = 4, DCDF_REDUCE_COUNT = 8, DCDF_REDUCE_MEAN = 16 };
+int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
+                                  const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
 /* search of nq dataset-level cubes: (instant, row, col) triples in RASTER coordinates (span.rs:231-270 adds the segment offset,
  * superchunk.rs:516-585 the tile origin); query q's triples are out[3 * offsets[q] .. + 3 * counts[q]), ordered by piece
  * (segment, tile row, tile col), sorted inside a piece. */
