@@ -62,7 +62,7 @@ SYMBOLS = [
     "dcdf_synth_fill", "dcdf_calib_read", "dcdf_device_alloc", "dcdf_device_free", "dcdf_device_copy", "dcdf_strerror", "dcdf_device_name", "dcdf_abi_version", "dcdf_last_hip_error", "dcdf_device_pool_trim",
     "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
-    "dcdf_raster_reduce_time_batch",
+    "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -95,8 +95,27 @@ def lib():
         L.dcdf_chunk_search_values.restype = C.c_int
         L.dcdf_chunk_search_values.argtypes = [C.c_void_p, C.POINTER(Cube), C.c_double, C.c_double, C.c_void_p, C.c_size_t,
                                                C.POINTER(C.c_size_t)]
+        L.dcdf_raster_reduce_space_batch.restype = C.c_int
+        L.dcdf_raster_reduce_space_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_space_fold_records.restype = C.c_int
+        L.dcdf_space_fold_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
         _lib = L
     return _lib
+
+
+def space_fold_records(records):
+    """dcdf_space_fold_records (host only, no GPU): records = [(integer, shift, negative)], integer within 128 signed bits.  Returns
+    sum((-1)^negative * integer * 2^shift) / 2^63 as the nearest double, ties to even."""
+    import numpy as np
+    n = len(records)
+    hi = np.array([((int(v) >> 64) & (2 ** 64 - 1)) for v, _, _ in records], dtype=np.uint64)
+    lo = np.array([(int(v) & (2 ** 64 - 1)) for v, _, _ in records], dtype=np.uint64)
+    sc = np.array([int(s) | (256 if g else 0) for _, s, g in records], dtype=np.uint32)
+    out = C.c_double()
+    check(lib().dcdf_space_fold_records(hi.ctypes.data if n else None, lo.ctypes.data if n else None, sc.ctypes.data if n else None, n,
+                                        C.byref(out)), "space_fold_records")
+    return out.value
 
 
 def value_bounds(encoding, fractional_bits, lower, upper):

@@ -19,6 +19,7 @@
 #include "k2r_bulk.h"
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
+#include "k2r_space.h"
 
 namespace k2r {
 
@@ -550,6 +551,224 @@ int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const Reduc
         default: return DCDF_ERR_BAD_ARG;
     }
 #undef K2R_REDUCE_CASE
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- reduction over space (k2r_space.h): the decode kernel with its stores replaced by one record per instant ----------------
+// One instant of one selected cell into the thread's four values.  kind as in k_bulk_reduce (uniform over a unit).  m is the
+// integer the decoder divides (space_m): n itself, (float)(n - 1) -- which rounds beyond 2^24 -- or n - 1; |m| <= 2^30 here, so a
+// unit's 4096 cells stay below 2^43 in an int64.  lo / hi hold the extremes as stored integers, mirrored by sg (reduce_fold4's
+// monotonicity argument).
+template <uint32_t LIVE>
+__device__ __forceinline__ void space_fold1(int32_t n, bool sel, int kind, int64_t& s, uint32_t& cnt, int32_t& lo, int32_t& hi, int32_t sg) {
+    const bool ok = sel && (kind == 0 || n != 0);
+    if constexpr ((LIVE & RA_SUM) != 0) {
+        const int32_t d = n - (kind != 0 ? 1 : 0);
+        const int32_t m = kind == 1 ? (int32_t)(float)d : d;
+        s += ok ? (int64_t)m : (int64_t)0;
+    }
+    if constexpr ((LIVE & RA_COUNT) != 0) cnt += ok ? 1u : 0u;
+    const int32_t key = (n ^ sg) - sg;
+    if constexpr ((LIVE & RA_MIN) != 0) lo = ok && key < lo ? key : lo;
+    if constexpr ((LIVE & RA_MAX) != 0) hi = ok && key > hi ? key : hi;
+}
+
+constexpr uint32_t SPACE_B = 16;  // instants whose wave results wait in LDS before one barrier flushes them
+
+// LIVE: the values this instantiation carries (RA_*; MIN and MAX go together, SUM and COUNT go together).  MASKED: the cube has
+// a mask.  A thread owns the 16 cells k_bulk_decode stores per instant; which of them count -- inside the unit's rectangle, and
+// their mask byte non-zero -- is one 16-bit word per unit (bit (2 k + i) * 4 + e), never looked up per instant.  Per instant the
+// thread folds its cells, the wave folds its lanes (__shfl_xor), and lane 0 leaves the wave's result in the instant's LDS slot;
+// every SPACE_B instants one barrier lets SPACE_B threads fold the four waves and write the records.
+// (waves_per_eu: the allocator stays within 128 VGPRs -- k_bulk_decode's four waves per SIMD -- instead of 133-135; no scratch.)
+template <uint32_t LIVE, bool MASKED>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_bulk_space(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const SpaceUnit* __restrict__ units, uint32_t n_units,
+             const uint8_t* __restrict__ mask, SpacePartial* __restrict__ recs) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    __shared__ int64_t w_sum[SPACE_B][4];
+    __shared__ uint32_t w_cnt[SPACE_B][4];
+    __shared__ int32_t w_lo[SPACE_B][4], w_hi[SPACE_B][4];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const SpaceUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int32_t enc = (int32_t)encs[U.chunk];
+        const int kind = enc == ENC_F32 ? 1 : enc == ENC_F64 ? 2 : 0;
+        const int32_t sg = kind != 0 && C.fbits == 62u ? -1 : 0;  // (from_fixed's divisor is negative)
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
+        const bool sq_in = r16 + qi < G && c16 + qj < G;
+        // the thread's selected cells
+        uint32_t sel = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 16u; b++) {
+            const uint32_t g = tid + 256u * (b >> 3), r = (uint32_t)U.rr + 2u * (g >> 4) + ((b >> 2) & 1u), c = (uint32_t)U.rc + 4u * (g & 15u) + (b & 3u);
+            bool in = r >= top && r < bottom && c >= left && c < right;
+            if constexpr (MASKED) {
+                if (in) in = ((const __attribute__((address_space(1))) uint8_t*)mask)[U.m_off + (uint64_t)(r - top) * U.m_sr + (c - left)] != 0;
+            }
+            sel |= in ? 1u << b : 0u;
+        }
+        uint32_t cur_snap = 0xffffffffu;
+        for (uint32_t t = U.t0; t < U.t1; t++) {
+            const gdesc gD = (gdesc)C.descs + t;
+            const bool is_log = gD->is_log != 0;
+            const uint32_t snap = is_log ? gD->snap : t;
+            __syncthreads();  // (the previous instant's readers are done)
+            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
+                cur_snap = snap;
+                const TreeRef S = tree_ref((gdesc)C.descs + snap);
+                const DacDesc& Sfull = C.descs[snap].mx;
+                if (tid < 16u) {
+                    int32_t v = 0;
+                    uint32_t idx = WQ_NONE;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
+                        v = e.mt + e.ms;
+                        idx = e.bs;
+                    }
+                    pyr[BP_OFF[4] + tid] = v;
+                    nst[BN_OFF[4] + tid] = idx;
+                }
+                __syncthreads();
+                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+            }
+            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
+            const DacDesc& Lfull = C.descs[t].mx;
+            if (is_log) {
+                if (tid < 16u) {
+                    uint32_t st = BS_CONST;
+                    int32_t d = 0;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
+                        if (e.bt != WQ_NONE) {
+                            st = e.bt;
+                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
+                            st = BS_RES;
+                            d = e.mt;
+                        } else {
+                            d = e.mt + e.ms;
+                        }
+                    }
+                    nst[BN_OFF[4] + tid] = st;
+                    nd[BN_OFF[4] + tid] = d;
+                }
+                __syncthreads();
+                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+            }
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded where k_bulk_decode stores them ----
+            int64_t s = 0;
+            uint32_t cnt = 0;
+            int32_t lo = INT32_MAX, hi = INT32_MIN;  // (beyond every stored value of a narrow32 chunk: "no value yet")
+#pragma unroll
+            for (uint32_t k = 0; k < 2u; k++) {
+                const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                const uint32_t sel8 = (sel >> (8u * k)) & 255u;
+                if (sel8 == 0) continue;  // (none of the group's cells counts)
+                V v[2][4];
+#pragma unroll
+                for (uint32_t j = 0; j < 2u; j++) {
+                    const uint32_t n = rp * 32u + 2u * cg + j;
+                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
+                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
+                    if (!(st & BS_RES)) {
+                        V dt[4];
+                        dac4<V>(gb, L, Lfull, st, dt);
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
+                    } else {
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
+                    }
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < 2u; i++)
+#pragma unroll
+                    for (uint32_t c = 0; c < 4u; c++) {
+                        const bool on = ((sel8 >> (4u * i + c)) & 1u) != 0;
+                        space_fold1<LIVE>(v[i][c], on, kind, s, cnt, lo, hi, sg);
+                    }
+            }
+            // ---- the wave's lanes, then its slot ----
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                if constexpr ((LIVE & RA_SUM) != 0) s += __shfl_xor((long long)s, off);
+                if constexpr ((LIVE & RA_COUNT) != 0) cnt += __shfl_xor(cnt, off);
+                if constexpr ((LIVE & RA_MIN) != 0) lo = min(lo, __shfl_xor(lo, off));
+                if constexpr ((LIVE & RA_MAX) != 0) hi = max(hi, __shfl_xor(hi, off));
+            }
+            const uint32_t slot = (t - U.t0) % SPACE_B;
+            if ((tid & 63u) == 0) {
+                w_sum[slot][tid >> 6] = s;
+                w_cnt[slot][tid >> 6] = cnt;
+                w_lo[slot][tid >> 6] = lo;
+                w_hi[slot][tid >> 6] = hi;
+            }
+            if (slot == SPACE_B - 1u || t + 1u == U.t1) {  // the slots 0 .. slot hold the instants t - slot .. t
+                __syncthreads();
+                if (tid <= slot) {
+                    int64_t ts = 0;
+                    uint32_t tc = 0;
+                    int32_t tl = INT32_MAX, th = INT32_MIN;
+#pragma unroll
+                    for (uint32_t w = 0; w < 4u; w++) {
+                        ts += w_sum[tid][w];
+                        tc += w_cnt[tid][w];
+                        tl = min(tl, w_lo[tid][w]);
+                        th = max(th, w_hi[tid][w]);
+                    }
+                    __attribute__((address_space(1))) SpacePartial* const o =
+                        (__attribute__((address_space(1))) SpacePartial*)recs + (U.rec + (uint64_t)(t - U.t0 - slot + tid));
+                    o->hi = ts < 0 ? ~(uint64_t)0 : (uint64_t)0;
+                    o->lo = (uint64_t)ts;
+                    o->mn = tl == INT32_MAX ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((tl ^ sg) - sg));
+                    o->mx = th == INT32_MIN ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((th ^ sg) - sg));
+                    o->cnt = tc;
+                    o->scale = space_scale(enc, C.fbits);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+int launch_bulk_space(const ChunkRef* d_refs, const uint8_t* d_enc, const SpaceUnit* d_units, uint32_t n, const uint8_t* d_mask,
+                      SpacePartial* d_recs, uint32_t live) {
+    if (n == 0) return DCDF_OK;
+    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    constexpr uint32_t EXT = RA_MIN | RA_MAX, ADD = RA_SUM | RA_COUNT;
+    const uint32_t l = ((live & EXT) ? EXT : 0u) | ((live & ADD) ? ADD : 0u);
+#define K2R_SPACE_CASE(L)                                                                                                          \
+    case L:                                                                                                                        \
+        if (d_mask) hipLaunchKernelGGL((k_bulk_space<L, true>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_recs);       \
+        else hipLaunchKernelGGL((k_bulk_space<L, false>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_recs);             \
+        break;
+    switch (l) {
+        K2R_SPACE_CASE(EXT) K2R_SPACE_CASE(ADD) K2R_SPACE_CASE(EXT | ADD)
+        default: return DCDF_ERR_BAD_ARG;
+    }
+#undef K2R_SPACE_CASE
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

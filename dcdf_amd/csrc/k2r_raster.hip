@@ -9,6 +9,7 @@
 #include "k2r_decode.h"
 #include "k2r_query_host.h"
 #include "k2r_reduce.h"
+#include "k2r_space.h"
 
 using namespace k2r;
 
@@ -797,6 +798,433 @@ extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cu
         for (const MeanPiece& m : means) big = std::max(big, m.psz);
         hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)),
                            dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)means.size(), d_dst, d_scr.as<double>(), ops);
+        K2R_HIP(hipGetLastError());
+    }
+    K2R_HIP(hipEventRecord(ev.e1, 0));
+    K2R_HIP(hipDeviceSynchronize());
+    const int rcf = W.finish();
+    if (rcf != DCDF_OK) return rcf;
+    float ms = 0.f;
+    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (kernel_ms) *kernel_ms = ms;
+    return DCDF_OK;
+}
+// ---- reduce over space: per-instant min / max / sum / count / mean of the selected cells of a cube (k2r_space.h) ------------
+// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  Every piece -- a 64 x 64 unit of the bulk
+// kernel, a piece of the window walk, an elided piece -- leaves one SpacePartial per instant in a pooled scratch array; the
+// pieces of one (cube, segment) share their instants, so their records form one block [slot][instant] that k_space_finish folds
+// into the cube's series.  Instants are independent: one launch of each kind takes the work of all segments and cubes.
+//
+// 128-bit sums and the extremes of one wave's lanes into lane 0 .. and of a workgroup's four waves into thread 0 (LDS)
+struct SpaceAcc {
+    uint64_t hi, lo;
+    double mn, mx;
+    uint32_t cnt;
+};
+__device__ __forceinline__ void space_block_fold(SpaceAcc& a, SpaceAcc* sh) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t bh = (uint64_t)__shfl_xor((unsigned long long)a.hi, off), bl = (uint64_t)__shfl_xor((unsigned long long)a.lo, off);
+        space_add128(a.hi, a.lo, bh, bl);
+        a.cnt += __shfl_xor(a.cnt, off);
+        a.mn = fmin(a.mn, __shfl_xor(a.mn, off));
+        a.mx = fmax(a.mx, __shfl_xor(a.mx, off));
+    }
+    __syncthreads();  // (the previous round's reader is done)
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (uint32_t w = 1; w < 4u; w++) {
+            space_add128(a.hi, a.lo, sh[w].hi, sh[w].lo);
+            a.cnt += sh[w].cnt;
+            a.mn = fmin(a.mn, sh[w].mn);
+            a.mx = fmax(a.mx, sh[w].mx);
+        }
+}
+__device__ __forceinline__ void space_store(SpacePartial* recs, uint64_t at, const SpaceAcc& a, uint32_t scale) {
+    __attribute__((address_space(1))) SpacePartial* const o = (__attribute__((address_space(1))) SpacePartial*)recs + at;
+    o->hi = a.hi;
+    o->lo = a.lo;
+    o->mn = a.mn;
+    o->mx = a.mx;
+    o->cnt = a.cnt;
+    o->scale = scale;
+}
+// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding,
+// masked cells skipped.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per instant
+// writes value x count.
+__global__ void __launch_bounds__(256)
+k_space_fold(const SpaceFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+             const uint8_t* __restrict__ mask, SpacePartial* __restrict__ recs) {
+    __shared__ SpaceAcc sh[4];
+    __shared__ uint32_t sh_sel;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const SpaceFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        const uint32_t scale = space_scale(P.enc, P.fbits);
+        if (P.elided) {
+            if (blockIdx.y != 0) continue;
+            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+            if (mask) {
+                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) a.cnt += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
+            } else if (threadIdx.x == 0) {
+                a.cnt = (uint32_t)cells;
+            }
+            space_block_fold(a, sh);
+            if (threadIdx.x == 0) sh_sel = a.cnt;
+            __syncthreads();
+            const uint32_t selected = sh_sel;
+            for (uint32_t t = threadIdx.x; t < P.nt; t += blockDim.x) {
+                const int64_t v = vals[P.src + t];
+                const double x = reduce_widen(P.enc, P.fbits, v);
+                SpaceAcc o{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+                if (x == x && selected) {
+                    space_mul_m(o.hi, o.lo, space_m(P.enc, v), selected);
+                    o.cnt = selected;
+                    o.mn = o.mx = x;
+                }
+                space_store(recs, P.rec + t, o, scale);
+            }
+            continue;
+        }
+        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
+            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
+                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
+                const int64_t v = slab[P.src + (uint64_t)t * cells + e];
+                const double x = reduce_widen(P.enc, P.fbits, v);
+                if (x == x) {
+                    space_add_m(a.hi, a.lo, space_m(P.enc, v));
+                    a.cnt += 1u;
+                    a.mn = fmin(a.mn, x);
+                    a.mx = fmax(a.mx, x);
+                }
+            }
+            space_block_fold(a, sh);
+            if (threadIdx.x == 0) space_store(recs, P.rec + t, a, scale);
+        }
+    }
+}
+// A workgroup per (job, instant): the records of the pieces that cover the instant, their sums at the common 2^-63 scale added
+// in 192 bits, then the requested series -- SUM by one conversion of that integer, MEAN by one division.
+__global__ void __launch_bounds__(256)
+k_space_finish(const SpaceJob* __restrict__ jobs, uint32_t n, const SpacePartial* __restrict__ recs, double* dst, uint32_t ops) {
+    __shared__ U192 sh_s[4];
+    __shared__ uint64_t sh_c[4];
+    __shared__ double sh_mn[4], sh_mx[4];
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const SpaceJob J = jobs[j];
+        for (uint32_t t = blockIdx.y; t < J.nt; t += gridDim.y) {
+            U192 acc{0, 0, 0};
+            uint64_t cnt = 0;
+            double mn = __builtin_nan(""), mx = __builtin_nan("");
+            for (uint32_t s = threadIdx.x; s < J.n_slots; s += blockDim.x) {
+                const __attribute__((address_space(1))) SpacePartial* const R =
+                    (const __attribute__((address_space(1))) SpacePartial*)recs + (J.rec + (uint64_t)s * J.nt + t);
+                u192_add(acc, space_scaled(R->hi, R->lo, R->scale));
+                cnt += R->cnt;
+                mn = fmin(mn, R->mn);
+                mx = fmax(mx, R->mx);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                U192 b;
+                b.w0 = (uint64_t)__shfl_xor((unsigned long long)acc.w0, off);
+                b.w1 = (uint64_t)__shfl_xor((unsigned long long)acc.w1, off);
+                b.w2 = (uint64_t)__shfl_xor((unsigned long long)acc.w2, off);
+                u192_add(acc, b);
+                cnt += (uint64_t)__shfl_xor((unsigned long long)cnt, off);
+                mn = fmin(mn, __shfl_xor(mn, off));
+                mx = fmax(mx, __shfl_xor(mx, off));
+            }
+            __syncthreads();  // (the previous round's reader is done)
+            if ((threadIdx.x & 63u) == 0) {
+                sh_s[threadIdx.x >> 6] = acc;
+                sh_c[threadIdx.x >> 6] = cnt;
+                sh_mn[threadIdx.x >> 6] = mn;
+                sh_mx[threadIdx.x >> 6] = mx;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (uint32_t w = 1; w < 4u; w++) {
+                    u192_add(acc, sh_s[w]);
+                    cnt += sh_c[w];
+                    mn = fmin(mn, sh_mn[w]);
+                    mx = fmax(mx, sh_mx[w]);
+                }
+                const double sum = space_round(acc);
+                __attribute__((address_space(1))) double* o = (__attribute__((address_space(1))) double*)dst + (J.o_off + t);
+                if (ops & RA_MIN) { *o = mn == mn ? mn : __builtin_nan(""); o += J.o_stride; }
+                if (ops & RA_MAX) { *o = mx == mx ? mx : __builtin_nan(""); o += J.o_stride; }
+                if (ops & RA_SUM) { *o = sum; o += J.o_stride; }
+                if (ops & RA_COUNT) { *o = (double)cnt; o += J.o_stride; }
+                if (ops & ROP_MEAN) *o = cnt == 0 ? __builtin_nan("") : sum / (double)cnt;
+            }
+        }
+    }
+}
+// records of one batch of the plan (K2R_SPACE_RECORDS overrides: tests of the batch cut); 40 bytes each
+static uint64_t space_record_cap() {
+    const char* e = std::getenv("K2R_SPACE_RECORDS");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : (uint64_t)6 << 20;
+}
+extern "C" int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum) {
+    if ((n && (!hi || !lo || !scale)) || !sum) return DCDF_ERR_BAD_ARG;
+    U192 acc{0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+        if ((scale[i] & 255u) > 63u || scale[i] > (SPACE_NEG | 63u)) return DCDF_ERR_BAD_ARG;
+        u192_add(acc, space_scaled(hi[i], lo[i], scale[i]));
+    }
+    *sum = space_round(acc);
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint8_t* mask,
+                                              const uint64_t* mask_offset, int mask_mem, double* out, int out_mem, const uint64_t* out_offset,
+                                              uint64_t stats[3], float* kernel_ms) {
+    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || ops == 0 || ops > (RA_ALL | ROP_MEAN) ||
+        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) || (mask && !mask_offset) ||
+        (mask && mask_mem != DCDF_MEM_HOST && mask_mem != DCDF_MEM_DEVICE))
+        return DCDF_ERR_BAD_ARG;
+    if (!r->all_wave || r->bad_fbits) return DCDF_ERR_UNSUPPORTED;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (nq == 0) return DCDF_OK;
+    const uint32_t live = reduce_live(ops), n_out = popc32(ops);
+    // where the series go: cube q's are n_out "instants" of one row of [instants] to WindowOut; where its mask bytes are
+    std::vector<dcdf_cube> series(nq, dcdf_cube{});
+    std::vector<uint64_t> moff(nq, 0);
+    uint64_t mask_total = 0;
+    const bool stage_mask = mask && mask_mem == DCDF_MEM_HOST;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
+        if (c.end == c.start) continue;
+        series[q] = dcdf_cube{0, n_out, 0, 1, 0, c.end - c.start};
+        if (mask) {
+            moff[q] = stage_mask ? mask_total : mask_offset[q];
+            mask_total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+        }
+    }
+    WindowOut W(series.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    // the plan: batches of jobs whose records share the scratch, one after the other
+    struct Slab {
+        size_t item0, item1, fold0, fold1;
+    };
+    struct Batch {
+        size_t unit0, unit1, const0, const1, slab0, slab1, job0, job1;
+        uint32_t unit_nt, job_nt;  // the longest unit / job
+    };
+    std::vector<SpaceUnit> units;
+    std::vector<SpaceFold> cfolds, wfolds;
+    std::vector<WinItem> items;
+    std::vector<Slab> slabs;
+    std::vector<SpaceJob> jobs;
+    std::vector<Batch> batches;
+    const uint64_t rec_cap = space_record_cap(), slab_cap = reduce_slab_cells();
+    uint64_t rec_used = 0, rec_max = 0, slab_used = 0, slab_max = 0, fold_nt = 1;
+    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
+    Batch cur{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    Slab cur_slab{0, 0, 0, 0};
+    auto flush_slab = [&] {
+        cur_slab.item1 = items.size();
+        cur_slab.fold1 = wfolds.size();
+        if (cur_slab.fold1 > cur_slab.fold0) slabs.push_back(cur_slab);
+        slab_max = std::max(slab_max, slab_used);
+        cur_slab = Slab{items.size(), 0, wfolds.size(), 0};
+        slab_used = 0;
+    };
+    auto flush_batch = [&] {
+        flush_slab();
+        // few units: a unit's instants in several workgroups (bulk_parts); each part writes its own instants' records
+        const size_t nu = units.size() - cur.unit0;
+        if (bulk_parts(nu, cur.unit_nt, bulk_wanted_units()) > 1) {
+            std::vector<SpaceUnit> split;
+            for (size_t i = cur.unit0; i < units.size(); i++) {
+                const SpaceUnit& u = units[i];
+                const uint32_t nt = u.t1 - u.t0, np = bulk_parts(nu, nt, bulk_wanted_units());
+                for (uint32_t j = 0; j < np; j++) {
+                    SpaceUnit v = u;
+                    v.t0 = bulk_part(u.t0, nt, np, j);
+                    v.t1 = bulk_part(u.t0, nt, np, j + 1);
+                    v.rec = u.rec + (v.t0 - u.t0);
+                    if (v.t1 > v.t0) split.push_back(v);
+                }
+            }
+            units.resize(cur.unit0);
+            units.insert(units.end(), split.begin(), split.end());
+        }
+        cur.unit1 = units.size();
+        cur.const1 = cfolds.size();
+        cur.slab1 = slabs.size();
+        cur.job1 = jobs.size();
+        if (cur.job1 > cur.job0) batches.push_back(cur);
+        rec_max = std::max(rec_max, rec_used);
+        rec_used = 0;
+        cur = Batch{units.size(), 0, cfolds.size(), 0, slabs.size(), 0, jobs.size(), 0, 0, 0};
+    };
+    struct WalkPiece {  // a piece for the window walk: chunk, chunk-level cube, and its fold without slab offset and record
+        uint32_t chunk;
+        dcdf_cube k;
+        SpaceFold f;
+    };
+    std::vector<SpaceUnit> tu;
+    std::vector<SpaceFold> tc;
+    std::vector<WalkPiece> tw;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end == c.start) continue;
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        for (uint32_t seg = c.start / r->cs; seg <= (c.end - 1) / r->cs; seg++) {
+            const uint32_t s0 = seg * r->cs, ls = std::max(c.start, s0), le = std::min(c.end, s0 + r->cs);  // the cube's instants of this segment
+            tu.clear();
+            tc.clear();
+            tw.clear();
+            if (wr * wc)
+                raster_pieces(r, dcdf_cube{ls, le, c.top, c.bottom, c.left, c.right}, [&](uint32_t cid, const dcdf_cube& l, uint32_t, uint32_t r0, uint32_t c0) {
+                    const uint64_t m_off = moff[q] + (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
+                    const uint64_t cells = cube_cells(l);
+                    const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
+                    SpaceFold p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, f.enc, f.fbits, 1u, 0u,
+                                (uint64_t)cid * r->cs + l.start, 0, m_off};
+                    if (f.elided) {
+                        tc.push_back(p);
+                        n_const += cells;
+                        return;
+                    }
+                    const dcdf_chunk* h = r->chunks[cid];
+                    const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
+                    if (!(h->top_g && h->narrow32)) {
+                        p.enc = h->encoding;
+                        p.fbits = h->fbits;
+                        p.elided = 0;
+                        tw.push_back(WalkPiece{cid, k, p});
+                        n_walk += cells;
+                        return;
+                    }
+                    for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
+                        for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
+                            SpaceUnit u{};
+                            u.chunk = cid;
+                            u.t0 = k.start;
+                            u.t1 = k.end;
+                            u.rr = (uint16_t)rr;
+                            u.rc = (uint16_t)rc;
+                            u.top = (uint16_t)std::max(rr, k.top);
+                            u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
+                            u.left = (uint16_t)std::max(rc, k.left);
+                            u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
+                            u.m_sr = (uint32_t)wc;
+                            u.m_off = m_off + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
+                            tu.push_back(u);
+                        }
+                    n_bulk += cells;
+                });
+            // the segment's instants in jobs of at most rec_cap records (one job, but for a huge cube)
+            const uint64_t n_slots = tu.size() + tc.size() + tw.size();
+            const uint32_t nt = le - ls, step = n_slots ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, rec_cap / n_slots)) : nt;
+            for (uint32_t a = 0; a < nt; a += step) {
+                const uint32_t b = std::min(nt, a + step), jn = b - a;
+                if (rec_used && rec_used + n_slots * jn > rec_cap) flush_batch();
+                jobs.push_back(SpaceJob{rec_used, (uint32_t)n_slots, jn, W.base[q] + (ls + a - c.start), (uint64_t)(c.end - c.start)});
+                uint64_t rec = rec_used;
+                for (SpaceUnit u : tu) {
+                    u.t0 += a;
+                    u.t1 = u.t0 + jn;
+                    u.rec = rec;
+                    units.push_back(u);
+                    rec += jn;
+                }
+                if (!tu.empty()) cur.unit_nt = std::max(cur.unit_nt, jn);
+                for (SpaceFold p : tc) {
+                    p.src += a;
+                    p.nt = jn;
+                    p.rec = rec;
+                    cfolds.push_back(p);
+                    rec += jn;
+                }
+                for (const WalkPiece& w : tw) {  // into slabs: whole pieces up to the cell bound, a piece beyond it cut in time
+                    const uint64_t plane = (uint64_t)w.f.rows * w.f.cols;
+                    const uint32_t cut = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(jn, slab_cap / plane));
+                    if (cut < jn || slab_used + (uint64_t)jn * plane > slab_cap) flush_slab();
+                    for (uint32_t x = 0; x < jn; x += cut) {
+                        const uint32_t y = std::min(jn, x + cut);
+                        dcdf_cube k = w.k;
+                        k.start = w.k.start + a + x;
+                        k.end = w.k.start + a + y;
+                        SpaceFold p = w.f;
+                        p.nt = y - x;
+                        p.src = slab_used;
+                        p.rec = rec + x;
+                        window_items(w.chunk, k, slab_used, items, r->all_node);
+                        wfolds.push_back(p);
+                        fold_nt = std::max<uint64_t>(fold_nt, p.nt);
+                        slab_used += (uint64_t)(y - x) * plane;
+                        if (cut < jn) flush_slab();
+                    }
+                    rec += jn;
+                }
+                rec_used = rec;
+                cur.job_nt = std::max(cur.job_nt, jn);
+            }
+            if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || cfolds.size() + wfolds.size() > 0xfffffff0ull ||
+                jobs.size() > 0x7ffffff0ull)
+                return DCDF_ERR_CAPACITY;
+        }
+    }
+    flush_batch();
+    if (stats) {
+        stats[0] = n_bulk;
+        stats[1] = n_walk;
+        stats[2] = n_const;
+    }
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_wfolds, d_items, d_jobs, d_slab, d_recs, d_mask;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    double* const d_dst = (double*)W.dst();
+    const uint8_t* p_mask = mask;
+    if (stage_mask) {
+        K2R_HIP(d_mask.alloc_pooled(mask_total));
+        for (size_t q = 0; q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+            if (c.end == c.start || bytes == 0) continue;
+            K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], mask + mask_offset[q], bytes, hipMemcpyHostToDevice));
+        }
+        p_mask = (const uint8_t*)d_mask.p;
+    }
+    K2R_HIP(d_recs.alloc_pooled(rec_max * sizeof(SpacePartial)));
+    if (!units.empty()) K2R_HIP(upload(d_units, units));
+    if (!cfolds.empty()) K2R_HIP(upload(d_cfolds, cfolds));
+    if (!wfolds.empty()) K2R_HIP(upload(d_wfolds, wfolds));
+    if (!items.empty()) K2R_HIP(upload(d_items, items));
+    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
+    K2R_HIP(upload(d_jobs, jobs));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    SpacePartial* const recs = d_recs.as<SpacePartial>();
+    for (const Batch& b : batches) {
+        if (b.const1 > b.const0) {
+            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
+                               d_cfolds.as<SpaceFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), p_mask, recs);
+            K2R_HIP(hipGetLastError());
+        }
+        int rc = launch_bulk_space(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<SpaceUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0),
+                                   p_mask, recs, live);
+        if (rc != DCDF_OK) return rc;
+        for (size_t s = b.slab0; s < b.slab1; s++) {
+            const Slab& sl = slabs[s];
+            rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + sl.item0, (uint32_t)(sl.item1 - sl.item0), d_slab.p, DCDF_I64, nullptr,
+                                         nullptr, r->all_node, r->all_narrow);
+            if (rc != DCDF_OK) return rc;
+            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), (uint32_t)std::min<uint64_t>(fold_nt, 1024)),
+                               dim3(256), 0, 0, d_wfolds.as<SpaceFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), d_slab.as<int64_t>(), nullptr,
+                               p_mask, recs);
+            K2R_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_space_finish, dim3((uint32_t)std::min<size_t>(b.job1 - b.job0, 1u << 20), std::min<uint32_t>(b.job_nt, 1024)), dim3(256), 0,
+                           0, d_jobs.as<SpaceJob>() + b.job0, (uint32_t)(b.job1 - b.job0), recs, d_dst, ops);
         K2R_HIP(hipGetLastError());
     }
     K2R_HIP(hipEventRecord(ev.e1, 0));

@@ -395,6 +395,22 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return {n: np.full((bottom - top, right - left), 0.0 if n in ("sum", "count") else np.nan) for n in names}
         return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
 
+    def reduce_space(self, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
+        """Per-instant statistics over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
+        ([rows, cols] of the window, boolean or uint8) is non-zero when a mask is given: {name: ndarray [stop - start] float64} for
+        the names of `ops`, over the values window() returns widened to float64, NaN cells skipped; the sum is the exact sum
+        rounded once (math.fsum).  Through raster().reduce_space: the encoded bytes are read once on the GPU and only the series
+        are written (dcdf_raster_reduce_space_batch)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        bottom = R if bottom is None else bottom
+        right = Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            from .raster import EncodedRaster
+            return {n: np.empty(0, dtype=np.float64) for n in EncodedRaster.reduce_ops(ops)[1]}
+        return self.raster().reduce_space(ops, start, stop, window=(top, bottom, left, right), mask=mask)
+
     def search(self, start, stop, top, bottom, left, right, lower, upper):
         """(instant, row, col) of the cells with lower <= stored value <= upper (mmarray.rs:206; span.rs:231-270): not in
         py-dcdf, which never exposed search.  Integers only (stored values)."""

@@ -1,6 +1,6 @@
 # The README's example, with its claims as assertions (needs an MI355X: python examples/quickstart.py)
 
-import os, sys
+import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repo root: dcdf_amd is used in-tree
 import numpy as np, dcdf_amd as dc
 from dcdf_amd.raster import EncodedRaster
@@ -28,4 +28,9 @@ assert list(maps) == ["max", "count", "mean"] and (maps["max"] == a[8:24].max(0)
 assert (maps["mean"] == a[8:24].sum(0) / 16.0).all()
 flat, offsets, _, stats = R.reduce_time_flat([(0, 32, 10, 200, 0, 256)], ("min", "sum"))
 assert (flat.reshape(2, 190, 256) == np.stack([a[:, 10:200].min(0), a[:, 10:200].sum(0)])).all()
+series = R.reduce_space(("mean", "max", "count"), 8, 24, window=(10, 200, 0, 256))
+assert list(series) == ["max", "count", "mean"] and (series["max"] == a[8:24, 10:200].max((1, 2))).all() and (series["count"] == 190 * 256).all()
+disc = (np.mgrid[0:256, 0:256][0] - 128) ** 2 + (np.mgrid[0:256, 0:256][1] - 128) ** 2 < 100 ** 2
+flat, offsets, _, stats = R.reduce_space_flat([(0, 32, 0, 256, 0, 256)], ("sum", "mean"), masks=[disc])
+assert all(flat[t] == math.fsum(a[t][disc].tolist()) and flat[32 + t] == flat[t] / disc.sum() for t in range(32))
 print("readme example ok")

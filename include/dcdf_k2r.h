@@ -270,6 +270,31 @@ int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_
 enum { DCDF_REDUCE_MIN = 1, DCDF_REDUCE_MAX = 2, DCDF_REDUCE_SUM = 4, DCDF_REDUCE_COUNT = 8, DCDF_REDUCE_MEAN = 16 };
 int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
                                   const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Reduce over space: per instant of each cube, statistics over its SELECTED cells -- a series over an area.  The call takes
+ * plain and tiled rasters.  Cube q is [start, end) x [top, bottom) x [left, right) (reversed bounds are swapped); its cell (r, c)
+ * is selected when mask == NULL, or when the byte mask[mask_offset[q] + (r - top) * cols + (c - left)] is non-zero: a dense
+ * row-major [rows][cols] mask of one byte per cell, host or device memory (mask_mem).  mask_offset == NULL only with mask == NULL.
+ * x[r, c] of instant t is reduce_time's x[t]: the stored integer widened with the encoding and fractional bits of the leaf that
+ * holds the cell ((double)n, from_fixed in float or in double, NaN for a stored 0 of a float leaf).  Over the selected cells:
+ *   DCDF_REDUCE_MIN / MAX   fmin / fmax over the non-NaN x; NaN when there is none
+ *   DCDF_REDUCE_COUNT       the number of non-NaN x
+ *   DCDF_REDUCE_SUM         the EXACT real sum of the non-NaN x, rounded once to the nearest double, ties to even (what Python's
+ *                           math.fsum returns); +0.0 when there is none.  It depends on no order and on no cut of the work:
+ *                           every x is an integer multiple of 2^-63, and the sum is formed in integers.
+ *   DCDF_REDUCE_MEAN        SUM / COUNT (one IEEE division); NaN when COUNT is 0
+ * Cube q writes popcount(ops) series in ascending bit order, each dense [instants] float64, from out + out_offset[q] (elements),
+ * host or device memory.  A cube without instants writes nothing; one with instants but no rows or columns, or with an all-zero
+ * mask, writes the "none" values for every instant.  stats (may be NULL): cells read by {bulk kernel, fallback walk, elided
+ * leaves}, the numbers dcdf_raster_decode_batch reports for the same cubes; the mask does not change them.  ops == 0 or a bit
+ * above 16: DCDF_ERR_BAD_ARG; a cube outside the raster: DCDF_ERR_BOUNDS; k * k > 64 chunks: DCDF_ERR_UNSUPPORTED. */
+int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint8_t* mask,
+                                   const uint64_t* mask_offset, int mask_mem, double* out, int out_mem, const uint64_t* out_offset,
+                                   uint64_t stats[3], float* kernel_ms);
+/* The arithmetic DCDF_REDUCE_SUM of dcdf_raster_reduce_space_batch rests on, as the device runs it: n two's complement 128-bit
+ * integers (hi[i], lo[i]), each shifted left by scale[i] & 255 (at most 63) and negated when scale[i] & 256, are added in 192
+ * bits; *sum = that integer / 2^63 as the nearest double, ties to even.  Pure host function; no GPU, no HIP call (so it is
+ * testable on a CPU-only machine).  DCDF_ERR_BAD_ARG: a NULL pointer, a scale beyond those bits. */
+int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum);
 /* search of nq dataset-level cubes: (instant, row, col) triples in RASTER coordinates (span.rs:231-270 adds the segment offset,
  * superchunk.rs:516-585 the tile origin); query q's triples are out[3 * offsets[q] .. + 3 * counts[q]), ordered by piece
  * (segment, tile row, tile col), sorted inside a piece. */
