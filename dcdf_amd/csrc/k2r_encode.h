@@ -1004,12 +1004,19 @@ K2R_HD void emit4(EX& ex, const DacSink& d, uint32_t pos, uint32_t z0, uint32_t 
             const uint32_t run = (z0 > 0xffu ? 8u : 0u) | (z1 > 0xffu ? 4u : 0u) | (z2 > 0xffu ? 2u : 0u) | (z3 > 0xffu ? 1u : 0u);
             bm_or_run(ex, bm0, pos, 4, run);
             if (MODE == EM_ONE) {
-                const uint32_t z[4] = {z0, z1, z2, z3};
+                // the second bytes sit at lpos, lpos + 1, ...; a record's values are long all four together or not at all in
+                // 98 % of the records of a Log: those take one unaligned 4-byte store
+                if (run == 15u) {
+                    gstore32u(d.plane1 + guard_pos(ex, lpos, 4, d.n1, d.code + 1),
+                              ((z0 >> 8) & 0xffu) | (((z1 >> 8) & 0xffu) << 8) | (((z2 >> 8) & 0xffu) << 16) | ((z3 >> 8) << 24));
+                } else {
+                    const uint32_t z[4] = {z0, z1, z2, z3};
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if (z[i] > 0xffu) {
-                        gstore8(d.plane1 + guard_pos(ex, lpos, 1, d.n1, d.code + 1), (uint8_t)(z[i] >> 8));
-                        lpos++;
+                    for (int i = 0; i < 4; i++) {
+                        if (z[i] > 0xffu) {
+                            gstore8(d.plane1 + guard_pos(ex, lpos, 1, d.n1, d.code + 1), (uint8_t)(z[i] >> 8));
+                            lpos++;
+                        }
                     }
                 }
             }
@@ -2415,6 +2422,8 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
 
         // 5b. plane 0 of both Dacs, T (and eqB) bits.  Pass A covers the nodes of heights >= 2; it is instantiated
         // per emission mode.
+        const bool snap_dyn = as_snapshot;
+        const Totals<C>& TT_dyn = TT;
         auto passA = [&](auto mode_tag) {  // (no barrier at its end: the caller decides)
           constexpr int MODE = decltype(mode_tag)::value;
           ex.par_nosync([&](int tid, EncRegs& r) {
@@ -2422,6 +2431,9 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             blk_origin(tid, r0, c0);
             const uint64_t pLo = r.pf_lo;
 
+            // (a stash Log is never a Snapshot: the EM_P0 instantiation drops the Snapshot arms and their registers)
+            const bool as_snapshot = MODE == EM_P0 ? false : snap_dyn;
+            const Totals<C>& TT = MODE == EM_P0 ? sh.pl.T[1] : TT_dyn;
             // -- this thread's own height-3 node and, for the first NTOPX threads, one top node each --
             const uint32_t* const tb = as_snapshot ? sh.tbS : sh.tbL;
             if (MODE == EM_P0) r.pa[2] = 0;
@@ -2460,13 +2472,54 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
                     if (e) bm_set(ex, sh.bmE, guard_pos(ex, TT.offZ[h] + vrank - irank, 1, TT.LT - TT.M0, kGuardEOwn));
                 }
             };
+            // The same node of a stash Log (EM_P0) as straight-line code.  enode above is a chain of dependent LDS reads behind
+            // divergent branches (flag -> branch -> predicate -> ranks -> offsets -> values -> store), one round trip after
+            // the other; here every operand is read up front from an address that is valid in every lane (the root has no
+            // parent and a height-3 node no flag of its own: they read word 0 and ignore it), positions and predicates are
+            // computed on values, and only the stores and atomics are predicated.
+            auto enode_log = [&](int h, uint32_t j, const int slot) {
+                const bool root = h == H;
+                const int a = C::top_off(h) + (int)j;
+                const uint32_t bp = root ? (h == 3 ? 0u : tbit(h, 0)) : tbit(h + 1, j >> 2);  // the parent's flag
+                const uint32_t bo = h == 3 ? 0u : tbit(h, j);                                 // the node's own flag
+                const uint32_t wp = tb[bp >> 5], pp = sh.tbP[bp >> 5], wo = tb[bo >> 5], po = sh.tbP[bo >> 5];
+                const uint32_t rp = sh.ttR[root ? H : h + 1], ro = h == 3 ? 0u : sh.ttR[h];
+                const uint32_t oV = TT.offV[h], oI = TT.offI[h], oZ = TT.offZ[h];
+                const int32_t tmx = sh.tmax[a], tmn = sh.tmin[a], smx = sh.smax[a], smn = sh.smin[a];
+                const uint32_t eqa = h == 3 ? sh.eq[a] : 0u;
+                auto before = [](uint32_t pref, uint32_t w, uint32_t b) { return pref + popc32(w & ((1u << (b & 31u)) - 1u)); };
+                const bool ninv = !top_inval(h, j);
+                const bool vis = root || ((wp >> (bp & 31u)) & 1u) != 0;
+                const bool ne = ninv && tmn != tmx;  // not uniform
+                const bool p = h == 3 ? (ne && eqa == 0) : ((wo >> (bo & 31u)) & 1u) != 0;  // PL(h, j)
+                // level-order index: four children per internal parent, parents ranked among the internal nodes
+                const uint32_t vrank = root ? 0u : 4 * (before(pp, wp, bp) - rp) + (j & 3);
+                const uint32_t idx = oV + vrank;
+                const uint32_t irank = h == 3 ? unpackI(3, pLo, 0) : before(po, wo, bo) - ro;
+                const uint32_t im = oI + irank;
+                const uint32_t zv = zz32(ninv ? tmx - smx : 0), zm = zz32(tmn - smn);  // log.rs:133,148
+                r.pa[3 * slot] = idx;
+                r.pa[3 * slot + 1] = im;
+                r.pa[2] |= ((vis ? zv >> 8 : 0u) << (16 * slot)) | ((vis && p ? zm >> 8 : 0u) << (16 * slot + 8));
+                if (vis) {
+                    emit_val<0, EM_P0>(ex, sinkV, idx, zv, tid);
+                    if (p) {
+                        bm_set(ex, sh.bmT, guard_pos(ex, idx, 1, TT.LT, kGuardTOwn));
+                        emit_val<1, EM_P0>(ex, sinkM, im, zm, tid);
+                    } else if (ne) {  // not uniform => equal
+                        bm_set(ex, sh.bmE, guard_pos(ex, oZ + vrank - irank, 1, TT.LT - TT.M0, kGuardEOwn));
+                    }
+                }
+            };
             const uint32_t wt = opaque((uint32_t)tid);
-            enode(3, wt, 0);
+            if (MODE == EM_P0) enode_log(3, wt, 0);
+            else enode(3, wt, 0);
             if (wt < (uint32_t)C::NTOPX) {
                 int h;
                 uint32_t j;
                 top_decode(wt, h, j);
-                enode(h, j, 1);
+                if (MODE == EM_P0) enode_log(h, j, 1);
+                else enode(h, j, 1);
             }
 
             // -- the four height-2 children of this thread's block + the work list of internal height-2 nodes --
