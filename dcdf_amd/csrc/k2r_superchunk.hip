@@ -16,8 +16,8 @@
 //   * the instant-major min / max Dacs (superchunk.rs:190-198,246-247): `k_dac_pack` (k2r_generic.hip);
 //   * SHA-256 of every stored object: on the host (x86 SHA extensions, k2r_sha256_host.h) by the download's worker threads as each
 //     object lands in host memory -- a hash is one serial chain per object, 139 ms on one GPU lane for the 1.4 MB sub-chunks of a
-//     4096^2 level against 15 ms overlapped with the copy; the device kernels (`k_object_sha256`, `k_sha256_buffers`, k2r_cid.hip)
-//     remain for objects that stay in HBM (dcdf_encoder_object_sha256).
+//     4096^2 level against 15 ms overlapped with the copy; the device kernel (`k_object_sha256`, k2r_cid.hip) hashes the
+//     chunk objects that stay in HBM (dcdf_encoder_object_sha256).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -42,7 +42,6 @@
 
 namespace k2r {
 hipError_t launch_dac_pack(const int64_t* values, uint64_t n, uint8_t* out, uint8_t* tmp, uint64_t* out_len, hipStream_t stream);
-hipError_t launch_sha256_buffers(const uint8_t* data, const uint64_t* offs, const uint64_t* lens, uint32_t n, uint8_t* digests, hipStream_t stream);
 
 struct MinMaxTile {  // one tile of the superchunk's grid (device view)
     const void* base;
