@@ -63,9 +63,11 @@ SYMBOLS = [
     "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
     "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
+    "dcdf_raster_histogram_batch", "dcdf_histogram_bounds",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
+HIST_MAX_BINS = 256  # DCDF_HIST_MAX_BINS
 
 
 def lib():
@@ -100,6 +102,11 @@ def lib():
                                                      C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.dcdf_space_fold_records.restype = C.c_int
         L.dcdf_space_fold_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
+        L.dcdf_raster_histogram_batch.restype = C.c_int
+        L.dcdf_raster_histogram_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_histogram_bounds.restype = C.c_int
+        L.dcdf_histogram_bounds.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -116,6 +123,19 @@ def space_fold_records(records):
     check(lib().dcdf_space_fold_records(hi.ctypes.data if n else None, lo.ctypes.data if n else None, sc.ctypes.data if n else None, n,
                                         C.byref(out)), "space_fold_records")
     return out.value
+
+
+def histogram_bounds(encoding, fractional_bits, edges):
+    """dcdf_histogram_bounds (host only, no GPU): (lo, hi) int64[bins] -- the inclusive interval of stored integers of a chunk of
+    this encoding and these fractional bits that every bin of `edges` (bins + 1 increasing values) takes; lo[b] > hi[b] when
+    bin b takes none.  Stored 0 of a float encoding belongs to no bin."""
+    import numpy as np
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).ravel())
+    bins = max(int(e.size) - 1, 0)
+    lo, hi = np.zeros(max(bins, 1), dtype=np.int64), np.zeros(max(bins, 1), dtype=np.int64)
+    check(lib().dcdf_histogram_bounds(int(encoding), int(fractional_bits), e.ctypes.data, bins, lo.ctypes.data, hi.ctypes.data),
+          "histogram_bounds")
+    return lo[:bins], hi[:bins]
 
 
 def value_bounds(encoding, fractional_bits, lower, upper):

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "k2r_bulk.h"
+#include "k2r_hist.h"
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
 #include "k2r_space.h"
@@ -769,6 +770,230 @@ int launch_bulk_space(const ChunkRef* d_refs, const uint8_t* d_enc, const SpaceU
         default: return DCDF_ERR_BAD_ARG;
     }
 #undef K2R_SPACE_CASE
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- value histograms (k2r_hist.h): the decode kernel with its stores replaced by counts per instant and bin ------------------
+// K2R_HIST_VARIANT (diagnostic builds for DESIGN.md section 4h only, tools/build_variant.sh; their counts are wrong on purpose):
+// 1 = the binning compiled out (no threshold search: every cell goes to the first bin), 2 = the LDS and global adds compiled out
+// (the bins are searched and folded into a register), 3 = the 16 searches of a thread one after the other instead of 8 in step.
+#ifndef K2R_HIST_VARIANT
+#define K2R_HIST_VARIANT 0
+#endif
+constexpr uint32_t HIST_SLOTS = 16;     // instants whose counts wait in LDS before one barrier flushes them, at most
+constexpr uint32_t HIST_COUNTS = 1024;  // LDS counters: min(HIST_SLOTS, HIST_COUNTS / n_bins) instants of n_bins (4 at 256 bins)
+constexpr uint32_t HIST_THR = 512;      // entries of the largest threshold table (hist_steps(256) = 9)
+
+// MASKED: the cube has a mask.  A thread owns the 16 cells k_bulk_decode stores per instant and k_bulk_space's 16-bit word of those
+// that count.  The unit's leaf has one table of int32 thresholds (hist_thresholds32, made by the planner once per distinct encoding
+// and fractional bits), copied to LDS before the first instant; a cell's bin is a branch-free binary search of `steps` LDS reads --
+// integer compares only, nothing is widened.  The searches of a group's 8 cells advance together, step by step: a search is a
+// chain of dependent LDS reads, and 8 independent chains hide each other's latency (0.5 ms of 5.8 at 16 bins on the benchmark
+// cube).  The NaN code of a float leaf and cells outside the edges are dropped.
+//
+// Smooth data puts most of a wave's cells into one bin.  A thread therefore adds a RUN of equal bins among its cells with one
+// LDS atomic; on a constant field that is one add per thread and instant.  (Combining the lanes' last runs across the wave
+// first -- ballot, the first pending lane's bin, a __shfl_xor sum, one add -- was built and measured: no faster on a constant
+// field, 3 % slower on real data)
+//
+// Every `slots` instants (or at the unit's end) one barrier lets the workgroup add the non-zero counters to the cube's rows --
+// device-scope 64-bit atomic adds, contiguous over (instant, bin) -- and clear them.
+// (waves_per_eu: k_bulk_space's reason; no scratch.)
+template <bool MASKED>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_bulk_hist(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const HistUnit* __restrict__ units, uint32_t n_units,
+            const uint8_t* __restrict__ mask, const int32_t* __restrict__ thr, uint32_t n_bins, uint32_t steps, uint64_t* out) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    __shared__ int32_t s_thr[HIST_THR];
+    __shared__ uint32_t s_cnt[HIST_COUNTS];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t fit = HIST_COUNTS / n_bins, slots = fit < HIST_SLOTS ? fit : HIST_SLOTS;
+    for (uint32_t i = tid; i < HIST_COUNTS; i += 256u) s_cnt[i] = 0u;  // (every flush leaves them cleared)
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const HistUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int32_t enc = (int32_t)encs[U.chunk];
+        const bool is_float = enc == ENC_F32 || enc == ENC_F64;
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
+        const bool sq_in = r16 + qi < G && c16 + qj < G;
+        // the leaf's thresholds (read after the first instant's barriers; the previous unit's readers are behind its last barrier)
+        for (uint32_t i = tid; i < ((uint32_t)1 << steps); i += 256u)
+            s_thr[i] = ((const __attribute__((address_space(1))) int32_t*)thr)[U.thr + i];
+        // the thread's selected cells
+        uint32_t sel = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 16u; b++) {
+            const uint32_t g = tid + 256u * (b >> 3), r = (uint32_t)U.rr + 2u * (g >> 4) + ((b >> 2) & 1u), c = (uint32_t)U.rc + 4u * (g & 15u) + (b & 3u);
+            bool in = r >= top && r < bottom && c >= left && c < right;
+            if constexpr (MASKED) {
+                if (in) in = ((const __attribute__((address_space(1))) uint8_t*)mask)[U.m_off + (uint64_t)(r - top) * U.m_sr + (c - left)] != 0;
+            }
+            sel |= in ? 1u << b : 0u;
+        }
+        uint32_t cur_snap = 0xffffffffu, slot = 0;
+        for (uint32_t t = U.t0; t < U.t1; t++) {
+            const gdesc gD = (gdesc)C.descs + t;
+            const bool is_log = gD->is_log != 0;
+            const uint32_t snap = is_log ? gD->snap : t;
+            __syncthreads();  // (the previous instant's readers are done, the flush's clears too)
+            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
+                cur_snap = snap;
+                const TreeRef S = tree_ref((gdesc)C.descs + snap);
+                const DacDesc& Sfull = C.descs[snap].mx;
+                if (tid < 16u) {
+                    int32_t v = 0;
+                    uint32_t idx = WQ_NONE;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
+                        v = e.mt + e.ms;
+                        idx = e.bs;
+                    }
+                    pyr[BP_OFF[4] + tid] = v;
+                    nst[BN_OFF[4] + tid] = idx;
+                }
+                __syncthreads();
+                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
+                __syncthreads();
+            }
+            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
+            const DacDesc& Lfull = C.descs[t].mx;
+            if (is_log) {
+                if (tid < 16u) {
+                    uint32_t st = BS_CONST;
+                    int32_t d = 0;
+                    if (sq_in) {
+                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
+                        if (e.bt != WQ_NONE) {
+                            st = e.bt;
+                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
+                            st = BS_RES;
+                            d = e.mt;
+                        } else {
+                            d = e.mt + e.ms;
+                        }
+                    }
+                    nst[BN_OFF[4] + tid] = st;
+                    nd[BN_OFF[4] + tid] = d;
+                }
+                __syncthreads();
+                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
+                __syncthreads();
+            }
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, binned where k_bulk_decode stores them ----
+            uint32_t* const row = s_cnt + slot * n_bins;
+            uint32_t run_bin = 0, run = 0;  // the thread's current run of equal bins
+#if K2R_HIST_VARIANT == 2
+            uint32_t sink = row[0];
+#define K2R_HIST_ADD(b, c) sink = sink * 31u + (b) + (c)
+#else
+#define K2R_HIST_ADD(b, c) atomicAdd(row + (b), (c))
+#endif
+#pragma unroll
+            for (uint32_t k = 0; k < 2u; k++) {
+                const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                const uint32_t sel8 = (sel >> (8u * k)) & 255u;
+                if (sel8 == 0) continue;  // (none of the group's cells counts)
+                V v[2][4];
+#pragma unroll
+                for (uint32_t j = 0; j < 2u; j++) {
+                    const uint32_t n = rp * 32u + 2u * cg + j;
+                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
+                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
+                    if (!(st & BS_RES)) {
+                        V dt[4];
+                        dac4<V>(gb, L, Lfull, st, dt);
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
+                    } else {
+#pragma unroll
+                        for (uint32_t c = 0; c < 4u; c++)
+                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
+                    }
+                }
+                uint32_t pos[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // hist_search32, the 8 searches in step
+#if K2R_HIST_VARIANT == 1
+#pragma unroll
+                for (uint32_t e = 0; e < 8u; e++) pos[e] = v[e >> 2][e & 3u] == INT32_MIN ? 0u : 1u;
+#elif K2R_HIST_VARIANT == 3
+#pragma unroll
+                for (uint32_t e = 0; e < 8u; e++) pos[e] = (uint32_t)(hist_search32(s_thr, steps, v[e >> 2][e & 3u]) + 1);
+#else
+                for (uint32_t s = (uint32_t)1 << (steps - 1u); s; s >>= 1) {
+#pragma unroll
+                    for (uint32_t e = 0; e < 8u; e++) pos[e] += s_thr[pos[e] + s - 1u] <= v[e >> 2][e & 3u] ? s : 0u;
+                }
+#endif
+#pragma unroll
+                for (uint32_t e = 0; e < 8u; e++) {
+                    const uint32_t p = pos[e] - 1u;  // (0 - 1 wraps beyond n_bins)
+                    const bool on = ((sel8 >> e) & 1u) != 0 && !(is_float && v[e >> 2][e & 3u] == 0) && p < n_bins;
+                    const uint32_t bin = U.rev ? n_bins - 1u - p : p;
+                    if (on) {
+                        if (run != 0 && bin != run_bin) {
+                            K2R_HIST_ADD(run_bin, run);
+                            run = 0;
+                        }
+                        run_bin = bin;
+                        run += 1u;
+                    }
+                }
+            }
+            if (run != 0) K2R_HIST_ADD(run_bin, run);  // the thread's last run
+#if K2R_HIST_VARIANT == 2
+            if (sink == 0xdeadbeefu && t + 1u == U.t1) out[U.o_off] = sink;  // (keeps the searches alive; never true in practice)
+            continue;
+#endif
+            // ---- the slots' counters into the cube's rows ----
+            if (slot + 1u == slots || t + 1u == U.t1) {  // the slots 0 .. slot hold the instants t - slot .. t
+                __syncthreads();
+                __attribute__((address_space(1))) unsigned long long* const o =
+                    (__attribute__((address_space(1))) unsigned long long*)out + (U.o_off + (uint64_t)(t - U.t0 - slot) * n_bins);
+                for (uint32_t i = tid; i < (slot + 1u) * n_bins; i += 256u) {
+                    const uint32_t c = s_cnt[i];
+                    if (c != 0) {
+                        s_cnt[i] = 0u;
+                        __hip_atomic_fetch_add(o + i, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                slot = 0;
+            } else {
+                slot += 1u;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+#undef K2R_HIST_ADD
+
+int launch_bulk_hist(const ChunkRef* d_refs, const uint8_t* d_enc, const HistUnit* d_units, uint32_t n, const uint8_t* d_mask,
+                     const int32_t* d_thr, uint32_t n_bins, uint64_t* d_out) {
+    if (n == 0) return DCDF_OK;
+    if (n_bins == 0 || n_bins > HIST_MAX_BINS) return DCDF_ERR_BAD_ARG;
+    static_assert(((uint32_t)1 << 9) == HIST_THR && HIST_MAX_BINS + 2u <= HIST_THR, "the largest table fits s_thr");
+    static_assert(HIST_COUNTS >= HIST_MAX_BINS, "one instant's counters fit s_cnt");
+    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    const uint32_t steps = hist_steps(n_bins);
+    if (d_mask) hipLaunchKernelGGL((k_bulk_hist<true>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
+    else hipLaunchKernelGGL((k_bulk_hist<false>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

@@ -3,10 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <map>
 #include <new>
 
 #include "k2r_bulk.h"
 #include "k2r_decode.h"
+#include "k2r_hist.h"
 #include "k2r_query_host.h"
 #include "k2r_reduce.h"
 #include "k2r_space.h"
@@ -979,6 +981,18 @@ extern "C" int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, c
     *sum = space_round(acc);
     return DCDF_OK;
 }
+// the host masks of the cubes that have instants, one after the other in a pooled device buffer: cube q's at moff[q]
+static int stage_cube_masks(const dcdf_cube* cubes, size_t nq, const uint8_t* mask, const uint64_t* mask_offset, const std::vector<uint64_t>& moff,
+                            uint64_t mask_total, DevBuf& d_mask) {
+    K2R_HIP(d_mask.alloc_pooled(mask_total));
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+        if (c.end == c.start || bytes == 0) continue;
+        K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], mask + mask_offset[q], bytes, hipMemcpyHostToDevice));
+    }
+    return DCDF_OK;
+}
 extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint8_t* mask,
                                               const uint64_t* mask_offset, int mask_mem, double* out, int out_mem, const uint64_t* out_offset,
                                               uint64_t stats[3], float* kernel_ms) {
@@ -1184,13 +1198,8 @@ extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_c
     double* const d_dst = (double*)W.dst();
     const uint8_t* p_mask = mask;
     if (stage_mask) {
-        K2R_HIP(d_mask.alloc_pooled(mask_total));
-        for (size_t q = 0; q < nq; q++) {
-            const dcdf_cube c = norm_cube(cubes[q]);
-            const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-            if (c.end == c.start || bytes == 0) continue;
-            K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], mask + mask_offset[q], bytes, hipMemcpyHostToDevice));
-        }
+        const int rcm = stage_cube_masks(cubes, nq, mask, mask_offset, moff, mask_total, d_mask);
+        if (rcm != DCDF_OK) return rcm;
         p_mask = (const uint8_t*)d_mask.p;
     }
     K2R_HIP(d_recs.alloc_pooled(rec_max * sizeof(SpacePartial)));
@@ -1225,6 +1234,270 @@ extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_c
         }
         hipLaunchKernelGGL(k_space_finish, dim3((uint32_t)std::min<size_t>(b.job1 - b.job0, 1u << 20), std::min<uint32_t>(b.job_nt, 1024)), dim3(256), 0,
                            0, d_jobs.as<SpaceJob>() + b.job0, (uint32_t)(b.job1 - b.job0), recs, d_dst, ops);
+        K2R_HIP(hipGetLastError());
+    }
+    K2R_HIP(hipEventRecord(ev.e1, 0));
+    K2R_HIP(hipDeviceSynchronize());
+    const int rcf = W.finish();
+    if (rcf != DCDF_OK) return rcf;
+    float ms = 0.f;
+    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (kernel_ms) *kernel_ms = ms;
+    return DCDF_OK;
+}
+// ---- value histograms: per instant, how many selected cells of a cube fall into every bin of shared edges (k2r_hist.h) -------
+// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  Every piece -- a 64 x 64 unit of the bulk
+// kernel, a piece of the window walk, an elided piece -- adds its counts to the cube's own [instants][bins] array with
+// device-scope 64-bit atomic adds; the call zeroes exactly those arrays first.  Integer adds commute, so the work of all segments
+// and cubes goes into one launch of each kind and the result depends on no order.
+//
+// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding and
+// binned by the definition itself (hist_bin: the values here are wide, and the walk dominates), masked cells skipped, counts in
+// an LDS histogram first.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per
+// instant adds that count to the bin of the piece's value.
+__global__ void __launch_bounds__(256)
+k_hist_fold(const HistFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+            const uint8_t* __restrict__ mask, const double* __restrict__ edges, uint32_t n_bins, uint64_t* out) {
+    __shared__ uint32_t sh_cnt[HIST_MAX_BINS];
+    __shared__ uint32_t sh_sel;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const HistFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        if (P.elided) {
+            if (blockIdx.y != 0) continue;
+            __syncthreads();  // (the previous piece's readers are done)
+            if (threadIdx.x == 0) sh_sel = mask ? 0u : (uint32_t)cells;
+            __syncthreads();
+            if (mask) {
+                uint32_t c = 0;
+                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) c += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
+                if (c) atomicAdd(&sh_sel, c);
+                __syncthreads();
+            }
+            const uint32_t selected = sh_sel;
+            for (uint32_t t = threadIdx.x; t < P.nt && selected; t += blockDim.x) {
+                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, vals[P.src + t]));
+                if (b >= 0) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + (uint32_t)b), (unsigned long long)selected);
+            }
+            continue;
+        }
+        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
+            __syncthreads();  // (the previous round's readers are done)
+            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) sh_cnt[i] = 0u;
+            __syncthreads();
+            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
+                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
+                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, slab[P.src + (uint64_t)t * cells + e]));
+                if (b >= 0) atomicAdd(&sh_cnt[b], 1u);
+            }
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) {
+                const uint32_t c = sh_cnt[i];
+                if (c) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + i), (unsigned long long)c);
+            }
+        }
+    }
+}
+extern "C" int dcdf_histogram_bounds(int32_t encoding, uint32_t fractional_bits, const double* edges, uint32_t n_bins, int64_t* lo, int64_t* hi) {
+    if (!lo || !hi || !hist_edges_ok(edges, n_bins) || !hist_leaf_ok(encoding, fractional_bits)) return DCDF_ERR_BAD_ARG;
+    hist_intervals(encoding, fractional_bits, edges, n_bins, lo, hi);
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* edges, uint32_t n_bins,
+                                           const uint8_t* mask, const uint64_t* mask_offset, int mask_mem, uint64_t* out, int out_mem,
+                                           const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || !hist_edges_ok(edges, n_bins) ||
+        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) || (mask && !mask_offset) ||
+        (mask && mask_mem != DCDF_MEM_HOST && mask_mem != DCDF_MEM_DEVICE))
+        return DCDF_ERR_BAD_ARG;
+    if (!r->all_wave || r->bad_fbits) return DCDF_ERR_UNSUPPORTED;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (nq == 0) return DCDF_OK;
+    // where the counts go: cube q's are "instants" of one row of [bins] to WindowOut; where its mask bytes are
+    std::vector<dcdf_cube> rows(nq, dcdf_cube{});
+    std::vector<uint64_t> moff(nq, 0);
+    uint64_t mask_total = 0;
+    const bool stage_mask = mask && mask_mem == DCDF_MEM_HOST;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
+        if (c.end == c.start) continue;
+        rows[q] = dcdf_cube{0, c.end - c.start, 0, 1, 0, n_bins};
+        if (mask) {
+            moff[q] = stage_mask ? mask_total : mask_offset[q];
+            mask_total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+        }
+    }
+    WindowOut W(rows.data(), nq, out, out_offset, sizeof(uint64_t), out_mem == DCDF_MEM_DEVICE);
+    // the thresholds of every distinct (encoding, fractional bits) among the bulk kernel's leaves: translated once, here
+    const uint32_t tab = (uint32_t)1 << hist_steps(n_bins);
+    std::map<std::pair<int32_t, uint32_t>, uint32_t> leaf_thr;
+    std::vector<int32_t> thr;
+    struct Slab {
+        size_t item0, item1, fold0, fold1;
+    };
+    std::vector<HistUnit> units;
+    std::vector<HistFold> cfolds, wfolds;
+    std::vector<WinItem> items;
+    std::vector<Slab> slabs;
+    const uint64_t slab_cap = reduce_slab_cells();
+    uint64_t slab_used = 0, slab_max = 0, fold_nt = 1;
+    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
+    uint32_t max_nt = 0;
+    Slab cur_slab{0, 0, 0, 0};
+    auto flush_slab = [&] {
+        cur_slab.item1 = items.size();
+        cur_slab.fold1 = wfolds.size();
+        if (cur_slab.fold1 > cur_slab.fold0) slabs.push_back(cur_slab);
+        slab_max = std::max(slab_max, slab_used);
+        cur_slab = Slab{items.size(), 0, wfolds.size(), 0};
+        slab_used = 0;
+    };
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
+        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
+            const uint64_t m_off = moff[q] + (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
+            const uint64_t o_off = W.base[q] + (uint64_t)(t0 + l.start - c.start) * n_bins;
+            const uint64_t cells = cube_cells(l);
+            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
+            HistFold p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, f.enc, f.fbits, 1u, 0u,
+                       (uint64_t)cid * r->cs + l.start, o_off, m_off};
+            if (f.elided) {
+                cfolds.push_back(p);
+                n_const += cells;
+                return;
+            }
+            const dcdf_chunk* h = r->chunks[cid];
+            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
+            if (!(h->top_g && h->narrow32)) {  // into slabs: whole pieces up to the cell bound, a piece beyond it cut in time
+                p.enc = h->encoding;
+                p.fbits = h->fbits;
+                p.elided = 0;
+                const uint64_t plane = (uint64_t)p.rows * p.cols;
+                const uint32_t nt = p.nt, cut = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, slab_cap / plane));
+                if (cut < nt || slab_used + (uint64_t)nt * plane > slab_cap) flush_slab();
+                for (uint32_t x = 0; x < nt; x += cut) {
+                    const uint32_t y = std::min(nt, x + cut);
+                    dcdf_cube kk = k;
+                    kk.start = k.start + x;
+                    kk.end = k.start + y;
+                    HistFold w = p;
+                    w.nt = y - x;
+                    w.src = slab_used;
+                    w.o_off = o_off + (uint64_t)x * n_bins;
+                    window_items(cid, kk, slab_used, items, r->all_node);
+                    wfolds.push_back(w);
+                    fold_nt = std::max<uint64_t>(fold_nt, w.nt);
+                    slab_used += (uint64_t)(y - x) * plane;
+                    if (cut < nt) flush_slab();
+                }
+                n_walk += cells;
+                return;
+            }
+            const auto key = std::make_pair((int32_t)h->encoding, (uint32_t)h->fbits);
+            auto it = leaf_thr.find(key);
+            if (it == leaf_thr.end()) {
+                it = leaf_thr.emplace(key, (uint32_t)thr.size()).first;
+                thr.resize(thr.size() + tab);
+                hist_thresholds32(key.first, key.second, edges, n_bins, thr.data() + it->second, tab);
+            }
+            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
+                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
+                    HistUnit u{};
+                    u.chunk = cid;
+                    u.t0 = k.start;
+                    u.t1 = k.end;
+                    u.rr = (uint16_t)rr;
+                    u.rc = (uint16_t)rc;
+                    u.top = (uint16_t)std::max(rr, k.top);
+                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
+                    u.left = (uint16_t)std::max(rc, k.left);
+                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
+                    u.m_sr = (uint32_t)wc;
+                    u.thr = it->second;
+                    u.rev = hist_reversed(key.first, key.second) ? 1u : 0u;
+                    u.o_off = o_off;
+                    u.m_off = m_off + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
+                    units.push_back(u);
+                }
+            max_nt = std::max(max_nt, k.end - k.start);
+            n_bulk += cells;
+        });
+        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || cfolds.size() + wfolds.size() > 0xfffffff0ull ||
+            thr.size() > 0x7fffffffull)
+            return DCDF_ERR_CAPACITY;
+    }
+    flush_slab();
+    if (stats) {
+        stats[0] = n_bulk;
+        stats[1] = n_walk;
+        stats[2] = n_const;
+    }
+    if (W.total == 0) return DCDF_OK;
+    // few units: a unit's instants in several workgroups (bulk_parts); each part adds to its own instants' rows
+    if (bulk_parts(units.size(), max_nt, bulk_wanted_units()) > 1) {
+        std::vector<HistUnit> split;
+        split.reserve(units.size() * 2);
+        for (const HistUnit& u : units) {
+            const uint32_t nt = u.t1 - u.t0, np = bulk_parts(units.size(), nt, bulk_wanted_units());
+            for (uint32_t j = 0; j < np; j++) {
+                HistUnit v = u;
+                v.t0 = bulk_part(u.t0, nt, np, j);
+                v.t1 = bulk_part(u.t0, nt, np, j + 1);
+                v.o_off = u.o_off + (uint64_t)(v.t0 - u.t0) * n_bins;
+                if (v.t1 > v.t0) split.push_back(v);
+            }
+        }
+        units.swap(split);
+    }
+    DevBuf d_units, d_cfolds, d_wfolds, d_items, d_slab, d_mask, d_thr, d_edges;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    uint64_t* const d_dst = (uint64_t*)W.dst();
+    const uint8_t* p_mask = mask;
+    if (stage_mask) {
+        const int rcm = stage_cube_masks(cubes, nq, mask, mask_offset, moff, mask_total, d_mask);
+        if (rcm != DCDF_OK) return rcm;
+        p_mask = (const uint8_t*)d_mask.p;
+    }
+    if (!units.empty()) {
+        K2R_HIP(upload(d_units, units));
+        K2R_HIP(upload(d_thr, thr));
+    }
+    if (!cfolds.empty()) K2R_HIP(upload(d_cfolds, cfolds));
+    if (!wfolds.empty()) K2R_HIP(upload(d_wfolds, wfolds));
+    if (!items.empty()) K2R_HIP(upload(d_items, items));
+    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
+    if (!cfolds.empty() || !wfolds.empty()) K2R_HIP(upload(d_edges, std::vector<double>(edges, edges + n_bins + 1)));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    // the accumulators: exactly the cubes' arrays, nothing between them
+    if (!W.to_dev) {
+        K2R_HIP(hipMemsetAsync(d_dst, 0, W.total * W.es, 0));
+    } else {
+        for (size_t q = 0; q < nq; q++) {
+            const uint64_t n = cube_cells(rows[q]);
+            if (n) K2R_HIP(hipMemsetAsync(d_dst + W.base[q], 0, n * sizeof(uint64_t), 0));
+        }
+    }
+    if (!cfolds.empty()) {
+        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(cfolds.size(), 1u << 20), 1), dim3(256), 0, 0, d_cfolds.as<HistFold>(),
+                           (uint32_t)cfolds.size(), nullptr, r->d_vals.as<int64_t>(), p_mask, d_edges.as<double>(), n_bins, d_dst);
+        K2R_HIP(hipGetLastError());
+    }
+    int rc = launch_bulk_hist(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<HistUnit>(), (uint32_t)units.size(), p_mask,
+                              d_thr.as<int32_t>(), n_bins, d_dst);
+    if (rc != DCDF_OK) return rc;
+    for (const Slab& sl : slabs) {
+        rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + sl.item0, (uint32_t)(sl.item1 - sl.item0), d_slab.p, DCDF_I64, nullptr,
+                                     nullptr, r->all_node, r->all_narrow);
+        if (rc != DCDF_OK) return rc;
+        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), (uint32_t)std::min<uint64_t>(fold_nt, 1024)),
+                           dim3(256), 0, 0, d_wfolds.as<HistFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), d_slab.as<int64_t>(), nullptr,
+                           p_mask, d_edges.as<double>(), n_bins, d_dst);
         K2R_HIP(hipGetLastError());
     }
     K2R_HIP(hipEventRecord(ev.e1, 0));

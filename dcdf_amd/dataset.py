@@ -411,6 +411,25 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return {n: np.empty(0, dtype=np.float64) for n in EncodedRaster.reduce_ops(ops)[1]}
         return self.raster().reduce_space(ops, start, stop, window=(top, bottom, left, right), mask=mask)
 
+    def histogram(self, edges, start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
+        """Per-instant value histogram over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
+        ([rows, cols] of the window, boolean or uint8) is non-zero when a mask is given: ndarray [stop - start, bins] uint64, the
+        number of values window() returns, widened to float64, in every bin of `edges` (bins + 1 increasing values; edges[b] <= x
+        < edges[b + 1], the last bin closed, NaN cells and values outside the edges counted nowhere).  Through raster().histogram:
+        the encoded bytes are read once on the GPU and only the counts are written (dcdf_raster_histogram_batch)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        bottom = R if bottom is None else bottom
+        right = Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        from .raster import EncodedRaster
+        e = EncodedRaster._edges(edges)
+        if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
+            raise ValueError("histogram: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            return np.zeros((0, e.size - 1), dtype=np.uint64)
+        return self.raster().histogram(e, start, stop, window=(top, bottom, left, right), mask=mask)
+
     def search(self, start, stop, top, bottom, left, right, lower, upper):
         """(instant, row, col) of the cells with lower <= stored value <= upper (mmarray.rs:206; span.rs:231-270): not in
         py-dcdf, which never exposed search.  Integers only (stored values)."""

@@ -210,6 +210,41 @@ class EncodedRaster:
         out, _, _, _ = self.reduce_time_flat([[start, stop, top, bottom, left, right]], mask)
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
+    @staticmethod
+    def _mask_args(q, masks, what):
+        """The mask arguments of dcdf_raster_reduce_space_batch / dcdf_raster_histogram_batch for the cubes q: (pointer, offsets,
+        memory kind, what must stay alive over the call).  masks as reduce_space_flat documents them."""
+        m_ptr, m_off, m_mem, keep = None, None, L.MEM_HOST, None
+        if isinstance(masks, tuple) and len(masks) == 2 and isinstance(masks[0], (int, np.integer)):
+            keep = np.ascontiguousarray(np.asarray(masks[1], dtype=np.uint64))
+            if keep.shape != (len(q),):
+                raise ValueError("%s: %d mask offsets for %d cubes" % (what, keep.size, len(q)))
+            m_ptr, m_off, m_mem = C.c_void_p(int(masks[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE
+        elif masks is not None:
+            masks = list(masks)
+            if len(masks) != len(q):
+                raise ValueError("%s: %d masks for %d cubes" % (what, len(masks), len(q)))
+            if any(m is not None for m in masks):
+                rows = np.abs(q[:, 3].astype(np.int64) - q[:, 2])
+                cols = np.abs(q[:, 5].astype(np.int64) - q[:, 4])
+                parts = []
+                for i, m in enumerate(masks):
+                    shape = (int(rows[i]), int(cols[i]))
+                    if m is None:
+                        parts.append(np.ones(shape[0] * shape[1], dtype=np.uint8))
+                        continue
+                    m = np.asarray(m)
+                    if m.shape != shape:
+                        raise ValueError("%s: mask %d has shape %r, its cube %r" % (what, i, m.shape, shape))
+                    parts.append((m != 0).astype(np.uint8).ravel())
+                moff = np.zeros(len(q), dtype=np.uint64)
+                if len(q) > 1:
+                    moff[1:] = np.cumsum([p.size for p in parts])[:-1]
+                flat_mask = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=np.uint8)]))
+                keep = (flat_mask, moff)
+                m_ptr, m_off = C.c_void_p(flat_mask.ctypes.data), C.c_void_p(moff.ctypes.data)
+        return m_ptr, m_off, m_mem, keep
+
     def reduce_space_flat(self, cubes, ops, masks=None, out_device_ptr=None, out_offset=None):
         """Per-instant statistics over the selected cells of dataset-level cubes [n, 6] through dcdf_raster_reduce_space_batch: cube
         q yields one [instants] float64 series per statistic of `ops` (reduce_ops), in the order min, max, sum, count, mean, over
@@ -223,35 +258,7 @@ class EncodedRaster:
         q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
         ms = C.c_float()
         stats = np.zeros(3, dtype=np.uint64)
-        m_ptr, m_off, m_mem, keep = None, None, L.MEM_HOST, None
-        if isinstance(masks, tuple) and len(masks) == 2 and isinstance(masks[0], (int, np.integer)):
-            keep = np.ascontiguousarray(np.asarray(masks[1], dtype=np.uint64))
-            if keep.shape != (len(q),):
-                raise ValueError("reduce_space: %d mask offsets for %d cubes" % (keep.size, len(q)))
-            m_ptr, m_off, m_mem = C.c_void_p(int(masks[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE
-        elif masks is not None:
-            masks = list(masks)
-            if len(masks) != len(q):
-                raise ValueError("reduce_space: %d masks for %d cubes" % (len(masks), len(q)))
-            if any(m is not None for m in masks):
-                rows = np.abs(q[:, 3].astype(np.int64) - q[:, 2])
-                cols = np.abs(q[:, 5].astype(np.int64) - q[:, 4])
-                parts = []
-                for i, m in enumerate(masks):
-                    shape = (int(rows[i]), int(cols[i]))
-                    if m is None:
-                        parts.append(np.ones(shape[0] * shape[1], dtype=np.uint8))
-                        continue
-                    m = np.asarray(m)
-                    if m.shape != shape:
-                        raise ValueError("reduce_space: mask %d has shape %r, its cube %r" % (i, m.shape, shape))
-                    parts.append((m != 0).astype(np.uint8).ravel())
-                moff = np.zeros(len(q), dtype=np.uint64)
-                if len(q) > 1:
-                    moff[1:] = np.cumsum([p.size for p in parts])[:-1]
-                flat_mask = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=np.uint8)]))
-                keep = (flat_mask, moff)
-                m_ptr, m_off = C.c_void_p(flat_mask.ctypes.data), C.c_void_p(moff.ctypes.data)
+        m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "reduce_space")
         if out_device_ptr is None:
             vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(len(names))
             off = np.zeros(len(q), dtype=np.uint64)
@@ -288,6 +295,70 @@ class EncodedRaster:
             return {n: np.empty(0, dtype=np.float64) for n in names}
         out, _, _, _ = self.reduce_space_flat([[start, stop, top, bottom, left, right]], bits, None if mask is None else [mask])
         return {n: out[i * nt:(i + 1) * nt] for i, n in enumerate(names)}
+
+    @staticmethod
+    def _edges(edges):
+        """Histogram edges as float64 [bins + 1]: 1 .. 256 bins, no NaN, strictly increasing (-inf first and +inf last are fine)."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
+        if e.ndim != 1 or not 2 <= e.size <= L.HIST_MAX_BINS + 1:
+            raise ValueError("histogram: edges must be 2 .. %d increasing values" % (L.HIST_MAX_BINS + 1))
+        if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+            raise ValueError("histogram: edges must be strictly increasing, without NaN")
+        return e
+
+    def histogram_flat(self, cubes, edges, masks=None, out_device_ptr=None, out_offset=None):
+        """Per-instant value histograms over the selected cells of dataset-level cubes [n, 6] through dcdf_raster_histogram_batch:
+        cube q yields a dense [instants, bins] uint64 array of counts over the values decode_flat returns for it in the leaves' own
+        dtype, widened to float64 -- edges[b] <= x < edges[b + 1], the last bin closed (numpy.histogram's rule), NaN and values
+        outside the edges counted nowhere.  edges: bins + 1 increasing values shared by all cubes.  masks: as reduce_space_flat.
+        Host form: returns (flat uint64 array, offsets uint64[n], kernel ms, stats): cube q is flat[offsets[q]:] shaped (instants,
+        bins).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by
+        the bulk kernel, by the fallback walk, from elided leaves."""
+        e = self._edges(edges)
+        bins = e.size - 1
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        ms = C.c_float()
+        stats = np.zeros(3, dtype=np.uint64)
+        m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "histogram")
+        if out_device_ptr is None:
+            vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(bins)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = np.zeros(max(1, int(vol.sum())), dtype=np.uint64)
+            L.check(L.lib().dcdf_raster_histogram_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(e.ctypes.data),
+                                                        C.c_uint32(bins), m_ptr, m_off, m_mem, C.c_void_p(out.ctypes.data), L.MEM_HOST,
+                                                        C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
+                    "raster_histogram_batch")
+            return out, off, ms.value, stats
+        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_histogram_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(e.ctypes.data),
+                                                    C.c_uint32(bins), m_ptr, m_off, m_mem, C.c_void_p(out_device_ptr), L.MEM_DEVICE,
+                                                    C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
+                "raster_histogram_batch")
+        return ms.value, stats
+
+    def histogram(self, edges, start=0, stop=None, window=None, mask=None):
+        """ndarray [stop - start, bins] uint64: per instant of [start, stop), how many cells of the whole raster, or of `window` =
+        (top, bottom, left, right), fall into every bin of `edges` (histogram_flat's rule); mask: [rows, cols] of the window,
+        non-zero = the cell is selected.  Without instants: shape (0, bins)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
+        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
+            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        e = self._edges(edges)
+        bins = e.size - 1
+        if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
+            raise ValueError("histogram: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
+        nt = stop - start
+        if nt == 0:
+            return np.zeros((0, bins), dtype=np.uint64)
+        out, _, _, _ = self.histogram_flat([[start, stop, top, bottom, left, right]], e, None if mask is None else [mask])
+        return out[:nt * bins].reshape(nt, bins)
 
     def search_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
         """search of dataset-level cubes through dcdf_raster_search_batch: returns (triples uint32[hits, 3] in raster coordinates

@@ -33,4 +33,6 @@ assert list(series) == ["max", "count", "mean"] and (series["max"] == a[8:24, 10
 disc = (np.mgrid[0:256, 0:256][0] - 128) ** 2 + (np.mgrid[0:256, 0:256][1] - 128) ** 2 < 100 ** 2
 flat, offsets, _, stats = R.reduce_space_flat([(0, 32, 0, 256, 0, 256)], ("sum", "mean"), masks=[disc])
 assert all(flat[t] == math.fsum(a[t][disc].tolist()) and flat[32 + t] == flat[t] / disc.sum() for t in range(32))
+counts = R.histogram([0, 250, 500, 750, 1000], 8, 24, mask=disc)
+assert counts.shape == (16, 4) and all((counts[t] == np.histogram(a[8 + t][disc], [0, 250, 500, 750, 1000])[0]).all() for t in range(16))
 print("readme example ok")

@@ -295,6 +295,38 @@ int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes,
  * bits; *sum = that integer / 2^63 as the nearest double, ties to even.  Pure host function; no GPU, no HIP call (so it is
  * testable on a CPU-only machine).  DCDF_ERR_BAD_ARG: a NULL pointer, a scale beyond those bits. */
 int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum);
+/* Value histograms: per instant of each cube, how many of its SELECTED cells fall into every bin of shared edges -- the
+ * distribution of values over an area.  The call takes plain and tiled rasters (elided leaves included).  Cubes, the mask
+ * (mask, mask_offset, mask_mem) and stats are exactly dcdf_raster_reduce_space_batch's: reversed bounds are swapped, a non-zero
+ * byte of the dense [rows][cols] mask of cube q selects the cell, stats are the numbers dcdf_raster_decode_batch reports for the
+ * same cubes and the mask does not change them.
+ *   edges   n_bins + 1 doubles in HOST memory, shared by all cubes, strictly increasing; -inf first and +inf last are allowed
+ *           ("below" and "above" bins).  1 <= n_bins <= DCDF_HIST_MAX_BINS.
+ *   x       of a cell: reduce_space's x, the stored integer n widened with the encoding and fractional bits of the leaf that holds
+ *           the cell -- (double)(int32_t)n, (double)n, from_fixed in float widened to double, from_fixed in double, NaN for a stored
+ *           0 of a float leaf.  NaN cells are counted nowhere.
+ *   bin     a selected non-NaN cell is counted in bin b when edges[b] <= x < edges[b + 1]; the last bin takes edges[n_bins - 1]
+ *           <= x <= edges[n_bins] (numpy.histogram's rule for explicit edges).  Cells below edges[0] or above edges[n_bins] are
+ *           counted nowhere.
+ * Cube q writes a dense [instants][n_bins] array of uint64 from out + out_offset[q] (elements), host or device memory.  A cube
+ * without instants writes nothing; one with instants but no selected cell writes zeros; nothing outside a cube's array is
+ * written.  With device memory the arrays themselves are the accumulators: the call zeroes them, then adds.  Counts are integers,
+ * so the result depends on no order and on no cut of the work.
+ * DCDF_ERR_BAD_ARG: NULL edges, out, out_offset or cubes; n_bins of 0 or above DCDF_HIST_MAX_BINS; a NaN edge; edges not strictly
+ * increasing; a mask without offsets; an unknown *_mem.  DCDF_ERR_BOUNDS: a cube outside the raster.  DCDF_ERR_UNSUPPORTED:
+ * k * k > 64 chunks.  nq == 0 is fine; stats and kernel_ms may be NULL. */
+#define DCDF_HIST_MAX_BINS 256
+int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* edges, uint32_t n_bins,
+                                const uint8_t* mask, const uint64_t* mask_offset, int mask_mem, uint64_t* out, int out_mem,
+                                const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* The translation dcdf_raster_histogram_batch rests on: [lo[b], hi[b]] is the inclusive interval of the stored integers of a
+ * chunk of this encoding and these fractional bits that bin b takes; lo[b] > hi[b] when it takes none.  x is monotone in the
+ * stored integer, so the intervals are found by bisection with the decoder's own expression: (double)n rounds beyond 2^53 and
+ * (float)(n - 1) beyond 2^24, so n < edge does not imply x < edge; with 62 fractional bits x decreases in n and the intervals
+ * come out in reverse order.  Stored 0 of a float encoding (NaN) belongs to no bin: it is never an end of an interval, and where
+ * it lies strictly inside one it is simply never counted.  Pure host function; no GPU, no HIP call (so it is testable on a
+ * CPU-only machine).  DCDF_ERR_BAD_ARG: a NULL pointer, the edge errors above, an unknown encoding, float fractional_bits > 62. */
+int dcdf_histogram_bounds(int32_t encoding, uint32_t fractional_bits, const double* edges, uint32_t n_bins, int64_t* lo, int64_t* hi);
 /* search of nq dataset-level cubes: (instant, row, col) triples in RASTER coordinates (span.rs:231-270 adds the segment offset,
  * superchunk.rs:516-585 the tile origin); query q's triples are out[3 * offsets[q] .. + 3 * counts[q]), ordered by piece
  * (segment, tile row, tile col), sorted inside a piece. */
