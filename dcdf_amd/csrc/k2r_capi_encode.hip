@@ -586,6 +586,49 @@ extern "C" int dcdf_encoder_run(dcdf_encoder* e, float* kernel_ms) {
                 std::fprintf(stderr, "k2r-pw %-24s %9.0f %9.0f %9.0f %9.0f %6.1f%%\n", names[k], mean / d, mx / d, (double)w[0][k][0] / d, wait / d,
                              all ? 100.0 * (mean + wait) / all : 0.0);
             }
+            // Every wave of every phase: which wave is the busy one decides where work can be moved to.
+            const double d = insts ? (double)insts : 1.0;
+            for (int c = 0; c < 2; c++) {
+                std::fprintf(stderr, "k2r-pw-%s %-24s", c ? "wait" : "work", "phase \\ wave");
+                for (int v = 0; v < nw; v++) std::fprintf(stderr, " %6d", v);
+                std::fprintf(stderr, "\n");
+                for (int k = 0; k < NPROF; k++) {
+                    uint64_t any = 0;
+                    for (int v = 0; v < nw; v++) any += w[v][k][0] + w[v][k][1];
+                    if (!any) continue;
+                    std::fprintf(stderr, "k2r-pw-%s %-24s", c ? "wait" : "work", names[k]);
+                    for (int v = 0; v < nw; v++) std::fprintf(stderr, " %6.0f", (double)w[v][k][c] / d);
+                    std::fprintf(stderr, "\n");
+                }
+            }
+            // Phases with no barrier between them form a group: a wave runs through the group at its own pace, so the group costs
+            // the workgroup the largest per-wave SUM of work, not the sum of the per-phase maxima.  Every other phase is a group of
+            // its own.  (The third group wraps around: the tail of one instant runs into phase 1 of the next.)
+            static const struct { const char* name; int n; int k[3]; } groups[] = {
+                {"A + I + Q records", 3, {10, 11, 6}}, {"replay + zero bm + p1", 3, {14, 9, 0}}, {"p3 + scan", 2, {2, 3}},
+                {"p2 top", 1, {1}}, {"sizes+heuristic", 1, {12}}, {"clear+hdr", 1, {4}}, {"V0,M0 bitmaps", 1, {8}},
+                {"emit C snapshot", 1, {5}}, {"T/eqB bitmaps", 1, {7}}};
+            std::fprintf(stderr, "k2r-pw-group %-24s", "group \\ wave");
+            for (int v = 0; v < nw; v++) std::fprintf(stderr, " %6d", v);
+            std::fprintf(stderr, " %7s %7s\n", "max", "mean");
+            double crit = 0, avg = 0;
+            for (const auto& g : groups) {
+                double mx = 0, mean = 0;
+                std::fprintf(stderr, "k2r-pw-group %-24s", g.name);
+                for (int v = 0; v < nw; v++) {
+                    double s = 0;
+                    for (int i = 0; i < g.n; i++) s += (double)w[v][g.k[i]][0];
+                    std::fprintf(stderr, " %6.0f", s / d);
+                    mx = std::max(mx, s);
+                    mean += s;
+                }
+                mean /= nw ? nw : 1;
+                std::fprintf(stderr, " %7.0f %7.0f\n", mx / d, mean / d);
+                crit += mx;
+                avg += mean;
+            }
+            std::fprintf(stderr, "k2r-pw-group sum of the group maxima %.0f, of the group means %.0f, imbalance %.0f (cycles per chunk-instant)\n",
+                         crit / d, avg / d, (crit - avg) / d);
         }
 #endif
         // per-tile totals: how uneven are the chunks?  (cycles per instant, logs that did not come from the stash)

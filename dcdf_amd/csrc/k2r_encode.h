@@ -66,6 +66,11 @@ struct EncCfg {
     static constexpr int WT = (MAXT + 31) / 32;
     // offset of height h (3..H) inside the top arrays; height 3 first
     static constexpr int top_off(int h) { return ((1 << (2 * (H - 2))) - (1 << (2 * (H - h + 1)))) / 3; }
+    // Which wave takes the one-off work of a phase (EX::item: the wave named here gets items 0..63; wave numbers wrap in smaller
+    // workgroups).  From the per-wave table of DESIGN.md 7.0: wave 0 comes out of planning last, and the waves of the last
+    // quarter are the slowest of every phase they share with the others.
+    static constexpr int kWaveHeader = 1;  // phase 5a: instant header, min/max pair, block-header patch, list counters
+    static constexpr int kWavePrefix = 2;  // phase 5a: rank prefix over the top-node flags
 };
 
 struct EncRegs {
@@ -658,9 +663,9 @@ struct EncPool {
     static constexpr int POOL_BMV1 = 12 * C::NBLK;              // word offset of bmV1 (WV+1 words)
     static constexpr int POOL_PREFV = POOL_BMV1 + C::WV + 1;    // word offset of prefV (WV+2 words)
 #ifdef K2R_PROFILE
-    static constexpr int POOLFILL = 1828 - 16 * NPROF * 4;  // (the per-wave cycle sums of the diagnostic build live in LDS too)
+    static constexpr int POOLFILL = 1826 - 16 * NPROF * 4;  // (the per-wave cycle sums of the diagnostic build live in LDS too)
 #else
-    static constexpr int POOLFILL = 1828;
+    static constexpr int POOLFILL = 1826;  // (1828 before the two ticket words of EncShared)
 #endif
     static constexpr int POOLW = POOL_PREFV + C::WV + 2 + (C::H == 8 ? POOLFILL : 0);  // sidelen 256: LDS filled to 160 KB
     // The stash's two record kinds have fixed shares of the pool (I records from word 0, Q records from word QBASE);
@@ -709,6 +714,7 @@ struct EncShared : EncPool<C> {
     uint32_t ttR[C::H + 2];             // rank (over those flags) of the first node of height h
     uint32_t nlistV, nlistM;
     uint32_t stI, stQ;  // stash record counters
+    uint32_t tkI, tkQ;  // tickets of the two record passes of the emission: the next record nobody has taken (EX::take)
     InstPlan<C> pl;
     int32_t err;
     uint32_t work;
@@ -1173,6 +1179,8 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             sh.err = 0;
             sh.stI = 0;
             sh.stQ = 0;
+            sh.tkI = 0;
+            sh.tkQ = 0;
             for (int i = 0; i < 6; i++) sh.fault[i] = 0;
             for (int i = 0; i < NPROF; i++) sh.prof[i] = 0;
             if (cap >= 6 && !cont) {
@@ -2047,6 +2055,8 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             if (tid == 0) {
                 sh.stI = 0;
                 sh.stQ = 0;
+                sh.tkI = 0;  // (the previous instant's record passes ended many barriers ago)
+                sh.tkQ = 0;
             }
             if (wt < (uint32_t)C::NTOPX) {
                 int h;
@@ -2389,22 +2399,33 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             sh.pfx[0][tid] = pI12;
             sh.pfx[1][tid] = pL0;
             sh.pfx[2][tid] = (pL12 & 0xffffu) | (pM12 << 16);
-            if (tid <= C::TBW) {  // rank prefix over the winner's top-node flags (<= 12 words)
+            // The one-off work of this phase sits on two waves that have nothing else here, not on wave 0 behind its planning:
+            // the rank prefix on a lane of one, the header on a lane of the other.  The prefix is one lane's running sum over
+            // words it reads up front, stored as it goes (a loop over "the words before mine" on every one of thirteen lanes
+            // was a chain of LDS round trips that the whole workgroup waited for).
+            const uint32_t tp = EX::item(tid, C::kWavePrefix), th = EX::item(tid, C::kWaveHeader);
+            if (tp == 0) {  // rank prefix over the winner's top-node flags (<= 12 words)
                 const uint32_t* const tbw = as_snapshot ? sh.tbS : sh.tbL;
-                uint32_t run = 0;
-                for (int w = 0; w < tid && w < C::TBW; w++) run += popc32(tbw[w]);
-                sh.tbP[tid] = run;
+                uint32_t wd[C::TBW], run = 0;
+#pragma unroll
+                for (int w = 0; w < C::TBW; w++) wd[w] = tbw[w];
+#pragma unroll
+                for (int w = 0; w < C::TBW; w++) {
+                    sh.tbP[w] = run;
+                    run += popc32(wd[w]);
+                }
+                sh.tbP[C::TBW] = run;
             }
-            if (tid == 0) {
+            if (th == 0) {
                 sh.nlistV = 0;
                 sh.nlistM = 0;
-                if (do_patch) out[hdr_patch_off] = (uint8_t)hdr_patch_val;
-                io[0] = 2;  // k  (snapshot.rs:49, log.rs:54)
-                store_be32(io + 1, ta.rows);
-                store_be32(io + 5, ta.cols);
-                store_be32(io + 9, (uint32_t)C::S);
-                io[DV.bm_off[0] - 1] = (uint8_t)DV.nlev;  // dac.rs:38
-                io[DM.bm_off[0] - 1] = (uint8_t)DM.nlev;
+                if (do_patch) gstore8(out + hdr_patch_off, (uint8_t)hdr_patch_val);
+                gstore8(io, 2);  // k  (snapshot.rs:49, log.rs:54)
+                gstore32u(io + 1, __builtin_bswap32(ta.rows));
+                gstore32u(io + 5, __builtin_bswap32(ta.cols));
+                gstore32u(io + 9, __builtin_bswap32((uint32_t)C::S));
+                gstore8(io + DV.bm_off[0] - 1, (uint8_t)DV.nlev);  // dac.rs:38
+                gstore8(io + DM.bm_off[0] - 1, (uint8_t)DM.nlev);
                 if (ta.minmax) {
                     ta.minmax[2 * inst] = sh.tmin[C::top_off(H)];
                     ta.minmax[2 * inst + 1] = sh.tmax[C::top_off(H)];
@@ -2616,7 +2637,7 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
               ex.par_nosync([&](int tid, EncRegs&) {
                 const uint32_t offV1 = TT.offV[1], offZ1 = TT.offZ[1], offI1 = TT.offI[1], lt = TT.LT, ne = TT.LT - TT.M0;
                 const uint32_t lv1 = sh.pl.lngV[1], lm1 = sh.pl.lngM[1];
-                for (uint32_t k = (uint32_t)tid; k < nI2; k += NT) {
+                for (uint32_t k = ex.take(&sh.tkI, tid); k < nI2; k = ex.take(&sh.tkI, tid)) {
                     uint32_t rec[5];
                     if (!OVF || k < (uint32_t)SH::CAPI_REC) {
 #pragma unroll
@@ -2671,7 +2692,7 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
               constexpr bool OVF = decltype(ovf_tag)::value != 0;
               ex.par([&](int tid, EncRegs&) {
                 const uint32_t offV0 = TT.offV[0], lv0 = sh.pl.lngV[0];
-                for (uint32_t m = (uint32_t)tid; m < nI1; m += NT) {
+                for (uint32_t m = ex.take(&sh.tkQ, tid); m < nI1; m = ex.take(&sh.tkQ, tid)) {
                     uint32_t q[3];
                     if (!OVF || m < (uint32_t)SH::CAPQ_REC) {
 #pragma unroll

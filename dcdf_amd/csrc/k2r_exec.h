@@ -15,6 +15,23 @@ namespace k2r {
 
 constexpr int MAX_SCAN_FIELDS = 16;  // 32-bit words per thread that scan<>/reduce<> can combine
 
+// Which thread does which work item, with the waves rotated: wave v takes the 64 items that wave (v + rot) % NW takes in the
+// plain mapping (item == tid).  The lanes of a wave keep 64 consecutive items, so nothing changes for coalescing or for the
+// level order of the records a wave reads; what changes is WHICH wave gets the remainder trip of a strided loop, or the one-off
+// work of a phase: `rot` places it on a wave that has little else to do between the same two barriers.  The
+// identity for a workgroup of one wave or less.  Both execution contexts use it, so the simulator walks the same mapping.
+template <int NT>
+K2R_HD constexpr uint32_t wave_item(int tid, int rot) {
+    constexpr uint32_t NW = NT <= 64 ? 1u : (uint32_t)NT / 64u;
+    return NT <= 64 ? (uint32_t)tid : ((((uint32_t)tid >> 6) + (uint32_t)rot) % NW) * 64u + ((uint32_t)tid & 63u);
+}
+// rotation that puts item-wave 0 -- the first to get a remainder trip, the owner of items 0..63 -- on wave v
+template <int NT>
+K2R_HD constexpr int wave_rot_to(int v) {
+    constexpr int NW = NT <= 64 ? 1 : NT / 64;
+    return (NW - v % NW) % NW;
+}
+
 #if defined(__HIPCC__)
 
 template <class SH, class TR, int NT>
@@ -27,6 +44,8 @@ struct GpuExec {
     static constexpr bool kSim = false;
 
     __device__ GpuExec(SH& s) : sh(s), tid((int)threadIdx.x) {}
+    // work item of thread `t` with item-wave 0 on wave `first` (wave_item above; `first` is a compile-time constant)
+    __device__ __forceinline__ static uint32_t item(int t, int first) { return wave_item<NT>(t, wave_rot_to<NT>(first)); }
 
 #ifdef K2R_PROFILE
     // Diagnostic builds: every WAVE keeps two running sums between stamps -- cycles it spent running its own code ("work") and
@@ -347,6 +366,16 @@ struct GpuExec {
         endb = bb + (tot >> 16);
     }
 
+    // The next work items nobody has taken, one per lane: lane 0 draws a wave's worth of tickets from the LDS counter with one
+    // atomic add and the wave reads the first of them.  The lanes still in a loop over take() are always lanes 0..n of the
+    // wave (a lane leaves when ITS item is past the end, and items ascend with the lane), so lane 0 is there while any is.
+    __device__ __forceinline__ uint32_t take(uint32_t* ctr, int t) {
+        constexpr uint32_t W = NT < 64 ? NT : 64;
+        uint32_t first = 0;
+        if ((t & 63) == 0) first = atomicAdd(ctr, W);
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + (uint32_t)(t & 63);
+    }
+
     __device__ __forceinline__ uint32_t lds_or_nr(uint32_t* p, uint32_t v) { atomicOr(p, v); return 0; }
     __device__ __forceinline__ uint32_t lds_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
     __device__ __forceinline__ uint32_t lds_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
@@ -402,6 +431,7 @@ struct SimExec {
     static constexpr bool kSim = true;
 
     explicit SimExec(SH& s) : sh(s), regs(NT) {}
+    static uint32_t item(int t, int first) { return wave_item<NT>(t, wave_rot_to<NT>(first)); }
 
     template <class F>
     void par(F&& f) {
@@ -452,6 +482,7 @@ struct SimExec {
         enda = *cntA;
         endb = *cntB;
     }
+    uint32_t take(uint32_t* ctr, int) { return (*ctr)++; }  // (every thread is a "wave" of its own)
     uint32_t lds_or_nr(uint32_t* p, uint32_t v) {
         *p |= v;
         return 0;
