@@ -1,6 +1,11 @@
-// k2r_bulk.h -- the bulk decoder's work unit and launcher (k2r_bulk.hip), planned by dcdf_raster_decode_batch (k2r_raster.hip).
+// k2r_bulk.h -- the bulk decoder's work unit and launcher (k2r_bulk.hip), planned by plan_decode (k2r_plan.h).  The structs and
+// the split arithmetic compile for the host alone as well (g++).
 #pragma once
-#include "k2r_query_types.h"
+#if defined(__HIPCC__)
+#include "k2r_query_types.h"  // (ChunkRef, for the launcher and for k2r_bulk.hip)
+#else
+#include "k2r_common.h"
+#endif
 
 namespace k2r {
 
@@ -28,9 +33,11 @@ K2R_HD uint32_t bulk_parts(uint64_t n_units, uint32_t nt, uint32_t wanted) {
     return p < 1 ? 1u : (uint32_t)p;
 }
 
+#if defined(__HIPCC__)
 // k_bulk_decode over n units on the null stream (asynchronous); d_out holds out_dtype elements.  Returns a DCDF code.
 int launch_bulk_decode(const ChunkRef* d_refs, const BulkUnit* d_units, uint32_t n, void* d_out, int32_t out_dtype);
 // workgroups the device wants in flight before a unit's instants are worth splitting
 uint32_t bulk_wanted_units();
+#endif
 
 }  // namespace k2r

@@ -1,4 +1,4 @@
-// k2r_hist.h -- per-instant value histograms (dcdf_raster_histogram_batch): what the planner (k2r_raster.hip), the bulk kernel
+// k2r_hist.h -- per-instant value histograms (dcdf_raster_histogram_batch): what the planner (k2r_plan.h), the bulk kernel
 // (k2r_bulk.hip) and the fold kernel share.  Everything above the plan compiles for the host alone as well (g++), so the
 // translation of bin edges into stored integers can be run and sanitised on a CPU.
 //

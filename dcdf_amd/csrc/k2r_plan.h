@@ -1,0 +1,475 @@
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram: k2r_raster_region.hip) turn a
+// batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
+//
+// A cube is cut into pieces, one per leaf it meets (raster_pieces).  A piece is of one of three kinds: on an elided leaf (one
+// value per instant: dcdf_raster::d_vals), on a chunk the bulk kernels take (side-16 table, 32-bit values) -- it becomes one unit
+// per 64 x 64 region of the chunk's own grid --, or on any other chunk -- the window walk decodes it, for the reductions into a
+// slab of stored integers a fold kernel then reads.  The planner sees the raster's geometry and a table of its leaves, never a
+// chunk.  Everything that reaches a launch keeps one order: cubes in batch order, then segment, tile row, tile column, then the
+// regions' rows, columns, then instants.
+#pragma once
+#include <map>
+#include <utility>
+
+#include "k2r_bulk.h"
+#include "k2r_hist.h"
+#include "k2r_items.h"
+#include "k2r_reduce.h"
+#include "k2r_space.h"
+
+// an elided piece of a decode: one value per instant over a rectangle of the window (k_raster_fill_const; outside the namespace,
+// where the kernels' mangled names have it)
+struct ConstPiece {
+    uint32_t leaf, ls, le, rows, cols, out_sr;  // leaf-local instants [ls, le), the rectangle, the window's row stride
+    uint64_t out_off, out_st;                   // element of (ls, top, left) in `out`; the window's instant stride
+};
+
+namespace k2r {
+
+// The per-piece path -- raster_pieces, plan_pieces, plan_units and the callers' lambdas -- is forced inline: left to itself the
+// compiler keeps them out of line and builds every Piece in memory, which a batch of many small cubes pays for per piece.
+#define K2R_PLAN_INLINE inline __attribute__((always_inline))
+#define K2R_PLAN_LAMBDA __attribute__((always_inline))
+
+// ---- what the planner sees of a raster ---------------------------------------------------------------------------------------
+struct PlanLeaf {
+    uint32_t row0, col0;  // where the leaf starts inside its chunk
+    int32_t enc;          // what the folds widen with: the leaf's own for an elided leaf, else the chunk's
+    uint32_t fbits;
+    uint8_t elided, bulk_ok;  // bulk_ok: the chunk has a side-16 table and 32-bit values
+};
+struct PlanRaster {
+    uint32_t T, R, C, tile, cs, nti, ntj;
+    const PlanLeaf* leaves;  // [(segment * nti + ti) * ntj + tj]
+};
+inline int plan_bounds(const PlanRaster& g, const dcdf_cube* cubes, size_t nq) {
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end > g.T || c.bottom > g.R || c.right > g.C) return DCDF_ERR_BOUNDS;
+    }
+    return DCDF_OK;
+}
+
+// room to start a list with: a batch of nq cubes has at least nq pieces (many small cubes: no growth by doubling on the way there)
+inline size_t plan_reserve(size_t nq) { return std::min<size_t>(nq, (size_t)1 << 20); }
+
+// ---- pieces ------------------------------------------------------------------------------------------------------------------
+// the pieces of one dataset-level cube (normalised, not empty): f(leaf id, leaf-local cube, raster origin of the leaf)
+template <class F>
+K2R_PLAN_INLINE void raster_pieces(const PlanRaster& g, const dcdf_cube& c, F&& f) {
+    for (uint32_t seg = c.start / g.cs; seg <= (c.end - 1) / g.cs; seg++)
+        for (uint32_t ti = c.top / g.tile; ti <= (c.bottom - 1) / g.tile; ti++)
+            for (uint32_t tj = c.left / g.tile; tj <= (c.right - 1) / g.tile; tj++) {
+                const uint32_t t0 = seg * g.cs, r0 = ti * g.tile, c0 = tj * g.tile;
+                const dcdf_cube l{std::max(c.start, t0) - t0, std::min(c.end, t0 + g.cs) - t0, std::max(c.top, r0) - r0,
+                                  std::min(c.bottom, r0 + g.tile) - r0, std::max(c.left, c0) - c0, std::min(c.right, c0 + g.tile) - c0};
+                f((uint32_t)(((uint64_t)seg * g.nti + ti) * g.ntj + tj), l, t0, r0, c0);
+            }
+}
+enum PieceKind : uint32_t { PIECE_BULK = 0, PIECE_WALK = 1, PIECE_CONST = 2 };  // (the order of the calls' stats[3])
+struct Piece {
+    uint32_t leaf;
+    PieceKind kind;
+    dcdf_cube l, k;       // the piece in the leaf's coordinates and in its chunk's (l moved by row0 / col0)
+    uint32_t t0, r0, c0;  // the leaf's origin in the raster
+    int32_t enc;          // PlanLeaf's
+    uint32_t fbits;
+    uint32_t dt;          // the piece's first instant, counted from the cube's
+    uint64_t in_win;      // its first cell in the cube's [rows][cols] plane
+    uint64_t cells;
+    uint32_t nt() const { return l.end - l.start; }
+    uint32_t rows() const { return l.bottom - l.top; }
+    uint32_t cols() const { return l.right - l.left; }
+};
+// every piece of cube c, classified; its cells are added to stats[kind]
+template <class F>
+K2R_PLAN_INLINE void plan_pieces(const PlanRaster& g, const dcdf_cube& c, uint64_t stats[3], F&& f) {
+    raster_pieces(g, c, [&](uint32_t leaf, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) K2R_PLAN_LAMBDA {
+        const PlanLeaf& L = g.leaves[leaf];
+        Piece p{leaf, L.elided ? PIECE_CONST : L.bulk_ok ? PIECE_BULK : PIECE_WALK, l,
+                dcdf_cube{l.start, l.end, L.row0 + l.top, L.row0 + l.bottom, L.col0 + l.left, L.col0 + l.right}, t0, r0, c0, L.enc, L.fbits,
+                t0 + l.start - c.start, (uint64_t)(r0 + l.top - c.top) * (c.right - c.left) + (c0 + l.left - c.left), cube_cells(l)};
+        stats[p.kind] += p.cells;
+        f(p);
+    });
+}
+// One unit per 64 x 64 region of the chunk's grid that a bulk piece meets: the fields every unit type starts with (BulkUnit's
+// first 24 bytes) are set here, own(u) sets the rest.
+template <class U, class F>
+K2R_PLAN_INLINE void plan_units(const Piece& p, std::vector<U>& units, F&& own) {
+    const dcdf_cube& k = p.k;
+    for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
+        for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
+            U u{};
+            u.chunk = p.leaf;
+            u.t0 = k.start;
+            u.t1 = k.end;
+            u.rr = (uint16_t)rr;
+            u.rc = (uint16_t)rc;
+            u.top = (uint16_t)std::max(rr, k.top);
+            u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
+            u.left = (uint16_t)std::max(rc, k.left);
+            u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
+            own(u);
+            units.push_back(u);
+        }
+}
+// the place of unit u's first cell inside its piece, in a plane of row stride sr
+template <class U>
+inline uint64_t unit_in_piece(const U& u, const Piece& p, uint64_t sr) { return (uint64_t)(u.top - p.k.top) * sr + (u.left - p.k.left); }
+// Few units: the instants of every unit of units[from ..) in several workgroups (bulk_parts; each part decodes its Snapshot
+// again).  advance(v, dt) moves a part's own offset dt instants on.  wanted: bulk_wanted_units().
+template <class U, class F>
+inline void plan_time_split(std::vector<U>& units, size_t from, uint32_t wanted, F&& advance) {
+    const size_t nu = units.size() - from;
+    if (bulk_parts(nu, ~0u, wanted) <= 1) return;  // enough units, however long (the usual case: no pass over them)
+    uint32_t max_nt = 0;
+    for (size_t i = from; i < units.size(); i++) max_nt = std::max(max_nt, units[i].t1 - units[i].t0);
+    const uint32_t parts = bulk_parts(nu, max_nt, wanted);
+    if (parts <= 1) return;
+    std::vector<U> split;
+    split.reserve(nu * parts);
+    for (size_t i = from; i < units.size(); i++) {
+        const U& u = units[i];
+        const uint32_t nt = u.t1 - u.t0, np = bulk_parts(nu, nt, wanted);
+        for (uint32_t j = 0; j < np; j++) {
+            U v = u;
+            v.t0 = bulk_part(u.t0, nt, np, j);
+            v.t1 = bulk_part(u.t0, nt, np, j + 1);
+            advance(v, v.t0 - u.t0);
+            if (v.t1 > v.t0) split.push_back(v);
+        }
+    }
+    units.resize(from);
+    units.insert(units.end(), split.begin(), split.end());
+}
+
+// ---- the window walk's pieces, in slabs --------------------------------------------------------------------------------------
+// One slab: a walk launch over items[item0, item1) decodes stored integers into the slab, a fold launch over folds[fold0, fold1)
+// reads them.  A slab takes whole pieces up to `cap` cells; a piece beyond that is cut in time and each part gets a slab of its
+// own: two parts of one piece share their cells (reduce_time's state planes), so one fold launch must never hold both.
+struct Slab {
+    size_t item0, item1, fold0, fold1;
+};
+template <class Fold>
+struct SlabCutter {
+    uint64_t cap, used = 0, slab_max = 0;  // cells: the bound, of the current slab, of the largest
+    uint32_t fold_nt = 1;                  // the longest part
+    Slab cur{0, 0, 0, 0};
+    std::vector<WinItem> items;
+    std::vector<Fold> folds;
+    std::vector<Slab> slabs;
+    explicit SlabCutter(uint64_t cap_) : cap(cap_) {}
+    void flush() {
+        cur.item1 = items.size();
+        cur.fold1 = folds.size();
+        if (cur.fold1 > cur.fold0) slabs.push_back(cur);
+        slab_max = std::max(slab_max, used);
+        cur = Slab{items.size(), 0, folds.size(), 0};
+        used = 0;
+    }
+    // a walk piece of nt instants of `plane` cells: part(a, b, src) pushes the fold and the items of its instants [a, b), whose
+    // integers start at element src of the slab
+    template <class F>
+    void add(uint32_t nt, uint64_t plane, F&& part) {
+        const uint32_t cut = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, cap / plane));
+        if (cut < nt || used + (uint64_t)nt * plane > cap) flush();
+        for (uint32_t a = 0; a < nt; a += cut) {
+            const uint32_t b = std::min(nt, a + cut);
+            part(a, b, used);
+            fold_nt = std::max(fold_nt, b - a);
+            used += (uint64_t)(b - a) * plane;
+            if (cut < nt) flush();
+        }
+    }
+};
+// a walk piece kept until its slab is known: the leaf, the chunk-level cube, and its fold without the slab offset
+template <class Fold>
+struct WalkPiece {
+    uint32_t chunk;
+    dcdf_cube k;
+    Fold f;
+};
+// the instants [a, b) of a walk piece's cube
+inline dcdf_cube cube_instants(dcdf_cube k, uint32_t a, uint32_t b) {
+    k.end = k.start + b;
+    k.start += a;
+    return k;
+}
+
+// ---- decode ------------------------------------------------------------------------------------------------------------------
+// base[q]: element of cube q's first cell in the output; all three lists write that one array
+struct DecodePlan {
+    std::vector<BulkUnit> units;
+    std::vector<WinItem> items;
+    std::vector<ConstPiece> consts;
+    uint64_t stats[3] = {0, 0, 0};
+};
+inline int plan_decode(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, bool node_wise, uint32_t wanted,
+                       DecodePlan& P) {
+    P.units.reserve(plan_reserve(nq));
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if (cube_cells(c) == 0) continue;
+        plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+            const uint64_t at = base[q] + p.dt * wr * wc + p.in_win;
+            if (p.kind == PIECE_CONST) P.consts.push_back(ConstPiece{p.leaf, p.l.start, p.l.end, p.rows(), p.cols(), (uint32_t)wc, at, wr * wc});
+            else if (p.kind == PIECE_WALK) window_items(p.leaf, p.k, at, P.items, node_wise, wc, wr * wc);
+            else
+                plan_units(p, P.units, [&](BulkUnit& u) {
+                    u.out_sr = (uint32_t)wc;
+                    u.out_st = wr * wc;
+                    u.out_off = at + unit_in_piece(u, p, wc);
+                });
+        });
+        if (P.units.size() > 0x3fffffffull || P.items.size() > 0xfffffff0ull || P.consts.size() > 0xfffffff0ull) return DCDF_ERR_CAPACITY;
+    }
+    plan_time_split(P.units, 0, wanted, [](BulkUnit& v, uint32_t dt) { v.out_off += (uint64_t)dt * v.out_st; });
+    return DCDF_OK;
+}
+
+// ---- reduce over time --------------------------------------------------------------------------------------------------------
+// Within a time segment every cell of a cube lies in exactly one piece, so the work of one segment never shares a cell; the
+// segments are launched one after the other in ascending order (SegRange), and each piece continues the running sum of its cells'
+// state plane.  base[q] / sbase[q]: cube q's first output / scratch plane.
+struct SegRange {
+    size_t unit0, unit1, const0, const1, slab0, slab1;
+};
+struct TimePlan {
+    std::vector<ReduceUnit> units;
+    std::vector<FoldPiece> cfolds;
+    SlabCutter<FoldPiece> walk;
+    std::vector<SegRange> ranges;
+    std::vector<MeanPiece> means;
+    uint64_t stats[3] = {0, 0, 0};
+    explicit TimePlan(uint64_t slab_cap) : walk(slab_cap) {}
+};
+inline int plan_reduce_time(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* sbase, bool node_wise,
+                            TimePlan& P) {
+    struct Segment {
+        std::vector<ReduceUnit> units;
+        std::vector<FoldPiece> consts;
+        std::vector<WalkPiece<FoldPiece>> walks;
+    };
+    std::vector<Segment> segs((g.T + g.cs - 1) / g.cs);
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if (cube_cells(c) == 0) continue;
+        P.means.push_back(MeanPiece{base[q], sbase[q], wr * wc});
+        plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+            Segment& S = segs[p.t0 / g.cs];
+            const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
+            const FoldPiece f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
+                              (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc};
+            if (p.kind == PIECE_CONST) S.consts.push_back(f);
+            else if (p.kind == PIECE_WALK) S.walks.push_back(WalkPiece<FoldPiece>{p.leaf, p.k, f});
+            else
+                plan_units(p, S.units, [&](ReduceUnit& u) {
+                    u.sr = (uint32_t)wc;
+                    u.init = init;
+                    u.o_off = f.o_off + unit_in_piece(u, p, wc);
+                    u.s_off = f.s_off + unit_in_piece(u, p, wc);
+                    u.psz = wr * wc;
+                });
+        });
+    }
+    for (Segment& S : segs) {
+        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
+        SegRange r{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0};
+        P.units.insert(P.units.end(), S.units.begin(), S.units.end());
+        P.cfolds.insert(P.cfolds.end(), S.consts.begin(), S.consts.end());
+        for (const WalkPiece<FoldPiece>& w : S.walks)
+            P.walk.add(w.f.nt, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t a, uint32_t b, uint64_t src) {
+                FoldPiece f = w.f;
+                f.nt = b - a;
+                f.init = w.f.init && a == 0;
+                f.src = src;
+                window_items(w.chunk, cube_instants(w.k, a, b), src, P.walk.items, node_wise);
+                P.walk.folds.push_back(f);
+            });
+        P.walk.flush();  // (a slab never spans two segments)
+        r.unit1 = P.units.size();
+        r.const1 = P.cfolds.size();
+        r.slab1 = P.walk.slabs.size();
+        P.ranges.push_back(r);
+        S = Segment{};
+        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull)
+            return DCDF_ERR_CAPACITY;
+    }
+    return DCDF_OK;
+}
+
+// ---- reduce over space -------------------------------------------------------------------------------------------------------
+// Every piece leaves one SpacePartial per instant in a scratch array; the pieces of one (cube, segment) share their instants, so
+// their records form one block [slot][instant] (a SpaceJob) that k_space_finish folds into the cube's series.  The jobs are
+// taken in batches whose records fit rec_cap (a job beyond it alone: a huge cube's segment is cut in time first); the batches
+// run one after the other over the same scratch.  base[q]: cube q's series; moff[q]: its mask's first byte.
+struct SpaceBatch {
+    size_t unit0, unit1, const0, const1, slab0, slab1, job0, job1;
+    uint32_t job_nt;  // the longest job
+};
+struct SpacePlan {
+    std::vector<SpaceUnit> units;
+    std::vector<SpaceFold> cfolds;
+    SlabCutter<SpaceFold> walk;
+    std::vector<SpaceJob> jobs;
+    std::vector<SpaceBatch> batches;
+    uint64_t rec_max = 0;  // records of the largest batch
+    uint64_t stats[3] = {0, 0, 0};
+    explicit SpacePlan(uint64_t slab_cap) : walk(slab_cap) {}
+};
+inline int plan_reduce_space(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, bool node_wise,
+                             uint64_t rec_cap, uint32_t wanted, SpacePlan& P) {
+    uint64_t rec_used = 0;
+    SpaceBatch cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    P.units.reserve(plan_reserve(nq));
+    P.jobs.reserve(plan_reserve(nq));
+    auto flush_batch = [&] {
+        P.walk.flush();
+        // each part of a split unit writes its own instants' records
+        plan_time_split(P.units, cur.unit0, wanted, [](SpaceUnit& v, uint32_t dt) { v.rec += dt; });
+        cur.unit1 = P.units.size();
+        cur.const1 = P.cfolds.size();
+        cur.slab1 = P.walk.slabs.size();
+        cur.job1 = P.jobs.size();
+        if (cur.job1 > cur.job0) P.batches.push_back(cur);
+        P.rec_max = std::max(P.rec_max, rec_used);
+        rec_used = 0;
+        cur = SpaceBatch{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0, P.jobs.size(), 0, 0};
+    };
+    std::vector<SpaceUnit> tu;  // the pieces of one (cube, segment), before they are cut into jobs
+    std::vector<SpaceFold> tc;
+    std::vector<WalkPiece<SpaceFold>> tw;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end == c.start) continue;
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        for (uint32_t seg = c.start / g.cs; seg <= (c.end - 1) / g.cs; seg++) {
+            const uint32_t s0 = seg * g.cs, ls = std::max(c.start, s0), le = std::min(c.end, s0 + g.cs);  // the cube's instants of this segment
+            tu.clear();
+            tc.clear();
+            tw.clear();
+            if (wr * wc != 0)
+                plan_pieces(g, dcdf_cube{ls, le, c.top, c.bottom, c.left, c.right}, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+                    const SpaceFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, p.enc, p.fbits, p.kind == PIECE_CONST, 0u,
+                                      (uint64_t)p.leaf * g.cs + p.l.start, 0, moff[q] + p.in_win};
+                    if (p.kind == PIECE_CONST) tc.push_back(f);
+                    else if (p.kind == PIECE_WALK) tw.push_back(WalkPiece<SpaceFold>{p.leaf, p.k, f});
+                    else
+                        plan_units(p, tu, [&](SpaceUnit& u) {
+                            u.m_sr = (uint32_t)wc;
+                            u.m_off = f.m_off + unit_in_piece(u, p, wc);
+                        });
+                });
+            // the segment's instants in jobs of at most rec_cap records (one job, but for a huge cube)
+            const uint64_t n_slots = tu.size() + tc.size() + tw.size();
+            const uint32_t nt = le - ls, step = n_slots ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, rec_cap / n_slots)) : nt;
+            for (uint32_t a = 0; a < nt; a += step) {
+                const uint32_t jn = std::min(nt, a + step) - a;
+                if (rec_used && rec_used + n_slots * jn > rec_cap) flush_batch();
+                P.jobs.push_back(SpaceJob{rec_used, (uint32_t)n_slots, jn, base[q] + (ls + a - c.start), (uint64_t)(c.end - c.start)});
+                uint64_t rec = rec_used;  // a slot per piece: units, elided pieces, walk pieces
+                for (SpaceUnit u : tu) {
+                    u.t0 += a;
+                    u.t1 = u.t0 + jn;
+                    u.rec = rec;
+                    P.units.push_back(u);
+                    rec += jn;
+                }
+                for (SpaceFold f : tc) {
+                    f.src += a;
+                    f.nt = jn;
+                    f.rec = rec;
+                    P.cfolds.push_back(f);
+                    rec += jn;
+                }
+                for (const WalkPiece<SpaceFold>& w : tw) {
+                    P.walk.add(jn, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t x, uint32_t y, uint64_t src) {
+                        SpaceFold f = w.f;
+                        f.nt = y - x;
+                        f.src = src;
+                        f.rec = rec + x;
+                        window_items(w.chunk, cube_instants(w.k, a + x, a + y), src, P.walk.items, node_wise);
+                        P.walk.folds.push_back(f);
+                    });
+                    rec += jn;
+                }
+                rec_used = rec;
+                cur.job_nt = std::max(cur.job_nt, jn);
+            }
+            if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
+                P.jobs.size() > 0x7ffffff0ull)
+                return DCDF_ERR_CAPACITY;
+        }
+    }
+    flush_batch();
+    return DCDF_OK;
+}
+
+// ---- histogram ---------------------------------------------------------------------------------------------------------------
+// Every piece adds its counts to the cube's own [instants][bins] array (base[q]) with integer atomics, so the work of all
+// segments and cubes goes into one launch of each kind.  thr: the thresholds of every distinct (encoding, fractional bits) among
+// the bulk kernel's leaves (hist_thresholds32), 2^hist_steps(n_bins) entries each, translated once.
+struct HistPlan {
+    std::vector<HistUnit> units;
+    std::vector<HistFold> cfolds;
+    SlabCutter<HistFold> walk;
+    std::vector<int32_t> thr;
+    uint64_t stats[3] = {0, 0, 0};
+    explicit HistPlan(uint64_t slab_cap) : walk(slab_cap) {}
+};
+inline int plan_histogram(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, const double* edges,
+                          uint32_t n_bins, bool node_wise, uint32_t wanted, HistPlan& P) {
+    const uint32_t tab = (uint32_t)1 << hist_steps(n_bins);
+    std::map<std::pair<int32_t, uint32_t>, uint32_t> leaf_thr;
+    P.units.reserve(plan_reserve(nq));
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wc = c.right - c.left;
+        if (cube_cells(c) == 0) continue;
+        plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+            const HistFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, p.enc, p.fbits, p.kind == PIECE_CONST, 0u,
+                             (uint64_t)p.leaf * g.cs + p.l.start, base[q] + (uint64_t)p.dt * n_bins, moff[q] + p.in_win};
+            if (p.kind == PIECE_CONST) {
+                P.cfolds.push_back(f);
+            } else if (p.kind == PIECE_WALK) {
+                P.walk.add(f.nt, (uint64_t)f.rows * f.cols, [&](uint32_t x, uint32_t y, uint64_t src) {
+                    HistFold w = f;
+                    w.nt = y - x;
+                    w.src = src;
+                    w.o_off = f.o_off + (uint64_t)x * n_bins;
+                    window_items(p.leaf, cube_instants(p.k, x, y), src, P.walk.items, node_wise);
+                    P.walk.folds.push_back(w);
+                });
+            } else {
+                auto it = leaf_thr.find({p.enc, p.fbits});
+                if (it == leaf_thr.end()) {
+                    it = leaf_thr.emplace(std::make_pair(p.enc, p.fbits), (uint32_t)P.thr.size()).first;
+                    P.thr.resize(P.thr.size() + tab);
+                    hist_thresholds32(p.enc, p.fbits, edges, n_bins, P.thr.data() + it->second, tab);
+                }
+                plan_units(p, P.units, [&](HistUnit& u) {
+                    u.m_sr = (uint32_t)wc;
+                    u.thr = it->second;
+                    u.rev = hist_reversed(p.enc, p.fbits) ? 1u : 0u;
+                    u.o_off = f.o_off;
+                    u.m_off = f.m_off + unit_in_piece(u, p, wc);
+                });
+            }
+        });
+        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
+            P.thr.size() > 0x7fffffffull)
+            return DCDF_ERR_CAPACITY;
+    }
+    P.walk.flush();
+    // each part of a split unit adds to its own instants' rows
+    plan_time_split(P.units, 0, wanted, [n_bins](HistUnit& v, uint32_t dt) { v.o_off += (uint64_t)dt * n_bins; });
+    return DCDF_OK;
+}
+
+#undef K2R_PLAN_INLINE
+#undef K2R_PLAN_LAMBDA
+
+}  // namespace k2r

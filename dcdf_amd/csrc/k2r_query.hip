@@ -1076,25 +1076,6 @@ extern "C" int dcdf_query_fill_cell_batch(dcdf_chunk* const* chunks, const uint3
 }
 
 // ---- wave items and their launchers (k2r_query_host.h) -----------------------------------------------------------------
-void k2r::window_items(uint32_t chunk, const dcdf_cube& c, uint64_t out_base, std::vector<WinItem>& items, bool node_wise, uint64_t sr,
-                       uint64_t st) {
-    const uint64_t wc = sr ? sr : (uint64_t)(c.right - c.left), wr_wc = st ? st : (uint64_t)(c.bottom - c.top) * wc;
-    const uint32_t step = node_wise ? 64u : 32u;
-    for (uint32_t t = c.start; t < c.end; t++)
-        for (uint32_t r = node_wise ? c.top : (c.top & ~31u); r < c.bottom; r += step)
-            for (uint32_t cc = node_wise ? c.left : (c.left & ~31u); cc < c.right; cc += step) {
-                WinItem it{};
-                it.chunk = chunk;
-                it.inst = t;
-                it.top = (uint16_t)std::max(r, c.top);
-                it.bottom = (uint16_t)std::min(r + step, c.bottom);
-                it.left = (uint16_t)std::max(cc, c.left);
-                it.right = (uint16_t)std::min(cc + step, c.right);
-                it.out_sr = (uint32_t)wc;
-                it.out_off = out_base + (uint64_t)(t - c.start) * wr_wc + (uint64_t)(it.top - c.top) * wc + (it.left - c.left);
-                items.push_back(it);
-            }
-}
 int k2r::launch_window_items_dev(const DevBuf& d_refs, const WinItem* d_items, uint32_t n, void* d_out, int32_t dtype, hipEvent_t e0, hipEvent_t e1,
                                  bool node_wise, bool narrow) {
     const uint32_t grid = std::min<uint32_t>((n + 3) / 4, 256u * 16u);

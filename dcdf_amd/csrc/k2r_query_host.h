@@ -64,18 +64,9 @@ inline ChunkRef make_ref(const dcdf_chunk* h) {
     return ChunkRef{h->p_bytes, h->p_descs, h->instants, h->rows, h->cols, h->fbits,
                     h->top_g ? (const TopEnt*)h->p_top : nullptr, h->top_g ? (const TopMM*)h->p_top_mm : nullptr, h->top_g, 0};
 }
-// geom::Cube::new reorders reversed bounds (geom.rs:83-103)
-inline dcdf_cube norm_cube(const dcdf_cube& c) {
-    dcdf_cube o = c;
-    if (o.start > o.end) std::swap(o.start, o.end);
-    if (o.top > o.bottom) std::swap(o.top, o.bottom);
-    if (o.left > o.right) std::swap(o.left, o.right);
-    return o;
-}
 inline bool cube_in(const dcdf_chunk* h, const dcdf_cube& c) {  // mmarray.rs:218-229
     return c.end <= h->instants && c.bottom <= h->rows && c.right <= h->cols;
 }
-inline uint64_t cube_cells(const dcdf_cube& c) { return (uint64_t)(c.end - c.start) * (c.bottom - c.top) * (c.right - c.left); }  // (normalised)
 // the wave kernel handles k * k <= 64 children per node and 16-bit coordinates
 inline bool wave_kernel_ok(const dcdf_chunk* h) { return h->k0 * h->k0 <= 64 && h->sidelen0 <= 65535; }
 inline bool node_kernel_ok(const dcdf_chunk* h) { return h->k0 == 2 && h->sidelen0 >= 4; }
@@ -146,13 +137,6 @@ struct WindowOut {
 };
 
 // ---- what k2r_query.hip defines for the raster layer.  The launchers are asynchronous on the null stream and return a DCDF code.
-// (chunk, instant, sub-window) items of one chunk-level cube `c`: pieces of at most 64 x 64 cells from the window's origin
-// (node_wise: k_window_wave2), else the squares of the chunk's 32-grid the window meets (k_window_wave, k_search_wave), so that a
-// frontier level never exceeds what a wave's LDS queue holds.  out_base = element offset of cell (c.start, c.top, c.left);
-// sr / st = row and instant strides of the array the window is written into (0 = the window's own dense layout; a piece of a
-// larger window passes the parent's)
-void window_items(uint32_t chunk, const dcdf_cube& c, uint64_t out_base, std::vector<WinItem>& items, bool node_wise, uint64_t sr = 0,
-                  uint64_t st = 0);
 // the fill walk over n items; e0 / e1 (may be null) are recorded around it; synchronises the device
 int launch_window_items_dev(const DevBuf& d_refs, const WinItem* d_items, uint32_t n, void* d_out, int32_t dtype, hipEvent_t e0, hipEvent_t e1,
                             bool node_wise, bool narrow);

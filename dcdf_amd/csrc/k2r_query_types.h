@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "k2r_decode.h"
+#include "k2r_items.h"
 
 namespace k2r {
 
@@ -159,13 +160,6 @@ struct SearchItem {
                               // of 64 rows x 2 words each) and pieces per row; w0 == SI_FLAT: the flat bitmap above is the one in use
 };
 constexpr uint32_t SI_FLAT = 0xffffffffu;
-// one (chunk, instant, sub-window) of a wave walk: at most 32 x 32 cells (k_window_wave, k_search_wave) or 64 x 64 (k_window_wave2)
-struct WinItem {
-    uint32_t chunk, inst;
-    uint16_t top, bottom, left, right;  // sub-window, chunk coordinates, half-open
-    uint32_t out_sr;                     // output row stride in elements (column stride 1)
-    uint64_t out_off;                    // element offset of cell (top, left) of this instant in `out`
-};
 struct SearchExtra {
     int64_t lower, upper;
     // The reference's Log::search_window has no case for a single-node UNIFORM log over a multi-node snapshot (log.rs:527-548):

@@ -1,17 +1,11 @@
-// k2r_raster.hip -- C ABI, query side: a tiled, time-segmented raster of opened chunks (dcdf_raster_*).  Routes dataset-level cubes
-// and points to their chunks on the device and runs the walks of k2r_query.hip / k2r_bulk.hip over the pieces.
+// k2r_raster.hip -- C ABI, query side: a tiled, time-segmented raster of opened chunks (dcdf_raster_*): the handle and its two
+// constructors, fill_window, search, get / fill_cell.  Routes dataset-level cubes and points to their chunks on the device and runs
+// the walks of k2r_query.hip over the pieces.  The calls that read whole regions are k2r_raster_region.hip's.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <map>
 #include <new>
 
-#include "k2r_bulk.h"
-#include "k2r_decode.h"
-#include "k2r_hist.h"
-#include "k2r_query_host.h"
-#include "k2r_reduce.h"
-#include "k2r_space.h"
+#include "k2r_raster_host.h"
 
 using namespace k2r;
 
@@ -21,33 +15,6 @@ using namespace k2r;
 // span.rs:190-216 over time, Superchunk::subchunks_for superchunk.rs:589-633 over rows / cols).  dcdf_raster does that split for a
 // whole batch of dataset-level cubes on the host in C++ and decodes every piece in ONE launch straight into its place in the
 // caller's window (the pieces carry the parent window's strides): no per-piece copies, no reassembly, the chunk table uploaded once.
-// one leaf of a tiled raster (dcdf_raster_tile without its pointers): where the leaf starts inside its chunk, or the elided
-// leaf's encoding / bits (its values live in dcdf_raster::d_vals), and what its holding node's (min, max) allow
-struct RasterLeaf {
-    uint32_t row0, col0;
-    int32_t enc;          // of the values / minmax
-    uint8_t elided, fbits, has_mm, exact;
-};
-struct dcdf_raster {
-    std::vector<dcdf_chunk*> chunks;  // [(segment * nti + ti) * ntj + tj]
-    // d_refs holds device pointers into the chunks' streams and tables: the raster shares the ownership of every slab a batch-opened
-    // chunk lives in (dcdf_chunk::store), so closing such a chunk first leaves the raster usable; chunks opened one by one own their
-    // buffers themselves and must outlive the raster (dcdf_k2r.h)
-    std::vector<std::shared_ptr<void>> keep;
-    uint32_t T = 0, R = 0, C = 0, tile = 0, cs = 0, nseg = 0, nti = 0, ntj = 0;
-    DevBuf d_refs;
-    DevBuf d_quirk;  // [chunk][chunk_size]: dcdf_chunk::search_quirk of every instant (k_raster_search_expand)
-    DevBuf d_enc;    // [chunk]: the chunk's encoding (value search translates its bounds per piece on the device)
-    bool all_wave = true, all_node = true, all_narrow = true;
-    bool bad_fbits = false;  // a float chunk with fractional bits value_bounds does not take (> 62)
-    // tiled rasters (dcdf_raster_create_tiles): the grid is one of leaves; chunks[] / d_refs hold NULL / zeros for elided leaves
-    // and the all_* flags are over chunk leaves only
-    bool tiled = false;
-    std::vector<RasterLeaf> leaves;  // [leaf]
-    DevBuf d_leaf;                   // the same on the device
-    DevBuf d_vals;                   // [leaf][chunk_size] int64: an elided leaf's value per instant (0 elsewhere)
-    DevBuf d_mm;                     // [leaf][chunk_size][2] int64: the holding node's (min, max) per instant (RasterLeaf::has_mm)
-};
 // what dcdf_raster_create and dcdf_raster_create_tiles share: the grid, the per-leaf tables, "chunk h is leaf i", the uploads
 struct RasterTables {
     std::vector<ChunkRef> refs;
@@ -65,6 +32,7 @@ static int raster_init(const void* leaves, size_t n, const uint32_t shape[3], ui
     r->ntj = (r->C + tile - 1) / tile;
     if ((uint64_t)r->nseg * r->nti * r->ntj != n) return DCDF_ERR_BAD_ARG;
     r->chunks.assign(n, nullptr);
+    r->plan_leaves.assign(n, PlanLeaf{});
     t.refs.assign(n, ChunkRef{});
     t.quirk.assign(n * (size_t)chunk_size, 0);
     t.enc.assign(n, 0);
@@ -77,8 +45,10 @@ static void raster_leaf_shape(const dcdf_raster* r, size_t i, uint32_t* li, uint
     *lr = std::min(r->tile, r->R - ti * r->tile);
     *lc = std::min(r->tile, r->C - tj * r->tile);
 }
-static void raster_add_chunk(dcdf_raster* r, RasterTables& t, size_t i, dcdf_chunk* h) {
+// chunk h is leaf i, which starts at (row0, col0) of it
+static void raster_add_chunk(dcdf_raster* r, RasterTables& t, size_t i, dcdf_chunk* h, uint32_t row0 = 0, uint32_t col0 = 0) {
     r->chunks[i] = h;
+    r->plan_leaves[i] = PlanLeaf{row0, col0, h->encoding, h->fbits, 0, (uint8_t)(h->top_g && h->narrow32)};
     if (h->store && (r->keep.empty() || r->keep.back() != h->store)) r->keep.push_back(h->store);
     t.refs[i] = make_ref(h);
     r->all_wave = r->all_wave && wave_kernel_ok(h);
@@ -148,13 +118,14 @@ extern "C" int dcdf_raster_create_tiles(const dcdf_raster_tile* tiles, size_t n_
             f.elided = 1;
             for (uint32_t k = 0; k < li; k++) vals[i * chunk_size + k] = L.values[k];
             t.enc[i] = (uint8_t)L.encoding;
+            r->plan_leaves[i] = PlanLeaf{0, 0, f.enc, f.fbits, 1, 0};  // (RasterLeaf's, as the device reads them)
             continue;
         }
         // the chunk must cover the leaf at (row0, col0), with the leaf's instants
         if (h->instants != li || (uint64_t)L.row0 + lr > h->rows || (uint64_t)L.col0 + lc > h->cols) return DCDF_ERR_BAD_ARG;
         f.row0 = L.row0;
         f.col0 = L.col0;
-        raster_add_chunk(r.get(), t, i, h);
+        raster_add_chunk(r.get(), t, i, h, L.row0, L.col0);
     }
     rc = raster_upload(r.get(), t);
     if (rc != DCDF_OK) return rc;
@@ -165,18 +136,6 @@ extern "C" int dcdf_raster_create_tiles(const dcdf_raster_tile* tiles, size_t n_
     return DCDF_OK;
 }
 
-// the pieces of one dataset-level cube: f(chunk id, local cube, raster origin of the chunk)
-template <class F>
-static void raster_pieces(const dcdf_raster* r, const dcdf_cube& c, F&& f) {
-    for (uint32_t seg = c.start / r->cs; seg <= (c.end - 1) / r->cs; seg++)
-        for (uint32_t ti = c.top / r->tile; ti <= (c.bottom - 1) / r->tile; ti++)
-            for (uint32_t tj = c.left / r->tile; tj <= (c.right - 1) / r->tile; tj++) {
-                const uint32_t t0 = seg * r->cs, r0 = ti * r->tile, c0 = tj * r->tile;
-                const dcdf_cube l{std::max(c.start, t0) - t0, std::min(c.end, t0 + r->cs) - t0, std::max(c.top, r0) - r0,
-                                  std::min(c.bottom, r0 + r->tile) - r0, std::max(c.left, c0) - c0, std::min(c.right, c0 + r->tile) - c0};
-                f((uint32_t)(((uint64_t)seg * r->nti + ti) * r->ntj + tj), l, t0, r0, c0);
-            }
-}
 // One thread per dataset-level cube: the wave items of its pieces (the loops of raster_pieces x window_items), written at
 // item_base[q]; the host only counts them (a closed form per cube) -- 24 bytes per item need not cross PCIe.
 struct RasterGeom {
@@ -222,13 +181,9 @@ k_raster_expand(const dcdf_cube* __restrict__ cubes, const uint64_t* __restrict_
 }
 // wave items of one cube (the count of the loops above)
 static uint64_t raster_item_count(const dcdf_raster* r, const dcdf_cube& c, uint32_t step) {
-    auto along = [&](uint32_t a, uint32_t b, uint32_t unit) {  // sum over the tiles [a, b) meets of ceil(piece / step) (from the piece's start, or the 32-grid)
+    auto along = [&](uint32_t a, uint32_t b, uint32_t unit) {  // axis_items summed over the tiles [a, b) meets
         uint64_t n = 0;
-        for (uint32_t t = a / unit; t <= (b - 1) / unit; t++) {
-            const uint32_t lo = std::max(a, t * unit) - t * unit, hi = std::min(b, t * unit + unit) - t * unit;
-            const uint32_t from = step == 64 ? lo : (lo & ~31u);
-            n += (hi - from + step - 1) / step;
-        }
+        for (uint32_t t = a / unit; t <= (b - 1) / unit; t++) n += axis_items(std::max(a, t * unit) - t * unit, std::min(b, t * unit + unit) - t * unit, step);
         return n;
     };
     return (uint64_t)(c.end - c.start) * along(c.top, c.bottom, r->tile) * along(c.left, c.right, r->tile);
@@ -236,17 +191,10 @@ static uint64_t raster_item_count(const dcdf_raster* r, const dcdf_cube& c, uint
 
 // ---- tiled rasters: fill_window -------------------------------------------------------------------------------------------
 // A piece on a chunk leaf is decoded by the wave walk at (row0 + r, col0 + c) of its chunk; a piece on an elided leaf becomes a
-// ConstPiece: one value per instant over a rectangle of the window, written by k_raster_fill_const in the same call.
-struct ConstPiece {
-    uint32_t leaf, ls, le, rows, cols, out_sr;  // leaf-local instants [ls, le), the rectangle, the window's row stride
-    uint64_t out_off, out_st;                   // element of (ls, top, left) in `out`; the window's instant stride
-};
-// wave items along one axis of a piece [a, b) in chunk coordinates: from the piece's start (node-wise walk, step 64) or from the
-// chunk's 32-grid (step 32) -- the loops of k_raster_expand / k_raster_tiled_expand
-K2R_HD uint32_t axis_items(uint32_t a, uint32_t b, uint32_t step) { return (b - (step == 64 ? a : (a & ~31u)) + step - 1) / step; }
+// ConstPiece (k2r_plan.h): one value per instant over a rectangle of the window, written by k_raster_fill_const in the same call.
 // wave items and constant pieces of one cube of a tiled raster
 static void tiled_item_count(const dcdf_raster* r, const dcdf_cube& c, uint32_t step, uint64_t* n_items, uint64_t* n_const) {
-    raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t, uint32_t, uint32_t) {
+    raster_pieces(r->plan(), c, [&](uint32_t cid, const dcdf_cube& l, uint32_t, uint32_t, uint32_t) {
         const RasterLeaf& f = r->leaves[cid];
         if (f.elided) {
             (*n_const)++;
@@ -347,6 +295,13 @@ k_raster_fill_const(const ConstPiece* __restrict__ ps, uint32_t n, const RasterL
         }
     }
 }
+int k2r::launch_raster_fill_const(const dcdf_raster* r, const ConstPiece* d_consts, uint32_t n, void* d_out, int32_t out_dtype) {
+    if (n == 0) return DCDF_OK;
+    hipLaunchKernelGGL(k_raster_fill_const, dim3(std::min(n, 256u * 64u)), dim3(256), 0, 0, d_consts, n, r->d_leaf.as<RasterLeaf>(), r->d_vals.as<int64_t>(),
+                       r->cs, d_out, out_dtype);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
 
 extern "C" int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype,
                                              int out_mem, const uint64_t* out_offset, float* kernel_ms) {
@@ -395,1119 +350,14 @@ extern "C" int dcdf_raster_fill_window_batch(const dcdf_raster* r, const dcdf_cu
                            d_consts.as<ConstPiece>());
         K2R_HIP(hipGetLastError());
         K2R_HIP(hipEventRecord(ev.e0, 0));
-        if (n_const)
-            hipLaunchKernelGGL(k_raster_fill_const, dim3((uint32_t)std::min<uint64_t>(n_const, 256u * 64u)), dim3(256), 0, 0, d_consts.as<ConstPiece>(),
-                               (uint32_t)n_const, r->d_leaf.as<RasterLeaf>(), r->d_vals.as<int64_t>(), r->cs, W.dst(), out_dtype);
-        K2R_HIP(hipGetLastError());
-        if (n_items) {
+        rc = launch_raster_fill_const(r, d_consts.as<ConstPiece>(), (uint32_t)n_const, W.dst(), out_dtype);
+        if (rc != DCDF_OK) return rc;
+        if (n_items)
             rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>(), (uint32_t)n_items, W.dst(), out_dtype, nullptr, ev.e1, r->all_node,
                                          r->all_narrow);
-        } else {
-            K2R_HIP(hipEventRecord(ev.e1, 0));
-            K2R_HIP(hipDeviceSynchronize());
-        }
     }
-    if (rc == DCDF_OK) rc = W.finish();
     if (rc != DCDF_OK) return rc;
-    float ms = 0.f;
-    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    if (kernel_ms) *kernel_ms = ms;
-    return DCDF_OK;
-}
-// ---- decompress: whole regions, block by block (k2r_bulk.hip) ---------------------------------------------------------------
-// The pieces of every cube, by the kind of leaf they fall on: a chunk with a side-16 table and 32-bit values becomes BulkUnits (a
-// workgroup per 64 x 64 region of the chunk's grid, looping over the piece's instants); any other chunk the wave items
-// dcdf_raster_fill_window_batch makes of it; an elided leaf a ConstPiece.  All three write the same output array.
-extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype, int out_mem,
-                                        const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || !out_args_ok(out_dtype, out_mem)) return DCDF_ERR_BAD_ARG;
-    if (!r->all_wave) return DCDF_ERR_UNSUPPORTED;
-    if (stats) stats[0] = stats[1] = stats[2] = 0;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (nq == 0) return DCDF_OK;
-    WindowOut W(cubes, nq, out, out_offset, elem_size(out_dtype), out_mem == DCDF_MEM_DEVICE);
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
-    }
-    std::vector<BulkUnit> units;
-    std::vector<WinItem> items;
-    std::vector<ConstPiece> consts;
-    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells
-    uint32_t max_nt = 0;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
-        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
-        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
-            const uint64_t at = W.base[q] + ((uint64_t)(t0 + l.start - c.start) * wr + (r0 + l.top - c.top)) * wc + (c0 + l.left - c.left);
-            const uint64_t cells = cube_cells(l);
-            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
-            if (f.elided) {
-                consts.push_back(ConstPiece{cid, l.start, l.end, l.bottom - l.top, l.right - l.left, (uint32_t)wc, at, wr * wc});
-                n_const += cells;
-                return;
-            }
-            const dcdf_chunk* h = r->chunks[cid];
-            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
-            if (!(h->top_g && h->narrow32)) {
-                window_items(cid, k, at, items, r->all_node, wc, wr * wc);
-                n_walk += cells;
-                return;
-            }
-            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
-                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
-                    BulkUnit u{};
-                    u.chunk = cid;
-                    u.t0 = k.start;
-                    u.t1 = k.end;
-                    u.rr = (uint16_t)rr;
-                    u.rc = (uint16_t)rc;
-                    u.top = (uint16_t)std::max(rr, k.top);
-                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
-                    u.left = (uint16_t)std::max(rc, k.left);
-                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
-                    u.out_sr = (uint32_t)wc;
-                    u.out_st = wr * wc;
-                    u.out_off = at + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
-                    units.push_back(u);
-                }
-            max_nt = std::max(max_nt, k.end - k.start);
-            n_bulk += cells;
-        });
-        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || consts.size() > 0xfffffff0ull) return DCDF_ERR_CAPACITY;
-    }
-    if (stats) {
-        stats[0] = n_bulk;
-        stats[1] = n_walk;
-        stats[2] = n_const;
-    }
-    if (W.total == 0) return DCDF_OK;
-    // few units: a unit's instants in several workgroups (bulk_parts; each decodes its Snapshot again)
-    const uint32_t parts = bulk_parts(units.size(), max_nt, bulk_wanted_units());
-    if (parts > 1) {
-        std::vector<BulkUnit> split;
-        split.reserve(units.size() * parts);
-        for (const BulkUnit& u : units) {
-            const uint32_t nt = u.t1 - u.t0, np = bulk_parts(units.size(), nt, bulk_wanted_units());
-            for (uint32_t j = 0; j < np; j++) {
-                BulkUnit v = u;
-                v.t0 = bulk_part(u.t0, nt, np, j);
-                v.t1 = bulk_part(u.t0, nt, np, j + 1);
-                v.out_off = u.out_off + (uint64_t)(v.t0 - u.t0) * u.out_st;
-                if (v.t1 > v.t0) split.push_back(v);
-            }
-        }
-        units.swap(split);
-    }
-    DevBuf d_units, d_consts;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
-    void* const d_out = W.dst();
-    if (!units.empty()) {
-        K2R_HIP(d_units.alloc_pooled(units.size() * sizeof(BulkUnit)));
-        K2R_HIP(hipMemcpy(d_units.p, units.data(), units.size() * sizeof(BulkUnit), hipMemcpyHostToDevice));
-    }
-    if (!consts.empty()) {
-        K2R_HIP(d_consts.alloc_pooled(consts.size() * sizeof(ConstPiece)));
-        K2R_HIP(hipMemcpy(d_consts.p, consts.data(), consts.size() * sizeof(ConstPiece), hipMemcpyHostToDevice));
-    }
-    DevBuf d_items;
-    if (!items.empty()) {
-        K2R_HIP(d_items.alloc_pooled(items.size() * sizeof(WinItem)));
-        K2R_HIP(hipMemcpy(d_items.p, items.data(), items.size() * sizeof(WinItem), hipMemcpyHostToDevice));
-    }
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
-    if (!consts.empty()) {
-        hipLaunchKernelGGL(k_raster_fill_const, dim3((uint32_t)std::min<uint64_t>(consts.size(), 256u * 64u)), dim3(256), 0, 0, d_consts.as<ConstPiece>(),
-                           (uint32_t)consts.size(), r->d_leaf.as<RasterLeaf>(), r->d_vals.as<int64_t>(), r->cs, d_out, out_dtype);
-        K2R_HIP(hipGetLastError());
-    }
-    const int rcb = launch_bulk_decode(r->d_refs.as<ChunkRef>(), d_units.as<BulkUnit>(), (uint32_t)units.size(), d_out, out_dtype);
-    if (rcb != DCDF_OK) return rcb;
-    if (!items.empty()) {
-        const int rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>(), (uint32_t)items.size(), d_out, out_dtype, nullptr, ev.e1, r->all_node,
-                                               r->all_narrow);
-        if (rc != DCDF_OK) return rc;
-    } else {
-        K2R_HIP(hipEventRecord(ev.e1, 0));
-        K2R_HIP(hipDeviceSynchronize());
-    }
-    const int rcf = W.finish();
-    if (rcf != DCDF_OK) return rcf;
-    float ms = 0.f;
-    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    if (kernel_ms) *kernel_ms = ms;
-    return DCDF_OK;
-}
-// ---- reduce over time: per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h) --------------------
-// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  What keeps the sum's order: within a
-// time segment every cell of a cube lies in exactly one piece (raster_pieces), so the work of one segment never shares a cell;
-// the segments are launched one after the other, in ascending order, on the null stream, and each piece continues the running
-// sum its cells' state plane holds.  The state planes are the output planes themselves (cube q's requested planes in ascending
-// bit order); SUM / COUNT kept for MEAN alone live in scratch planes.
-//
-// Pieces on chunks the bulk kernel does not take are decoded by the window walk as stored integers (DCDF_I64: store_typed
-// leaves n as it is) into a slab of a bounded number of cells, then folded by k_reduce_fold, which applies the leaf's own
-// encoding (reduce_widen: the conversions of store_typed, so the value is the typed fill_window's) -- one walk launch per slab
-// whatever mix of encodings its chunks have.  Elided pieces are folded by the same kernel straight from dcdf_raster::d_vals.
-__global__ void __launch_bounds__(256)
-k_reduce_fold(const FoldPiece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, double* dst,
-              double* scr, uint32_t ops) {
-    const uint32_t live = reduce_live(ops);
-    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-        const FoldPiece P = ps[p];
-        const uint64_t cells = (uint64_t)P.rows * P.cols;
-        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
-            const uint64_t at = e / P.cols * P.sr + e % P.cols;
-            double s = 0.0, c = 0.0, lo = __builtin_nan(""), hi = __builtin_nan("");
-            if (!P.init) {
-                if (live & RA_MIN) lo = p_min[at];
-                if (live & RA_MAX) hi = p_max[at];
-                if (live & RA_SUM) s = p_sum[at];
-                if (live & RA_COUNT) c = p_cnt[at];
-            }
-            for (uint32_t t = 0; t < P.nt; t++) {
-                const double x = reduce_widen(P.enc, P.fbits, P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e]);
-                if (x == x) {
-                    s = s + x;
-                    c = c + 1.0;
-                    lo = fmin(lo, x);
-                    hi = fmax(hi, x);
-                }
-            }
-            if (live & RA_MIN) p_min[at] = lo;
-            if (live & RA_MAX) p_max[at] = hi;
-            if (live & RA_SUM) p_sum[at] = s;
-            if (live & RA_COUNT) p_cnt[at] = c;
-        }
-    }
-}
-// the finishing kernel: MEAN = SUM / COUNT, NaN where nothing was counted
-__global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
-    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
-        const MeanPiece P = ps[p];
-        const double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        const double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_mean = dst + P.o_off + (uint64_t)popc32(ops & RA_ALL) * P.psz;
-        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) {
-            const double c = p_cnt[e];
-            p_mean[e] = c == 0.0 ? __builtin_nan("") : p_sum[e] / c;
-        }
-    }
-}
-// cells of one fallback slab (K2R_REDUCE_SLAB_CELLS overrides: tests of the slab cut)
-static uint64_t reduce_slab_cells() {
-    const char* e = std::getenv("K2R_REDUCE_SLAB_CELLS");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (uint64_t)1 << 22;
-}
-static int launch_reduce_fold(const FoldPiece* d_ps, uint32_t n, const int64_t* d_slab, const int64_t* d_vals, double* d_dst, double* d_scr,
-                              uint32_t ops) {
-    if (n == 0) return DCDF_OK;
-    hipLaunchKernelGGL(k_reduce_fold, dim3(std::min<uint32_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, n, d_slab, d_vals, d_dst, d_scr, ops);
-    K2R_HIP(hipGetLastError());
-    return DCDF_OK;
-}
-extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
-                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || ops == 0 || ops > (RA_ALL | ROP_MEAN) ||
-        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE))
-        return DCDF_ERR_BAD_ARG;
-    if (!r->all_wave) return DCDF_ERR_UNSUPPORTED;
-    if (stats) stats[0] = stats[1] = stats[2] = 0;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (nq == 0) return DCDF_OK;
-    const uint32_t live = reduce_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
-    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
-    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
-    std::vector<uint64_t> sbase(nq, 0);
-    uint64_t scr_total = 0;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
-        if (cube_cells(c) == 0) continue;
-        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
-        sbase[q] = scr_total;
-        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
-    }
-    WindowOut W(planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
-    // the plan, segment by segment
-    struct WalkPiece {  // a piece for the window walk: chunk, chunk-level cube, and its fold without the slab offset
-        uint32_t chunk;
-        dcdf_cube k;
-        FoldPiece f;
-    };
-    struct Segment {
-        std::vector<ReduceUnit> units;
-        std::vector<FoldPiece> consts;
-        std::vector<WalkPiece> walks;
-    };
-    std::vector<Segment> segs(r->nseg);
-    std::vector<MeanPiece> means;
-    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
-        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
-        means.push_back(MeanPiece{W.base[q], sbase[q], wr * wc});
-        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
-            Segment& S = segs[t0 / r->cs];
-            const uint64_t in_plane = (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
-            const uint32_t init = t0 + l.start == c.start;
-            const uint64_t cells = cube_cells(l);
-            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
-            FoldPiece p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, init, f.enc, f.fbits, 1u,
-                        (uint64_t)cid * r->cs + l.start, W.base[q] + in_plane, sbase[q] + in_plane, wr * wc};
-            if (f.elided) {
-                S.consts.push_back(p);
-                n_const += cells;
-                return;
-            }
-            const dcdf_chunk* h = r->chunks[cid];
-            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
-            if (!(h->top_g && h->narrow32)) {
-                p.enc = h->encoding;
-                p.fbits = h->fbits;
-                p.elided = 0;
-                S.walks.push_back(WalkPiece{cid, k, p});
-                n_walk += cells;
-                return;
-            }
-            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
-                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
-                    ReduceUnit u{};
-                    u.chunk = cid;
-                    u.t0 = k.start;
-                    u.t1 = k.end;
-                    u.rr = (uint16_t)rr;
-                    u.rc = (uint16_t)rc;
-                    u.top = (uint16_t)std::max(rr, k.top);
-                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
-                    u.left = (uint16_t)std::max(rc, k.left);
-                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
-                    u.sr = (uint32_t)wc;
-                    u.init = init;
-                    const uint64_t in_piece = (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
-                    u.o_off = p.o_off + in_piece;
-                    u.s_off = p.s_off + in_piece;
-                    u.psz = wr * wc;
-                    S.units.push_back(u);
-                }
-            n_bulk += cells;
-        });
-    }
-    if (stats) {
-        stats[0] = n_bulk;
-        stats[1] = n_walk;
-        stats[2] = n_const;
-    }
-    if (W.total == 0) return DCDF_OK;
-    // One upload of every segment's work.  The window walk's pieces are cut into slabs here: a slab holds whole pieces up to the
-    // cell bound; a piece beyond it is cut in time, each part a slab of its own (two parts of one piece share their cells, so
-    // they must not be folded by the same launch).
-    struct Slab {
-        size_t item0, item1, fold0, fold1;
-    };
-    struct SegRange {
-        size_t unit0, unit1, const0, const1, slab0, slab1;
-    };
-    std::vector<ReduceUnit> units;
-    std::vector<FoldPiece> folds;
-    std::vector<WinItem> items;
-    std::vector<Slab> slabs;
-    std::vector<SegRange> ranges;
-    const uint64_t slab_cap = reduce_slab_cells();
-    uint64_t slab_max = 0;
-    for (Segment& S : segs) {
-        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
-        SegRange g{units.size(), 0, folds.size(), 0, slabs.size(), 0};
-        units.insert(units.end(), S.units.begin(), S.units.end());
-        folds.insert(folds.end(), S.consts.begin(), S.consts.end());
-        g.unit1 = units.size();
-        g.const1 = folds.size();
-        Slab cur{items.size(), 0, folds.size(), 0};
-        uint64_t used = 0;
-        auto flush = [&] {
-            cur.item1 = items.size();
-            cur.fold1 = folds.size();
-            if (cur.fold1 > cur.fold0) slabs.push_back(cur);
-            slab_max = std::max(slab_max, used);
-            cur = Slab{items.size(), 0, folds.size(), 0};
-            used = 0;
-        };
-        for (const WalkPiece& w : S.walks) {
-            const uint64_t plane = (uint64_t)w.f.rows * w.f.cols;
-            const uint32_t nt = w.f.nt, step = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, slab_cap / plane));
-            if (step < nt || used + (uint64_t)nt * plane > slab_cap) flush();
-            for (uint32_t a = 0; a < nt; a += step) {
-                const uint32_t b = std::min(nt, a + step);
-                dcdf_cube k = w.k;
-                k.start = w.k.start + a;
-                k.end = w.k.start + b;
-                FoldPiece f = w.f;
-                f.nt = b - a;
-                f.init = w.f.init && a == 0;
-                f.src = used;
-                window_items(w.chunk, k, used, items, r->all_node);
-                folds.push_back(f);
-                used += (uint64_t)(b - a) * plane;
-                if (step < nt) flush();
-            }
-        }
-        flush();
-        g.slab1 = slabs.size();
-        ranges.push_back(g);
-        S = Segment{};
-        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || folds.size() > 0xfffffff0ull) return DCDF_ERR_CAPACITY;
-    }
-    DevBuf d_units, d_folds, d_items, d_means, d_slab, d_scr;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
-    double* const d_dst = (double*)W.dst();
-    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(double)));
-    if (!units.empty()) K2R_HIP(upload(d_units, units));
-    if (!folds.empty()) K2R_HIP(upload(d_folds, folds));
-    if (!items.empty()) K2R_HIP(upload(d_items, items));
-    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
-    if (ops & ROP_MEAN) K2R_HIP(upload(d_means, means));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
-    for (const SegRange& g : ranges) {
-        int rc = launch_reduce_fold(d_folds.as<FoldPiece>() + g.const0, (uint32_t)(g.const1 - g.const0), nullptr, r->d_vals.as<int64_t>(), d_dst,
-                                    d_scr.as<double>(), ops);
-        if (rc != DCDF_OK) return rc;
-        rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                d_dst, d_scr.as<double>(), ops);
-        if (rc != DCDF_OK) return rc;
-        for (size_t s = g.slab0; s < g.slab1; s++) {
-            const Slab& b = slabs[s];
-            rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), d_slab.p, DCDF_I64, nullptr,
-                                         nullptr, r->all_node, r->all_narrow);
-            if (rc != DCDF_OK) return rc;
-            rc = launch_reduce_fold(d_folds.as<FoldPiece>() + b.fold0, (uint32_t)(b.fold1 - b.fold0), d_slab.as<int64_t>(), nullptr, d_dst,
-                                    d_scr.as<double>(), ops);
-            if (rc != DCDF_OK) return rc;
-        }
-    }
-    if (ops & ROP_MEAN) {
-        uint64_t big = 0;
-        for (const MeanPiece& m : means) big = std::max(big, m.psz);
-        hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)),
-                           dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)means.size(), d_dst, d_scr.as<double>(), ops);
-        K2R_HIP(hipGetLastError());
-    }
-    K2R_HIP(hipEventRecord(ev.e1, 0));
-    K2R_HIP(hipDeviceSynchronize());
-    const int rcf = W.finish();
-    if (rcf != DCDF_OK) return rcf;
-    float ms = 0.f;
-    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    if (kernel_ms) *kernel_ms = ms;
-    return DCDF_OK;
-}
-// ---- reduce over space: per-instant min / max / sum / count / mean of the selected cells of a cube (k2r_space.h) ------------
-// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  Every piece -- a 64 x 64 unit of the bulk
-// kernel, a piece of the window walk, an elided piece -- leaves one SpacePartial per instant in a pooled scratch array; the
-// pieces of one (cube, segment) share their instants, so their records form one block [slot][instant] that k_space_finish folds
-// into the cube's series.  Instants are independent: one launch of each kind takes the work of all segments and cubes.
-//
-// 128-bit sums and the extremes of one wave's lanes into lane 0 .. and of a workgroup's four waves into thread 0 (LDS)
-struct SpaceAcc {
-    uint64_t hi, lo;
-    double mn, mx;
-    uint32_t cnt;
-};
-__device__ __forceinline__ void space_block_fold(SpaceAcc& a, SpaceAcc* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t bh = (uint64_t)__shfl_xor((unsigned long long)a.hi, off), bl = (uint64_t)__shfl_xor((unsigned long long)a.lo, off);
-        space_add128(a.hi, a.lo, bh, bl);
-        a.cnt += __shfl_xor(a.cnt, off);
-        a.mn = fmin(a.mn, __shfl_xor(a.mn, off));
-        a.mx = fmax(a.mx, __shfl_xor(a.mx, off));
-    }
-    __syncthreads();  // (the previous round's reader is done)
-    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (uint32_t w = 1; w < 4u; w++) {
-            space_add128(a.hi, a.lo, sh[w].hi, sh[w].lo);
-            a.cnt += sh[w].cnt;
-            a.mn = fmin(a.mn, sh[w].mn);
-            a.mx = fmax(a.mx, sh[w].mx);
-        }
-}
-__device__ __forceinline__ void space_store(SpacePartial* recs, uint64_t at, const SpaceAcc& a, uint32_t scale) {
-    __attribute__((address_space(1))) SpacePartial* const o = (__attribute__((address_space(1))) SpacePartial*)recs + at;
-    o->hi = a.hi;
-    o->lo = a.lo;
-    o->mn = a.mn;
-    o->mx = a.mx;
-    o->cnt = a.cnt;
-    o->scale = scale;
-}
-// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding,
-// masked cells skipped.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per instant
-// writes value x count.
-__global__ void __launch_bounds__(256)
-k_space_fold(const SpaceFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
-             const uint8_t* __restrict__ mask, SpacePartial* __restrict__ recs) {
-    __shared__ SpaceAcc sh[4];
-    __shared__ uint32_t sh_sel;
-    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-        const SpaceFold P = ps[p];
-        const uint64_t cells = (uint64_t)P.rows * P.cols;
-        const uint32_t scale = space_scale(P.enc, P.fbits);
-        if (P.elided) {
-            if (blockIdx.y != 0) continue;
-            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
-            if (mask) {
-                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) a.cnt += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
-            } else if (threadIdx.x == 0) {
-                a.cnt = (uint32_t)cells;
-            }
-            space_block_fold(a, sh);
-            if (threadIdx.x == 0) sh_sel = a.cnt;
-            __syncthreads();
-            const uint32_t selected = sh_sel;
-            for (uint32_t t = threadIdx.x; t < P.nt; t += blockDim.x) {
-                const int64_t v = vals[P.src + t];
-                const double x = reduce_widen(P.enc, P.fbits, v);
-                SpaceAcc o{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
-                if (x == x && selected) {
-                    space_mul_m(o.hi, o.lo, space_m(P.enc, v), selected);
-                    o.cnt = selected;
-                    o.mn = o.mx = x;
-                }
-                space_store(recs, P.rec + t, o, scale);
-            }
-            continue;
-        }
-        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
-            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
-            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
-                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
-                const int64_t v = slab[P.src + (uint64_t)t * cells + e];
-                const double x = reduce_widen(P.enc, P.fbits, v);
-                if (x == x) {
-                    space_add_m(a.hi, a.lo, space_m(P.enc, v));
-                    a.cnt += 1u;
-                    a.mn = fmin(a.mn, x);
-                    a.mx = fmax(a.mx, x);
-                }
-            }
-            space_block_fold(a, sh);
-            if (threadIdx.x == 0) space_store(recs, P.rec + t, a, scale);
-        }
-    }
-}
-// A workgroup per (job, instant): the records of the pieces that cover the instant, their sums at the common 2^-63 scale added
-// in 192 bits, then the requested series -- SUM by one conversion of that integer, MEAN by one division.
-__global__ void __launch_bounds__(256)
-k_space_finish(const SpaceJob* __restrict__ jobs, uint32_t n, const SpacePartial* __restrict__ recs, double* dst, uint32_t ops) {
-    __shared__ U192 sh_s[4];
-    __shared__ uint64_t sh_c[4];
-    __shared__ double sh_mn[4], sh_mx[4];
-    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
-        const SpaceJob J = jobs[j];
-        for (uint32_t t = blockIdx.y; t < J.nt; t += gridDim.y) {
-            U192 acc{0, 0, 0};
-            uint64_t cnt = 0;
-            double mn = __builtin_nan(""), mx = __builtin_nan("");
-            for (uint32_t s = threadIdx.x; s < J.n_slots; s += blockDim.x) {
-                const __attribute__((address_space(1))) SpacePartial* const R =
-                    (const __attribute__((address_space(1))) SpacePartial*)recs + (J.rec + (uint64_t)s * J.nt + t);
-                u192_add(acc, space_scaled(R->hi, R->lo, R->scale));
-                cnt += R->cnt;
-                mn = fmin(mn, R->mn);
-                mx = fmax(mx, R->mx);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                U192 b;
-                b.w0 = (uint64_t)__shfl_xor((unsigned long long)acc.w0, off);
-                b.w1 = (uint64_t)__shfl_xor((unsigned long long)acc.w1, off);
-                b.w2 = (uint64_t)__shfl_xor((unsigned long long)acc.w2, off);
-                u192_add(acc, b);
-                cnt += (uint64_t)__shfl_xor((unsigned long long)cnt, off);
-                mn = fmin(mn, __shfl_xor(mn, off));
-                mx = fmax(mx, __shfl_xor(mx, off));
-            }
-            __syncthreads();  // (the previous round's reader is done)
-            if ((threadIdx.x & 63u) == 0) {
-                sh_s[threadIdx.x >> 6] = acc;
-                sh_c[threadIdx.x >> 6] = cnt;
-                sh_mn[threadIdx.x >> 6] = mn;
-                sh_mx[threadIdx.x >> 6] = mx;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t w = 1; w < 4u; w++) {
-                    u192_add(acc, sh_s[w]);
-                    cnt += sh_c[w];
-                    mn = fmin(mn, sh_mn[w]);
-                    mx = fmax(mx, sh_mx[w]);
-                }
-                const double sum = space_round(acc);
-                __attribute__((address_space(1))) double* o = (__attribute__((address_space(1))) double*)dst + (J.o_off + t);
-                if (ops & RA_MIN) { *o = mn == mn ? mn : __builtin_nan(""); o += J.o_stride; }
-                if (ops & RA_MAX) { *o = mx == mx ? mx : __builtin_nan(""); o += J.o_stride; }
-                if (ops & RA_SUM) { *o = sum; o += J.o_stride; }
-                if (ops & RA_COUNT) { *o = (double)cnt; o += J.o_stride; }
-                if (ops & ROP_MEAN) *o = cnt == 0 ? __builtin_nan("") : sum / (double)cnt;
-            }
-        }
-    }
-}
-// records of one batch of the plan (K2R_SPACE_RECORDS overrides: tests of the batch cut); 40 bytes each
-static uint64_t space_record_cap() {
-    const char* e = std::getenv("K2R_SPACE_RECORDS");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (uint64_t)6 << 20;
-}
-extern "C" int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum) {
-    if ((n && (!hi || !lo || !scale)) || !sum) return DCDF_ERR_BAD_ARG;
-    U192 acc{0, 0, 0};
-    for (size_t i = 0; i < n; i++) {
-        if ((scale[i] & 255u) > 63u || scale[i] > (SPACE_NEG | 63u)) return DCDF_ERR_BAD_ARG;
-        u192_add(acc, space_scaled(hi[i], lo[i], scale[i]));
-    }
-    *sum = space_round(acc);
-    return DCDF_OK;
-}
-// the host masks of the cubes that have instants, one after the other in a pooled device buffer: cube q's at moff[q]
-static int stage_cube_masks(const dcdf_cube* cubes, size_t nq, const uint8_t* mask, const uint64_t* mask_offset, const std::vector<uint64_t>& moff,
-                            uint64_t mask_total, DevBuf& d_mask) {
-    K2R_HIP(d_mask.alloc_pooled(mask_total));
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-        if (c.end == c.start || bytes == 0) continue;
-        K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], mask + mask_offset[q], bytes, hipMemcpyHostToDevice));
-    }
-    return DCDF_OK;
-}
-extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint8_t* mask,
-                                              const uint64_t* mask_offset, int mask_mem, double* out, int out_mem, const uint64_t* out_offset,
-                                              uint64_t stats[3], float* kernel_ms) {
-    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || ops == 0 || ops > (RA_ALL | ROP_MEAN) ||
-        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) || (mask && !mask_offset) ||
-        (mask && mask_mem != DCDF_MEM_HOST && mask_mem != DCDF_MEM_DEVICE))
-        return DCDF_ERR_BAD_ARG;
-    if (!r->all_wave || r->bad_fbits) return DCDF_ERR_UNSUPPORTED;
-    if (stats) stats[0] = stats[1] = stats[2] = 0;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (nq == 0) return DCDF_OK;
-    const uint32_t live = reduce_live(ops), n_out = popc32(ops);
-    // where the series go: cube q's are n_out "instants" of one row of [instants] to WindowOut; where its mask bytes are
-    std::vector<dcdf_cube> series(nq, dcdf_cube{});
-    std::vector<uint64_t> moff(nq, 0);
-    uint64_t mask_total = 0;
-    const bool stage_mask = mask && mask_mem == DCDF_MEM_HOST;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
-        if (c.end == c.start) continue;
-        series[q] = dcdf_cube{0, n_out, 0, 1, 0, c.end - c.start};
-        if (mask) {
-            moff[q] = stage_mask ? mask_total : mask_offset[q];
-            mask_total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-        }
-    }
-    WindowOut W(series.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
-    // the plan: batches of jobs whose records share the scratch, one after the other
-    struct Slab {
-        size_t item0, item1, fold0, fold1;
-    };
-    struct Batch {
-        size_t unit0, unit1, const0, const1, slab0, slab1, job0, job1;
-        uint32_t unit_nt, job_nt;  // the longest unit / job
-    };
-    std::vector<SpaceUnit> units;
-    std::vector<SpaceFold> cfolds, wfolds;
-    std::vector<WinItem> items;
-    std::vector<Slab> slabs;
-    std::vector<SpaceJob> jobs;
-    std::vector<Batch> batches;
-    const uint64_t rec_cap = space_record_cap(), slab_cap = reduce_slab_cells();
-    uint64_t rec_used = 0, rec_max = 0, slab_used = 0, slab_max = 0, fold_nt = 1;
-    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
-    Batch cur{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    Slab cur_slab{0, 0, 0, 0};
-    auto flush_slab = [&] {
-        cur_slab.item1 = items.size();
-        cur_slab.fold1 = wfolds.size();
-        if (cur_slab.fold1 > cur_slab.fold0) slabs.push_back(cur_slab);
-        slab_max = std::max(slab_max, slab_used);
-        cur_slab = Slab{items.size(), 0, wfolds.size(), 0};
-        slab_used = 0;
-    };
-    auto flush_batch = [&] {
-        flush_slab();
-        // few units: a unit's instants in several workgroups (bulk_parts); each part writes its own instants' records
-        const size_t nu = units.size() - cur.unit0;
-        if (bulk_parts(nu, cur.unit_nt, bulk_wanted_units()) > 1) {
-            std::vector<SpaceUnit> split;
-            for (size_t i = cur.unit0; i < units.size(); i++) {
-                const SpaceUnit& u = units[i];
-                const uint32_t nt = u.t1 - u.t0, np = bulk_parts(nu, nt, bulk_wanted_units());
-                for (uint32_t j = 0; j < np; j++) {
-                    SpaceUnit v = u;
-                    v.t0 = bulk_part(u.t0, nt, np, j);
-                    v.t1 = bulk_part(u.t0, nt, np, j + 1);
-                    v.rec = u.rec + (v.t0 - u.t0);
-                    if (v.t1 > v.t0) split.push_back(v);
-                }
-            }
-            units.resize(cur.unit0);
-            units.insert(units.end(), split.begin(), split.end());
-        }
-        cur.unit1 = units.size();
-        cur.const1 = cfolds.size();
-        cur.slab1 = slabs.size();
-        cur.job1 = jobs.size();
-        if (cur.job1 > cur.job0) batches.push_back(cur);
-        rec_max = std::max(rec_max, rec_used);
-        rec_used = 0;
-        cur = Batch{units.size(), 0, cfolds.size(), 0, slabs.size(), 0, jobs.size(), 0, 0, 0};
-    };
-    struct WalkPiece {  // a piece for the window walk: chunk, chunk-level cube, and its fold without slab offset and record
-        uint32_t chunk;
-        dcdf_cube k;
-        SpaceFold f;
-    };
-    std::vector<SpaceUnit> tu;
-    std::vector<SpaceFold> tc;
-    std::vector<WalkPiece> tw;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (c.end == c.start) continue;
-        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
-        for (uint32_t seg = c.start / r->cs; seg <= (c.end - 1) / r->cs; seg++) {
-            const uint32_t s0 = seg * r->cs, ls = std::max(c.start, s0), le = std::min(c.end, s0 + r->cs);  // the cube's instants of this segment
-            tu.clear();
-            tc.clear();
-            tw.clear();
-            if (wr * wc)
-                raster_pieces(r, dcdf_cube{ls, le, c.top, c.bottom, c.left, c.right}, [&](uint32_t cid, const dcdf_cube& l, uint32_t, uint32_t r0, uint32_t c0) {
-                    const uint64_t m_off = moff[q] + (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
-                    const uint64_t cells = cube_cells(l);
-                    const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
-                    SpaceFold p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, f.enc, f.fbits, 1u, 0u,
-                                (uint64_t)cid * r->cs + l.start, 0, m_off};
-                    if (f.elided) {
-                        tc.push_back(p);
-                        n_const += cells;
-                        return;
-                    }
-                    const dcdf_chunk* h = r->chunks[cid];
-                    const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
-                    if (!(h->top_g && h->narrow32)) {
-                        p.enc = h->encoding;
-                        p.fbits = h->fbits;
-                        p.elided = 0;
-                        tw.push_back(WalkPiece{cid, k, p});
-                        n_walk += cells;
-                        return;
-                    }
-                    for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
-                        for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
-                            SpaceUnit u{};
-                            u.chunk = cid;
-                            u.t0 = k.start;
-                            u.t1 = k.end;
-                            u.rr = (uint16_t)rr;
-                            u.rc = (uint16_t)rc;
-                            u.top = (uint16_t)std::max(rr, k.top);
-                            u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
-                            u.left = (uint16_t)std::max(rc, k.left);
-                            u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
-                            u.m_sr = (uint32_t)wc;
-                            u.m_off = m_off + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
-                            tu.push_back(u);
-                        }
-                    n_bulk += cells;
-                });
-            // the segment's instants in jobs of at most rec_cap records (one job, but for a huge cube)
-            const uint64_t n_slots = tu.size() + tc.size() + tw.size();
-            const uint32_t nt = le - ls, step = n_slots ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, rec_cap / n_slots)) : nt;
-            for (uint32_t a = 0; a < nt; a += step) {
-                const uint32_t b = std::min(nt, a + step), jn = b - a;
-                if (rec_used && rec_used + n_slots * jn > rec_cap) flush_batch();
-                jobs.push_back(SpaceJob{rec_used, (uint32_t)n_slots, jn, W.base[q] + (ls + a - c.start), (uint64_t)(c.end - c.start)});
-                uint64_t rec = rec_used;
-                for (SpaceUnit u : tu) {
-                    u.t0 += a;
-                    u.t1 = u.t0 + jn;
-                    u.rec = rec;
-                    units.push_back(u);
-                    rec += jn;
-                }
-                if (!tu.empty()) cur.unit_nt = std::max(cur.unit_nt, jn);
-                for (SpaceFold p : tc) {
-                    p.src += a;
-                    p.nt = jn;
-                    p.rec = rec;
-                    cfolds.push_back(p);
-                    rec += jn;
-                }
-                for (const WalkPiece& w : tw) {  // into slabs: whole pieces up to the cell bound, a piece beyond it cut in time
-                    const uint64_t plane = (uint64_t)w.f.rows * w.f.cols;
-                    const uint32_t cut = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(jn, slab_cap / plane));
-                    if (cut < jn || slab_used + (uint64_t)jn * plane > slab_cap) flush_slab();
-                    for (uint32_t x = 0; x < jn; x += cut) {
-                        const uint32_t y = std::min(jn, x + cut);
-                        dcdf_cube k = w.k;
-                        k.start = w.k.start + a + x;
-                        k.end = w.k.start + a + y;
-                        SpaceFold p = w.f;
-                        p.nt = y - x;
-                        p.src = slab_used;
-                        p.rec = rec + x;
-                        window_items(w.chunk, k, slab_used, items, r->all_node);
-                        wfolds.push_back(p);
-                        fold_nt = std::max<uint64_t>(fold_nt, p.nt);
-                        slab_used += (uint64_t)(y - x) * plane;
-                        if (cut < jn) flush_slab();
-                    }
-                    rec += jn;
-                }
-                rec_used = rec;
-                cur.job_nt = std::max(cur.job_nt, jn);
-            }
-            if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || cfolds.size() + wfolds.size() > 0xfffffff0ull ||
-                jobs.size() > 0x7ffffff0ull)
-                return DCDF_ERR_CAPACITY;
-        }
-    }
-    flush_batch();
-    if (stats) {
-        stats[0] = n_bulk;
-        stats[1] = n_walk;
-        stats[2] = n_const;
-    }
-    if (W.total == 0) return DCDF_OK;
-    DevBuf d_units, d_cfolds, d_wfolds, d_items, d_jobs, d_slab, d_recs, d_mask;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
-    double* const d_dst = (double*)W.dst();
-    const uint8_t* p_mask = mask;
-    if (stage_mask) {
-        const int rcm = stage_cube_masks(cubes, nq, mask, mask_offset, moff, mask_total, d_mask);
-        if (rcm != DCDF_OK) return rcm;
-        p_mask = (const uint8_t*)d_mask.p;
-    }
-    K2R_HIP(d_recs.alloc_pooled(rec_max * sizeof(SpacePartial)));
-    if (!units.empty()) K2R_HIP(upload(d_units, units));
-    if (!cfolds.empty()) K2R_HIP(upload(d_cfolds, cfolds));
-    if (!wfolds.empty()) K2R_HIP(upload(d_wfolds, wfolds));
-    if (!items.empty()) K2R_HIP(upload(d_items, items));
-    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
-    K2R_HIP(upload(d_jobs, jobs));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
-    SpacePartial* const recs = d_recs.as<SpacePartial>();
-    for (const Batch& b : batches) {
-        if (b.const1 > b.const0) {
-            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
-                               d_cfolds.as<SpaceFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), p_mask, recs);
-            K2R_HIP(hipGetLastError());
-        }
-        int rc = launch_bulk_space(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<SpaceUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0),
-                                   p_mask, recs, live);
-        if (rc != DCDF_OK) return rc;
-        for (size_t s = b.slab0; s < b.slab1; s++) {
-            const Slab& sl = slabs[s];
-            rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + sl.item0, (uint32_t)(sl.item1 - sl.item0), d_slab.p, DCDF_I64, nullptr,
-                                         nullptr, r->all_node, r->all_narrow);
-            if (rc != DCDF_OK) return rc;
-            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), (uint32_t)std::min<uint64_t>(fold_nt, 1024)),
-                               dim3(256), 0, 0, d_wfolds.as<SpaceFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), d_slab.as<int64_t>(), nullptr,
-                               p_mask, recs);
-            K2R_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_space_finish, dim3((uint32_t)std::min<size_t>(b.job1 - b.job0, 1u << 20), std::min<uint32_t>(b.job_nt, 1024)), dim3(256), 0,
-                           0, d_jobs.as<SpaceJob>() + b.job0, (uint32_t)(b.job1 - b.job0), recs, d_dst, ops);
-        K2R_HIP(hipGetLastError());
-    }
-    K2R_HIP(hipEventRecord(ev.e1, 0));
-    K2R_HIP(hipDeviceSynchronize());
-    const int rcf = W.finish();
-    if (rcf != DCDF_OK) return rcf;
-    float ms = 0.f;
-    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    if (kernel_ms) *kernel_ms = ms;
-    return DCDF_OK;
-}
-// ---- value histograms: per instant, how many selected cells of a cube fall into every bin of shared edges (k2r_hist.h) -------
-// The pieces of every cube are classified as dcdf_raster_decode_batch classifies them.  Every piece -- a 64 x 64 unit of the bulk
-// kernel, a piece of the window walk, an elided piece -- adds its counts to the cube's own [instants][bins] array with
-// device-scope 64-bit atomic adds; the call zeroes exactly those arrays first.  Integer adds commute, so the work of all segments
-// and cubes goes into one launch of each kind and the result depends on no order.
-//
-// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding and
-// binned by the definition itself (hist_bin: the values here are wide, and the walk dominates), masked cells skipped, counts in
-// an LDS histogram first.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per
-// instant adds that count to the bin of the piece's value.
-__global__ void __launch_bounds__(256)
-k_hist_fold(const HistFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
-            const uint8_t* __restrict__ mask, const double* __restrict__ edges, uint32_t n_bins, uint64_t* out) {
-    __shared__ uint32_t sh_cnt[HIST_MAX_BINS];
-    __shared__ uint32_t sh_sel;
-    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-        const HistFold P = ps[p];
-        const uint64_t cells = (uint64_t)P.rows * P.cols;
-        if (P.elided) {
-            if (blockIdx.y != 0) continue;
-            __syncthreads();  // (the previous piece's readers are done)
-            if (threadIdx.x == 0) sh_sel = mask ? 0u : (uint32_t)cells;
-            __syncthreads();
-            if (mask) {
-                uint32_t c = 0;
-                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) c += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
-                if (c) atomicAdd(&sh_sel, c);
-                __syncthreads();
-            }
-            const uint32_t selected = sh_sel;
-            for (uint32_t t = threadIdx.x; t < P.nt && selected; t += blockDim.x) {
-                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, vals[P.src + t]));
-                if (b >= 0) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + (uint32_t)b), (unsigned long long)selected);
-            }
-            continue;
-        }
-        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
-            __syncthreads();  // (the previous round's readers are done)
-            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) sh_cnt[i] = 0u;
-            __syncthreads();
-            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
-                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
-                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, slab[P.src + (uint64_t)t * cells + e]));
-                if (b >= 0) atomicAdd(&sh_cnt[b], 1u);
-            }
-            __syncthreads();
-            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) {
-                const uint32_t c = sh_cnt[i];
-                if (c) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + i), (unsigned long long)c);
-            }
-        }
-    }
-}
-extern "C" int dcdf_histogram_bounds(int32_t encoding, uint32_t fractional_bits, const double* edges, uint32_t n_bins, int64_t* lo, int64_t* hi) {
-    if (!lo || !hi || !hist_edges_ok(edges, n_bins) || !hist_leaf_ok(encoding, fractional_bits)) return DCDF_ERR_BAD_ARG;
-    hist_intervals(encoding, fractional_bits, edges, n_bins, lo, hi);
-    return DCDF_OK;
-}
-extern "C" int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* edges, uint32_t n_bins,
-                                           const uint8_t* mask, const uint64_t* mask_offset, int mask_mem, uint64_t* out, int out_mem,
-                                           const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || !hist_edges_ok(edges, n_bins) ||
-        (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE) || (mask && !mask_offset) ||
-        (mask && mask_mem != DCDF_MEM_HOST && mask_mem != DCDF_MEM_DEVICE))
-        return DCDF_ERR_BAD_ARG;
-    if (!r->all_wave || r->bad_fbits) return DCDF_ERR_UNSUPPORTED;
-    if (stats) stats[0] = stats[1] = stats[2] = 0;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (nq == 0) return DCDF_OK;
-    // where the counts go: cube q's are "instants" of one row of [bins] to WindowOut; where its mask bytes are
-    std::vector<dcdf_cube> rows(nq, dcdf_cube{});
-    std::vector<uint64_t> moff(nq, 0);
-    uint64_t mask_total = 0;
-    const bool stage_mask = mask && mask_mem == DCDF_MEM_HOST;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
-        if (c.end == c.start) continue;
-        rows[q] = dcdf_cube{0, c.end - c.start, 0, 1, 0, n_bins};
-        if (mask) {
-            moff[q] = stage_mask ? mask_total : mask_offset[q];
-            mask_total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-        }
-    }
-    WindowOut W(rows.data(), nq, out, out_offset, sizeof(uint64_t), out_mem == DCDF_MEM_DEVICE);
-    // the thresholds of every distinct (encoding, fractional bits) among the bulk kernel's leaves: translated once, here
-    const uint32_t tab = (uint32_t)1 << hist_steps(n_bins);
-    std::map<std::pair<int32_t, uint32_t>, uint32_t> leaf_thr;
-    std::vector<int32_t> thr;
-    struct Slab {
-        size_t item0, item1, fold0, fold1;
-    };
-    std::vector<HistUnit> units;
-    std::vector<HistFold> cfolds, wfolds;
-    std::vector<WinItem> items;
-    std::vector<Slab> slabs;
-    const uint64_t slab_cap = reduce_slab_cells();
-    uint64_t slab_used = 0, slab_max = 0, fold_nt = 1;
-    uint64_t n_bulk = 0, n_walk = 0, n_const = 0;  // cells read
-    uint32_t max_nt = 0;
-    Slab cur_slab{0, 0, 0, 0};
-    auto flush_slab = [&] {
-        cur_slab.item1 = items.size();
-        cur_slab.fold1 = wfolds.size();
-        if (cur_slab.fold1 > cur_slab.fold0) slabs.push_back(cur_slab);
-        slab_max = std::max(slab_max, slab_used);
-        cur_slab = Slab{items.size(), 0, wfolds.size(), 0};
-        slab_used = 0;
-    };
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
-        if ((uint64_t)(c.end - c.start) * wr * wc == 0) continue;
-        raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
-            const uint64_t m_off = moff[q] + (uint64_t)(r0 + l.top - c.top) * wc + (c0 + l.left - c.left);
-            const uint64_t o_off = W.base[q] + (uint64_t)(t0 + l.start - c.start) * n_bins;
-            const uint64_t cells = cube_cells(l);
-            const RasterLeaf f = r->tiled ? r->leaves[cid] : RasterLeaf{};
-            HistFold p{l.end - l.start, l.bottom - l.top, l.right - l.left, (uint32_t)wc, f.enc, f.fbits, 1u, 0u,
-                       (uint64_t)cid * r->cs + l.start, o_off, m_off};
-            if (f.elided) {
-                cfolds.push_back(p);
-                n_const += cells;
-                return;
-            }
-            const dcdf_chunk* h = r->chunks[cid];
-            const dcdf_cube k{l.start, l.end, f.row0 + l.top, f.row0 + l.bottom, f.col0 + l.left, f.col0 + l.right};  // chunk coordinates
-            if (!(h->top_g && h->narrow32)) {  // into slabs: whole pieces up to the cell bound, a piece beyond it cut in time
-                p.enc = h->encoding;
-                p.fbits = h->fbits;
-                p.elided = 0;
-                const uint64_t plane = (uint64_t)p.rows * p.cols;
-                const uint32_t nt = p.nt, cut = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, slab_cap / plane));
-                if (cut < nt || slab_used + (uint64_t)nt * plane > slab_cap) flush_slab();
-                for (uint32_t x = 0; x < nt; x += cut) {
-                    const uint32_t y = std::min(nt, x + cut);
-                    dcdf_cube kk = k;
-                    kk.start = k.start + x;
-                    kk.end = k.start + y;
-                    HistFold w = p;
-                    w.nt = y - x;
-                    w.src = slab_used;
-                    w.o_off = o_off + (uint64_t)x * n_bins;
-                    window_items(cid, kk, slab_used, items, r->all_node);
-                    wfolds.push_back(w);
-                    fold_nt = std::max<uint64_t>(fold_nt, w.nt);
-                    slab_used += (uint64_t)(y - x) * plane;
-                    if (cut < nt) flush_slab();
-                }
-                n_walk += cells;
-                return;
-            }
-            const auto key = std::make_pair((int32_t)h->encoding, (uint32_t)h->fbits);
-            auto it = leaf_thr.find(key);
-            if (it == leaf_thr.end()) {
-                it = leaf_thr.emplace(key, (uint32_t)thr.size()).first;
-                thr.resize(thr.size() + tab);
-                hist_thresholds32(key.first, key.second, edges, n_bins, thr.data() + it->second, tab);
-            }
-            for (uint32_t rr = k.top & ~(BULK_REGION - 1); rr < k.bottom; rr += BULK_REGION)
-                for (uint32_t rc = k.left & ~(BULK_REGION - 1); rc < k.right; rc += BULK_REGION) {
-                    HistUnit u{};
-                    u.chunk = cid;
-                    u.t0 = k.start;
-                    u.t1 = k.end;
-                    u.rr = (uint16_t)rr;
-                    u.rc = (uint16_t)rc;
-                    u.top = (uint16_t)std::max(rr, k.top);
-                    u.bottom = (uint16_t)std::min(rr + BULK_REGION, k.bottom);
-                    u.left = (uint16_t)std::max(rc, k.left);
-                    u.right = (uint16_t)std::min(rc + BULK_REGION, k.right);
-                    u.m_sr = (uint32_t)wc;
-                    u.thr = it->second;
-                    u.rev = hist_reversed(key.first, key.second) ? 1u : 0u;
-                    u.o_off = o_off;
-                    u.m_off = m_off + (uint64_t)(u.top - k.top) * wc + (u.left - k.left);
-                    units.push_back(u);
-                }
-            max_nt = std::max(max_nt, k.end - k.start);
-            n_bulk += cells;
-        });
-        if (units.size() > 0x3fffffffull || items.size() > 0xfffffff0ull || cfolds.size() + wfolds.size() > 0xfffffff0ull ||
-            thr.size() > 0x7fffffffull)
-            return DCDF_ERR_CAPACITY;
-    }
-    flush_slab();
-    if (stats) {
-        stats[0] = n_bulk;
-        stats[1] = n_walk;
-        stats[2] = n_const;
-    }
-    if (W.total == 0) return DCDF_OK;
-    // few units: a unit's instants in several workgroups (bulk_parts); each part adds to its own instants' rows
-    if (bulk_parts(units.size(), max_nt, bulk_wanted_units()) > 1) {
-        std::vector<HistUnit> split;
-        split.reserve(units.size() * 2);
-        for (const HistUnit& u : units) {
-            const uint32_t nt = u.t1 - u.t0, np = bulk_parts(units.size(), nt, bulk_wanted_units());
-            for (uint32_t j = 0; j < np; j++) {
-                HistUnit v = u;
-                v.t0 = bulk_part(u.t0, nt, np, j);
-                v.t1 = bulk_part(u.t0, nt, np, j + 1);
-                v.o_off = u.o_off + (uint64_t)(v.t0 - u.t0) * n_bins;
-                if (v.t1 > v.t0) split.push_back(v);
-            }
-        }
-        units.swap(split);
-    }
-    DevBuf d_units, d_cfolds, d_wfolds, d_items, d_slab, d_mask, d_thr, d_edges;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
-    uint64_t* const d_dst = (uint64_t*)W.dst();
-    const uint8_t* p_mask = mask;
-    if (stage_mask) {
-        const int rcm = stage_cube_masks(cubes, nq, mask, mask_offset, moff, mask_total, d_mask);
-        if (rcm != DCDF_OK) return rcm;
-        p_mask = (const uint8_t*)d_mask.p;
-    }
-    if (!units.empty()) {
-        K2R_HIP(upload(d_units, units));
-        K2R_HIP(upload(d_thr, thr));
-    }
-    if (!cfolds.empty()) K2R_HIP(upload(d_cfolds, cfolds));
-    if (!wfolds.empty()) K2R_HIP(upload(d_wfolds, wfolds));
-    if (!items.empty()) K2R_HIP(upload(d_items, items));
-    if (slab_max) K2R_HIP(d_slab.alloc_pooled(slab_max * sizeof(int64_t)));
-    if (!cfolds.empty() || !wfolds.empty()) K2R_HIP(upload(d_edges, std::vector<double>(edges, edges + n_bins + 1)));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
-    // the accumulators: exactly the cubes' arrays, nothing between them
-    if (!W.to_dev) {
-        K2R_HIP(hipMemsetAsync(d_dst, 0, W.total * W.es, 0));
-    } else {
-        for (size_t q = 0; q < nq; q++) {
-            const uint64_t n = cube_cells(rows[q]);
-            if (n) K2R_HIP(hipMemsetAsync(d_dst + W.base[q], 0, n * sizeof(uint64_t), 0));
-        }
-    }
-    if (!cfolds.empty()) {
-        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(cfolds.size(), 1u << 20), 1), dim3(256), 0, 0, d_cfolds.as<HistFold>(),
-                           (uint32_t)cfolds.size(), nullptr, r->d_vals.as<int64_t>(), p_mask, d_edges.as<double>(), n_bins, d_dst);
-        K2R_HIP(hipGetLastError());
-    }
-    int rc = launch_bulk_hist(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<HistUnit>(), (uint32_t)units.size(), p_mask,
-                              d_thr.as<int32_t>(), n_bins, d_dst);
-    if (rc != DCDF_OK) return rc;
-    for (const Slab& sl : slabs) {
-        rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>() + sl.item0, (uint32_t)(sl.item1 - sl.item0), d_slab.p, DCDF_I64, nullptr,
-                                     nullptr, r->all_node, r->all_narrow);
-        if (rc != DCDF_OK) return rc;
-        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), (uint32_t)std::min<uint64_t>(fold_nt, 1024)),
-                           dim3(256), 0, 0, d_wfolds.as<HistFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), d_slab.as<int64_t>(), nullptr,
-                           p_mask, d_edges.as<double>(), n_bins, d_dst);
-        K2R_HIP(hipGetLastError());
-    }
-    K2R_HIP(hipEventRecord(ev.e1, 0));
-    K2R_HIP(hipDeviceSynchronize());
-    const int rcf = W.finish();
-    if (rcf != DCDF_OK) return rcf;
-    float ms = 0.f;
-    K2R_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    if (kernel_ms) *kernel_ms = ms;
-    return DCDF_OK;
+    return batch_epilogue(W, ev, r->tiled && n_items == 0, kernel_ms);
 }
 // ---- search of dataset-level cubes with everything but a count per cube on the device ---------------------------------
 // One thread per cube writes what search_impl builds on the host: a WinQuery per chunk-level piece (with the chunk's origin
@@ -1974,7 +824,7 @@ static int raster_search(const dcdf_raster* r, const dcdf_cube* cubes, const int
         const dcdf_cube c = norm_cube(cubes[q]);
         if (c.end > r->T || c.bottom > r->R || c.right > r->C) return DCDF_ERR_BOUNDS;
         if (cube_cells(c) != 0)
-            raster_pieces(r, c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
+            raster_pieces(r->plan(), c, [&](uint32_t cid, const dcdf_cube& l, uint32_t t0, uint32_t r0, uint32_t c0) {
                 sch.push_back(r->chunks[cid]);
                 scid.push_back(cid);
                 scube.push_back(l);

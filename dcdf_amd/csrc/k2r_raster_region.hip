@@ -1,0 +1,588 @@
+// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, reduce
+// over space, histogram -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// are the arguments, the uploads and the launches.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "k2r_raster_host.h"
+
+using namespace k2r;
+
+// ---- what the four calls share -----------------------------------------------------------------------------------------------
+// Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
+// error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
+enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
+static int region_begin(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const void* out, const uint64_t* out_offset, int out_mem,
+                        bool own_args_ok, RegionFloats floats, uint64_t stats[3], float* kernel_ms) {
+    if (!r || !cubes || !out || !out_offset || nq > 0x7fffffffu || !own_args_ok || (out_mem != DCDF_MEM_HOST && out_mem != DCDF_MEM_DEVICE))
+        return DCDF_ERR_BAD_ARG;
+    if (!r->all_wave || (floats == EXACT_FLOATS && r->bad_fbits)) return DCDF_ERR_UNSUPPORTED;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (kernel_ms) *kernel_ms = 0.f;
+    return plan_bounds(r->plan(), cubes, nq);
+}
+static void put_stats(uint64_t stats[3], const uint64_t cells[3]) {
+    if (stats)
+        for (int i = 0; i < 3; i++) stats[i] = cells[i];
+}
+template <class T>
+static int upload_some(DevBuf& d, const std::vector<T>& v) {
+    if (!v.empty()) K2R_HIP(upload(d, v));
+    return DCDF_OK;
+}
+// cells of one fallback slab (K2R_REDUCE_SLAB_CELLS overrides: tests of the slab cut)
+static uint64_t reduce_slab_cells() {
+    const char* e = std::getenv("K2R_REDUCE_SLAB_CELLS");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : (uint64_t)1 << 22;
+}
+// the window walk's share of a plan on the device: its items, its folds, and the slab both kinds of launch meet in
+struct WalkDev {
+    DevBuf items, folds, slab;
+    template <class Fold>
+    int upload(const SlabCutter<Fold>& w) {
+        int rc = upload_some(items, w.items);
+        if (rc == DCDF_OK) rc = upload_some(folds, w.folds);
+        if (rc == DCDF_OK && w.slab_max) K2R_HIP(slab.alloc_pooled(w.slab_max * sizeof(int64_t)));
+        return rc;
+    }
+    // the slabs [s0, s1) one after the other: the walk decodes a slab's items as stored integers (DCDF_I64: store_typed leaves n
+    // as it is) -- one launch whatever mix of encodings its chunks have --, then fold(slab) launches the call's fold kernel
+    template <class F>
+    int run(const dcdf_raster* r, const std::vector<Slab>& slabs, size_t s0, size_t s1, F&& fold) const {
+        for (size_t s = s0; s < s1; s++) {
+            const Slab& b = slabs[s];
+            const int rc = launch_window_items_dev(r->d_refs, items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), slab.p, DCDF_I64, nullptr,
+                                                   nullptr, r->all_node, r->all_narrow);
+            if (rc != DCDF_OK) return rc;
+            fold(b);
+            K2R_HIP(hipGetLastError());
+        }
+        return DCDF_OK;
+    }
+};
+// The masks of reduce_space and histogram: cube q's bytes start at p[moff[q]] -- in the caller's device array, or in a pooled copy
+// of the host masks of the cubes that have instants, one after the other (stage()).
+struct CubeMasks {
+    std::vector<uint64_t> moff;
+    uint64_t total = 0;
+    const uint8_t* p;
+    bool host;
+    DevBuf d_mask;
+    static bool args_ok(const uint8_t* mask, const uint64_t* mask_offset, int mask_mem) {
+        return !mask || (mask_offset && (mask_mem == DCDF_MEM_HOST || mask_mem == DCDF_MEM_DEVICE));
+    }
+    CubeMasks(const dcdf_cube* cubes, size_t nq, const uint8_t* mask, const uint64_t* mask_offset, int mask_mem)
+        : moff(nq, 0), p(mask), host(mask && mask_mem == DCDF_MEM_HOST) {
+        for (size_t q = 0; mask && q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            if (c.end == c.start) continue;
+            moff[q] = host ? total : mask_offset[q];
+            total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+        }
+    }
+    int stage(const dcdf_cube* cubes, size_t nq, const uint64_t* mask_offset) {
+        if (!host) return DCDF_OK;
+        K2R_HIP(d_mask.alloc_pooled(total));
+        for (size_t q = 0; q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+            if (c.end == c.start || bytes == 0) continue;
+            K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], p + mask_offset[q], bytes, hipMemcpyHostToDevice));
+        }
+        p = (const uint8_t*)d_mask.p;
+        return DCDF_OK;
+    }
+};
+
+// ---- decompress: whole regions, block by block (k2r_bulk.hip) ---------------------------------------------------------------
+// plan_decode (k2r_plan.h): BulkUnits for the pieces on chunks the bulk kernel takes, the wave items dcdf_raster_fill_window_batch
+// makes of the pieces on any other chunk, a ConstPiece per elided piece.  All three write the same output array.
+extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, void* out, int32_t out_dtype, int out_mem,
+                                        const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, out_args_ok(out_dtype, out_mem), ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    WindowOut W(cubes, nq, out, out_offset, elem_size(out_dtype), out_mem == DCDF_MEM_DEVICE);
+    DecodePlan P;
+    rc = plan_decode(r->plan(), cubes, nq, W.base.data(), r->all_node, bulk_wanted_units(), P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_consts, d_items;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    void* const d_out = W.dst();
+    rc = upload_some(d_units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(d_consts, P.consts);
+    if (rc == DCDF_OK) rc = upload_some(d_items, P.items);
+    if (rc != DCDF_OK) return rc;
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    rc = launch_raster_fill_const(r, d_consts.as<ConstPiece>(), (uint32_t)P.consts.size(), d_out, out_dtype);
+    if (rc == DCDF_OK) rc = launch_bulk_decode(r->d_refs.as<ChunkRef>(), d_units.as<BulkUnit>(), (uint32_t)P.units.size(), d_out, out_dtype);
+    if (rc == DCDF_OK && !P.items.empty())
+        rc = launch_window_items_dev(r->d_refs, d_items.as<WinItem>(), (uint32_t)P.items.size(), d_out, out_dtype, nullptr, ev.e1, r->all_node,
+                                     r->all_narrow);
+    if (rc != DCDF_OK) return rc;
+    return batch_epilogue(W, ev, P.items.empty(), kernel_ms);
+}
+// ---- reduce over time: per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h) --------------------
+// The plan, and what keeps the sum's order, are plan_reduce_time's (k2r_plan.h): the segments are launched one after the other in
+// ascending order on the null stream.  The state planes are the output planes themselves (cube q's requested planes in ascending
+// bit order); SUM / COUNT kept for MEAN alone live in scratch planes.
+//
+// Pieces on chunks the bulk kernel does not take are decoded by the window walk as stored integers (DCDF_I64: store_typed
+// leaves n as it is) into a slab of a bounded number of cells, then folded by k_reduce_fold, which applies the leaf's own
+// encoding (reduce_widen: the conversions of store_typed, so the value is the typed fill_window's) -- one walk launch per slab
+// whatever mix of encodings its chunks have.  Elided pieces are folded by the same kernel straight from dcdf_raster::d_vals.
+__global__ void __launch_bounds__(256)
+k_reduce_fold(const FoldPiece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, double* dst,
+              double* scr, uint32_t ops) {
+    const uint32_t live = reduce_live(ops);
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const FoldPiece P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
+            const uint64_t at = e / P.cols * P.sr + e % P.cols;
+            double s = 0.0, c = 0.0, lo = __builtin_nan(""), hi = __builtin_nan("");
+            if (!P.init) {
+                if (live & RA_MIN) lo = p_min[at];
+                if (live & RA_MAX) hi = p_max[at];
+                if (live & RA_SUM) s = p_sum[at];
+                if (live & RA_COUNT) c = p_cnt[at];
+            }
+            for (uint32_t t = 0; t < P.nt; t++) {
+                const double x = reduce_widen(P.enc, P.fbits, P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e]);
+                if (x == x) {
+                    s = s + x;
+                    c = c + 1.0;
+                    lo = fmin(lo, x);
+                    hi = fmax(hi, x);
+                }
+            }
+            if (live & RA_MIN) p_min[at] = lo;
+            if (live & RA_MAX) p_max[at] = hi;
+            if (live & RA_SUM) p_sum[at] = s;
+            if (live & RA_COUNT) p_cnt[at] = c;
+        }
+    }
+}
+// the finishing kernel: MEAN = SUM / COUNT, NaN where nothing was counted
+__global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const MeanPiece P = ps[p];
+        const double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        const double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_mean = dst + P.o_off + (uint64_t)popc32(ops & RA_ALL) * P.psz;
+        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) {
+            const double c = p_cnt[e];
+            p_mean[e] = c == 0.0 ? __builtin_nan("") : p_sum[e] / c;
+        }
+    }
+}
+static void launch_reduce_fold(const FoldPiece* d_ps, size_t n, const int64_t* d_slab, const int64_t* d_vals, double* d_dst, double* d_scr,
+                               uint32_t ops) {
+    if (n) hipLaunchKernelGGL(k_reduce_fold, dim3((uint32_t)std::min<size_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, (uint32_t)n, d_slab, d_vals, d_dst, d_scr, ops);
+}
+extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
+                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    const uint32_t live = reduce_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
+    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
+    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
+    std::vector<uint64_t> sbase(nq, 0);
+    uint64_t scr_total = 0;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
+        sbase[q] = scr_total;
+        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
+    }
+    WindowOut W(planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    TimePlan P(reduce_slab_cells());
+    rc = plan_reduce_time(r->plan(), cubes, nq, W.base.data(), sbase.data(), r->all_node, P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_means, d_scr;
+    WalkDev D;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    double* const d_dst = (double*)W.dst();
+    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(double)));
+    rc = upload_some(d_units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
+    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (rc != DCDF_OK) return rc;
+    if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    for (const SegRange& g : P.ranges) {
+        launch_reduce_fold(d_cfolds.as<FoldPiece>() + g.const0, g.const1 - g.const0, nullptr, r->d_vals.as<int64_t>(), d_dst, d_scr.as<double>(), ops);
+        K2R_HIP(hipGetLastError());
+        rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                d_dst, d_scr.as<double>(), ops);
+        if (rc == DCDF_OK)
+            rc = D.run(r, P.walk.slabs, g.slab0, g.slab1, [&](const Slab& b) {
+                launch_reduce_fold(D.folds.as<FoldPiece>() + b.fold0, b.fold1 - b.fold0, D.slab.as<int64_t>(), nullptr, d_dst, d_scr.as<double>(), ops);
+            });
+        if (rc != DCDF_OK) return rc;
+    }
+    if (ops & ROP_MEAN) {
+        uint64_t big = 0;
+        for (const MeanPiece& m : P.means) big = std::max(big, m.psz);
+        hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
+                           dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr.as<double>(), ops);
+        K2R_HIP(hipGetLastError());
+    }
+    return batch_epilogue(W, ev, true, kernel_ms);
+}
+// ---- reduce over space: per-instant min / max / sum / count / mean of the selected cells of a cube (k2r_space.h) ------------
+// The plan is plan_reduce_space's (k2r_plan.h): records of the pieces in a pooled scratch array, in blocks [slot][instant] that
+// k_space_finish folds into the cubes' series.  Instants are independent: one launch of each kind takes the work of a whole batch.
+//
+// 128-bit sums and the extremes of one wave's lanes into lane 0 .. and of a workgroup's four waves into thread 0 (LDS)
+struct SpaceAcc {
+    uint64_t hi, lo;
+    double mn, mx;
+    uint32_t cnt;
+};
+__device__ __forceinline__ void space_block_fold(SpaceAcc& a, SpaceAcc* sh) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t bh = (uint64_t)__shfl_xor((unsigned long long)a.hi, off), bl = (uint64_t)__shfl_xor((unsigned long long)a.lo, off);
+        space_add128(a.hi, a.lo, bh, bl);
+        a.cnt += __shfl_xor(a.cnt, off);
+        a.mn = fmin(a.mn, __shfl_xor(a.mn, off));
+        a.mx = fmax(a.mx, __shfl_xor(a.mx, off));
+    }
+    __syncthreads();  // (the previous round's reader is done)
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (uint32_t w = 1; w < 4u; w++) {
+            space_add128(a.hi, a.lo, sh[w].hi, sh[w].lo);
+            a.cnt += sh[w].cnt;
+            a.mn = fmin(a.mn, sh[w].mn);
+            a.mx = fmax(a.mx, sh[w].mx);
+        }
+}
+__device__ __forceinline__ void space_store(SpacePartial* recs, uint64_t at, const SpaceAcc& a, uint32_t scale) {
+    __attribute__((address_space(1))) SpacePartial* const o = (__attribute__((address_space(1))) SpacePartial*)recs + at;
+    o->hi = a.hi;
+    o->lo = a.lo;
+    o->mn = a.mn;
+    o->mx = a.mx;
+    o->cnt = a.cnt;
+    o->scale = scale;
+}
+// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding,
+// masked cells skipped.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per instant
+// writes value x count.
+__global__ void __launch_bounds__(256)
+k_space_fold(const SpaceFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+             const uint8_t* __restrict__ mask, SpacePartial* __restrict__ recs) {
+    __shared__ SpaceAcc sh[4];
+    __shared__ uint32_t sh_sel;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const SpaceFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        const uint32_t scale = space_scale(P.enc, P.fbits);
+        if (P.elided) {
+            if (blockIdx.y != 0) continue;
+            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+            if (mask) {
+                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) a.cnt += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
+            } else if (threadIdx.x == 0) {
+                a.cnt = (uint32_t)cells;
+            }
+            space_block_fold(a, sh);
+            if (threadIdx.x == 0) sh_sel = a.cnt;
+            __syncthreads();
+            const uint32_t selected = sh_sel;
+            for (uint32_t t = threadIdx.x; t < P.nt; t += blockDim.x) {
+                const int64_t v = vals[P.src + t];
+                const double x = reduce_widen(P.enc, P.fbits, v);
+                SpaceAcc o{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+                if (x == x && selected) {
+                    space_mul_m(o.hi, o.lo, space_m(P.enc, v), selected);
+                    o.cnt = selected;
+                    o.mn = o.mx = x;
+                }
+                space_store(recs, P.rec + t, o, scale);
+            }
+            continue;
+        }
+        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
+            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
+                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
+                const int64_t v = slab[P.src + (uint64_t)t * cells + e];
+                const double x = reduce_widen(P.enc, P.fbits, v);
+                if (x == x) {
+                    space_add_m(a.hi, a.lo, space_m(P.enc, v));
+                    a.cnt += 1u;
+                    a.mn = fmin(a.mn, x);
+                    a.mx = fmax(a.mx, x);
+                }
+            }
+            space_block_fold(a, sh);
+            if (threadIdx.x == 0) space_store(recs, P.rec + t, a, scale);
+        }
+    }
+}
+// A workgroup per (job, instant): the records of the pieces that cover the instant, their sums at the common 2^-63 scale added
+// in 192 bits, then the requested series -- SUM by one conversion of that integer, MEAN by one division.
+__global__ void __launch_bounds__(256)
+k_space_finish(const SpaceJob* __restrict__ jobs, uint32_t n, const SpacePartial* __restrict__ recs, double* dst, uint32_t ops) {
+    __shared__ U192 sh_s[4];
+    __shared__ uint64_t sh_c[4];
+    __shared__ double sh_mn[4], sh_mx[4];
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const SpaceJob J = jobs[j];
+        for (uint32_t t = blockIdx.y; t < J.nt; t += gridDim.y) {
+            U192 acc{0, 0, 0};
+            uint64_t cnt = 0;
+            double mn = __builtin_nan(""), mx = __builtin_nan("");
+            for (uint32_t s = threadIdx.x; s < J.n_slots; s += blockDim.x) {
+                const __attribute__((address_space(1))) SpacePartial* const R =
+                    (const __attribute__((address_space(1))) SpacePartial*)recs + (J.rec + (uint64_t)s * J.nt + t);
+                u192_add(acc, space_scaled(R->hi, R->lo, R->scale));
+                cnt += R->cnt;
+                mn = fmin(mn, R->mn);
+                mx = fmax(mx, R->mx);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                U192 b;
+                b.w0 = (uint64_t)__shfl_xor((unsigned long long)acc.w0, off);
+                b.w1 = (uint64_t)__shfl_xor((unsigned long long)acc.w1, off);
+                b.w2 = (uint64_t)__shfl_xor((unsigned long long)acc.w2, off);
+                u192_add(acc, b);
+                cnt += (uint64_t)__shfl_xor((unsigned long long)cnt, off);
+                mn = fmin(mn, __shfl_xor(mn, off));
+                mx = fmax(mx, __shfl_xor(mx, off));
+            }
+            __syncthreads();  // (the previous round's reader is done)
+            if ((threadIdx.x & 63u) == 0) {
+                sh_s[threadIdx.x >> 6] = acc;
+                sh_c[threadIdx.x >> 6] = cnt;
+                sh_mn[threadIdx.x >> 6] = mn;
+                sh_mx[threadIdx.x >> 6] = mx;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (uint32_t w = 1; w < 4u; w++) {
+                    u192_add(acc, sh_s[w]);
+                    cnt += sh_c[w];
+                    mn = fmin(mn, sh_mn[w]);
+                    mx = fmax(mx, sh_mx[w]);
+                }
+                const double sum = space_round(acc);
+                __attribute__((address_space(1))) double* o = (__attribute__((address_space(1))) double*)dst + (J.o_off + t);
+                if (ops & RA_MIN) { *o = mn == mn ? mn : __builtin_nan(""); o += J.o_stride; }
+                if (ops & RA_MAX) { *o = mx == mx ? mx : __builtin_nan(""); o += J.o_stride; }
+                if (ops & RA_SUM) { *o = sum; o += J.o_stride; }
+                if (ops & RA_COUNT) { *o = (double)cnt; o += J.o_stride; }
+                if (ops & ROP_MEAN) *o = cnt == 0 ? __builtin_nan("") : sum / (double)cnt;
+            }
+        }
+    }
+}
+// records of one batch of the plan (K2R_SPACE_RECORDS overrides: tests of the batch cut); 40 bytes each
+static uint64_t space_record_cap() {
+    const char* e = std::getenv("K2R_SPACE_RECORDS");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : (uint64_t)6 << 20;
+}
+extern "C" int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum) {
+    if ((n && (!hi || !lo || !scale)) || !sum) return DCDF_ERR_BAD_ARG;
+    U192 acc{0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+        if ((scale[i] & 255u) > 63u || scale[i] > (SPACE_NEG | 63u)) return DCDF_ERR_BAD_ARG;
+        u192_add(acc, space_scaled(hi[i], lo[i], scale[i]));
+    }
+    *sum = space_round(acc);
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint8_t* mask,
+                                              const uint64_t* mask_offset, int mask_mem, double* out, int out_mem, const uint64_t* out_offset,
+                                              uint64_t stats[3], float* kernel_ms) {
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem,
+                          ops != 0 && ops <= (RA_ALL | ROP_MEAN) && CubeMasks::args_ok(mask, mask_offset, mask_mem), EXACT_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    const uint32_t live = reduce_live(ops), n_out = popc32(ops);
+    // where the series go: cube q's are n_out "instants" of one row of [instants] to WindowOut
+    std::vector<dcdf_cube> series(nq, dcdf_cube{});
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end != c.start) series[q] = dcdf_cube{0, n_out, 0, 1, 0, c.end - c.start};
+    }
+    WindowOut W(series.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    CubeMasks M(cubes, nq, mask, mask_offset, mask_mem);
+    SpacePlan P(reduce_slab_cells());
+    rc = plan_reduce_space(r->plan(), cubes, nq, W.base.data(), M.moff.data(), r->all_node, space_record_cap(), bulk_wanted_units(), P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_jobs, d_recs;
+    WalkDev D;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    double* const d_dst = (double*)W.dst();
+    rc = M.stage(cubes, nq, mask_offset);
+    if (rc != DCDF_OK) return rc;
+    K2R_HIP(d_recs.alloc_pooled(P.rec_max * sizeof(SpacePartial)));
+    rc = upload_some(d_units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
+    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (rc != DCDF_OK) return rc;
+    K2R_HIP(upload(d_jobs, P.jobs));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    SpacePartial* const recs = d_recs.as<SpacePartial>();
+    for (const SpaceBatch& b : P.batches) {
+        if (b.const1 > b.const0) {
+            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
+                               d_cfolds.as<SpaceFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), M.p, recs);
+            K2R_HIP(hipGetLastError());
+        }
+        rc = launch_bulk_space(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<SpaceUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
+                               recs, live);
+        if (rc == DCDF_OK)
+            rc = D.run(r, P.walk.slabs, b.slab0, b.slab1, [&](const Slab& sl) {
+                hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
+                                   dim3(256), 0, 0, D.folds.as<SpaceFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr,
+                                   M.p, recs);
+            });
+        if (rc != DCDF_OK) return rc;
+        hipLaunchKernelGGL(k_space_finish, dim3((uint32_t)std::min<size_t>(b.job1 - b.job0, 1u << 20), std::min<uint32_t>(b.job_nt, 1024)), dim3(256), 0,
+                           0, d_jobs.as<SpaceJob>() + b.job0, (uint32_t)(b.job1 - b.job0), recs, d_dst, ops);
+        K2R_HIP(hipGetLastError());
+    }
+    return batch_epilogue(W, ev, true, kernel_ms);
+}
+// ---- value histograms: per instant, how many selected cells of a cube fall into every bin of shared edges (k2r_hist.h) -------
+// The plan is plan_histogram's (k2r_plan.h).  Every piece adds its counts to the cube's own [instants][bins] array with device-scope
+// 64-bit atomic adds; the call zeroes exactly those arrays first.  Integer adds commute: the result depends on no order.
+//
+// A workgroup per (piece, instant) of the window walk's slab: the cells' stored integers widened by the leaf's own encoding and
+// binned by the definition itself (hist_bin: the values here are wide, and the walk dominates), masked cells skipped, counts in
+// an LDS histogram first.  An elided piece (blockIdx.y == 0 alone): its selected cells are counted once, then a thread per
+// instant adds that count to the bin of the piece's value.
+__global__ void __launch_bounds__(256)
+k_hist_fold(const HistFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+            const uint8_t* __restrict__ mask, const double* __restrict__ edges, uint32_t n_bins, uint64_t* out) {
+    __shared__ uint32_t sh_cnt[HIST_MAX_BINS];
+    __shared__ uint32_t sh_sel;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const HistFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        if (P.elided) {
+            if (blockIdx.y != 0) continue;
+            __syncthreads();  // (the previous piece's readers are done)
+            if (threadIdx.x == 0) sh_sel = mask ? 0u : (uint32_t)cells;
+            __syncthreads();
+            if (mask) {
+                uint32_t c = 0;
+                for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) c += mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] != 0 ? 1u : 0u;
+                if (c) atomicAdd(&sh_sel, c);
+                __syncthreads();
+            }
+            const uint32_t selected = sh_sel;
+            for (uint32_t t = threadIdx.x; t < P.nt && selected; t += blockDim.x) {
+                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, vals[P.src + t]));
+                if (b >= 0) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + (uint32_t)b), (unsigned long long)selected);
+            }
+            continue;
+        }
+        for (uint32_t t = blockIdx.y; t < P.nt; t += gridDim.y) {
+            __syncthreads();  // (the previous round's readers are done)
+            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) sh_cnt[i] = 0u;
+            __syncthreads();
+            for (uint64_t e = threadIdx.x; e < cells; e += blockDim.x) {
+                if (mask && mask[P.m_off + e / P.cols * P.m_sr + e % P.cols] == 0) continue;
+                const int32_t b = hist_bin(edges, n_bins, reduce_widen(P.enc, P.fbits, slab[P.src + (uint64_t)t * cells + e]));
+                if (b >= 0) atomicAdd(&sh_cnt[b], 1u);
+            }
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < n_bins; i += blockDim.x) {
+                const uint32_t c = sh_cnt[i];
+                if (c) atomicAdd((unsigned long long*)out + (P.o_off + (uint64_t)t * n_bins + i), (unsigned long long)c);
+            }
+        }
+    }
+}
+extern "C" int dcdf_histogram_bounds(int32_t encoding, uint32_t fractional_bits, const double* edges, uint32_t n_bins, int64_t* lo, int64_t* hi) {
+    if (!lo || !hi || !hist_edges_ok(edges, n_bins) || !hist_leaf_ok(encoding, fractional_bits)) return DCDF_ERR_BAD_ARG;
+    hist_intervals(encoding, fractional_bits, edges, n_bins, lo, hi);
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* edges, uint32_t n_bins,
+                                           const uint8_t* mask, const uint64_t* mask_offset, int mask_mem, uint64_t* out, int out_mem,
+                                           const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, hist_edges_ok(edges, n_bins) && CubeMasks::args_ok(mask, mask_offset, mask_mem),
+                          EXACT_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    // where the counts go: cube q's are "instants" of one row of [bins] to WindowOut
+    std::vector<dcdf_cube> rows(nq, dcdf_cube{});
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end != c.start) rows[q] = dcdf_cube{0, c.end - c.start, 0, 1, 0, n_bins};
+    }
+    WindowOut W(rows.data(), nq, out, out_offset, sizeof(uint64_t), out_mem == DCDF_MEM_DEVICE);
+    CubeMasks M(cubes, nq, mask, mask_offset, mask_mem);
+    HistPlan P(reduce_slab_cells());
+    rc = plan_histogram(r->plan(), cubes, nq, W.base.data(), M.moff.data(), edges, n_bins, r->all_node, bulk_wanted_units(), P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_thr, d_edges;
+    WalkDev D;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    uint64_t* const d_dst = (uint64_t*)W.dst();
+    rc = M.stage(cubes, nq, mask_offset);
+    if (rc != DCDF_OK) return rc;
+    if (!P.units.empty()) {
+        K2R_HIP(upload(d_units, P.units));
+        K2R_HIP(upload(d_thr, P.thr));
+    }
+    rc = upload_some(d_cfolds, P.cfolds);
+    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (rc != DCDF_OK) return rc;
+    if (!P.cfolds.empty() || !P.walk.folds.empty()) K2R_HIP(upload(d_edges, std::vector<double>(edges, edges + n_bins + 1)));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    // the accumulators: exactly the cubes' arrays, nothing between them
+    if (!W.to_dev) {
+        K2R_HIP(hipMemsetAsync(d_dst, 0, W.total * W.es, 0));
+    } else {
+        for (size_t q = 0; q < nq; q++) {
+            const uint64_t n = cube_cells(rows[q]);
+            if (n) K2R_HIP(hipMemsetAsync(d_dst + W.base[q], 0, n * sizeof(uint64_t), 0));
+        }
+    }
+    if (!P.cfolds.empty()) {
+        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(P.cfolds.size(), 1u << 20), 1), dim3(256), 0, 0, d_cfolds.as<HistFold>(),
+                           (uint32_t)P.cfolds.size(), nullptr, r->d_vals.as<int64_t>(), M.p, d_edges.as<double>(), n_bins, d_dst);
+        K2R_HIP(hipGetLastError());
+    }
+    rc = launch_bulk_hist(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<HistUnit>(), (uint32_t)P.units.size(), M.p, d_thr.as<int32_t>(),
+                          n_bins, d_dst);
+    if (rc == DCDF_OK)
+        rc = D.run(r, P.walk.slabs, 0, P.walk.slabs.size(), [&](const Slab& sl) {
+            hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
+                               dim3(256), 0, 0, D.folds.as<HistFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr, M.p,
+                               d_edges.as<double>(), n_bins, d_dst);
+        });
+    if (rc != DCDF_OK) return rc;
+    return batch_epilogue(W, ev, true, kernel_ms);
+}

@@ -1,12 +1,12 @@
-// k2r_reduce.h -- reduction over time (dcdf_raster_reduce_time_batch): what the planner (k2r_raster.hip), the bulk kernel
-// (k2r_bulk.hip) and the fold kernels share.
+// k2r_reduce.h -- reduction over time (dcdf_raster_reduce_time_batch): what the planner (k2r_plan.h), the bulk kernel
+// (k2r_bulk.hip) and the fold kernels share.  Compiles for the host alone as well (g++).
 //
 // The contract (include/dcdf_k2r.h): per cell, x[t] = the value the typed fill_window returns with the
 // leaf's own encoding, widened to double; MIN / MAX = fmin / fmax over the non-NaN x[t]; SUM = the sequential chain
 // s = 0.0, s = s + x[t] in instant order; COUNT = the non-NaN x[t]; MEAN = SUM / COUNT.  The chain's order is what every piece
 // of the plan keeps: a cell's instants are only ever added one after the other to the one running sum of its state plane.
 #pragma once
-#include "k2r_query_types.h"
+#include "k2r_decode.h"
 
 namespace k2r {
 
@@ -57,8 +57,11 @@ struct MeanPiece {
     uint64_t o_off, s_off, psz;
 };
 
+#if defined(__HIPCC__)
+struct ChunkRef;
 // k_bulk_reduce over n units on the null stream (asynchronous).  d_enc: the chunks' encodings.  Returns a DCDF code.
 int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const ReduceUnit* d_units, uint32_t n, double* d_dst, double* d_scr,
                        uint32_t ops);
+#endif
 
 }  // namespace k2r

@@ -1,4 +1,4 @@
-// k2r_space.h -- reduction over space (dcdf_raster_reduce_space_batch): what the planner (k2r_raster.hip), the bulk kernel
+// k2r_space.h -- reduction over space (dcdf_raster_reduce_space_batch): what the planner (k2r_plan.h), the bulk kernel
 // (k2r_bulk.hip) and the fold / finish kernels share.  Everything here compiles for the host alone as well (g++), so the
 // arithmetic the result rests on can be run and sanitised on a CPU.
 //
