@@ -1,6 +1,8 @@
 """Superchunk assembly (dcdf_superchunk_build, superchunk.rs:88-270) on the GPU against the oracle: every stored object --
 framed sub-chunks, nested superchunks, Links, the Superchunk node itself -- byte-identical, CIDs equal, same de-duplication,
-same MMStruct3Build counters, for the shapes of the reference's own fixtures (superchunk.rs:1006-1188)."""
+same MMStruct3Build counters, for the shapes of the reference's own fixtures (superchunk.rs:1006-1188), synthetic rasters with
+the fused kernels' 256-tiles and the banded upload.  Device-resident input (Superchunk.build_device, strided views) and k up
+to 16 are checked against the oracle by tests/test_gpu_superchunk_cases.py over the table of tests/superchunk_cases.py."""
 import json
 import os
 

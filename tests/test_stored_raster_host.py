@@ -7,6 +7,7 @@ import pytest
 import oracle_lib as O
 import oracle_superchunk as OS
 from dcdf_amd.dataset import leaf_grid
+from raster_rebuild import rebuild_from
 
 
 def store_variable(a, levels, chunk_size, round_bits=None):
@@ -21,42 +22,10 @@ def store_variable(a, levels, chunk_size, round_bits=None):
     return store, cids
 
 
-def typed(values, bits, dtype):
-    v = np.asarray(values, dtype=np.int64)
-    if np.dtype(dtype).kind != "f":
-        return v.astype(dtype)
-    out = ((v - 1) / float(1 << (bits + 1))).astype(dtype)
-    out[v == 0] = np.nan
-    return out
-
-
 def rebuild(a, levels, chunk_size, round_bits=None):
     """The array rebuilt from leaf_grid's records, plus the records (with their raster positions) for further checks."""
     store, cids = store_variable(a, levels, chunk_size, round_bits)
-    leaf, grid = leaf_grid(store, cids, levels, round_bits is not None)
-    assert leaf == 1 << levels[-1]
-    T, R, C = a.shape
-    nti, ntj = -(-R // leaf), -(-C // leaf)
-    out = np.zeros_like(a)
-    recs = []
-    opened = {}
-    assert len(grid) == -(-T // chunk_size)
-    for s, g in enumerate(grid):
-        assert len(g) == nti * ntj
-        t0 = s * chunk_size
-        nt = min(chunk_size, T - t0)
-        for i, lf in enumerate(g):
-            r0, c0 = (i // ntj) * leaf, (i % ntj) * leaf
-            h, w = min(leaf, R - r0), min(leaf, C - c0)
-            assert lf.minmax.shape == (nt, 2)
-            if lf.cid is None:
-                assert lf.values.shape == (nt,)
-                out[t0:t0 + nt, r0:r0 + h, c0:c0 + w] = typed(lf.values, lf.fractional_bits, a.dtype)[:, None, None]
-            else:
-                ch = opened.setdefault(lf.cid, O.Chunk(store[lf.cid][8:]))
-                out[t0:t0 + nt, r0:r0 + h, c0:c0 + w] = ch.fill_window(0, nt, lf.row0, lf.row0 + h, lf.col0, lf.col0 + w, dtype=a.dtype)
-            recs.append((s, t0, nt, r0, c0, h, w, lf, store[lf.cid] if lf.cid else None))
-    return out, recs
+    return rebuild_from(store, cids, a, levels, chunk_size, round_bits is not None)
 
 
 def check_minmax_and_exact(a, recs, round_):

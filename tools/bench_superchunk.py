@@ -4,7 +4,6 @@ path): one time segment of the bench.py raster, [32, 4096, 4096], device-residen
 Everything `Variable::append` needs for one chunk_size slice is inside the timed call: per-tile (min, max), fractional bits (float
 input), 256 Chunk::builds in one launch, the min / max Dacs, SHA-256 of every stored object, the objects copied to the host."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -36,22 +35,16 @@ def main():
         import torch
         t = torch.empty(0)  # noqa: F841  (torch only to convert on the device)
         raise SystemExit("float32 variant: use tests (test_gpu_superchunk.py); the throughput figure is quoted for int32")
-    d = L.TileDesc()
-    d.base, d.dtype = buf.ptr, dtype
-    d.stride_t, d.stride_r, d.stride_c = E * E, E, 1
-    d.instants, d.rows, d.cols = T, E, E
-    d.fractional_bits, d.round = fb, 0
-    levels = (C.c_uint32 * 2)(int(np.log2(E)) - 8, 8)
+    from dcdf_amd import Superchunk
+    levels = [int(np.log2(E)) - 8, 8]
     best, last = None, None
     for _ in range(args.reps):
-        out = C.POINTER(L.SuperchunkBuild)()
         t0 = time.perf_counter()
-        L.check(L.lib().dcdf_superchunk_build(C.byref(d), levels, C.c_size_t(2), 2, L.MEM_DEVICE, C.byref(out)), "superchunk_build")
+        b = Superchunk.build_device(buf.ptr, np.int32, (E * E, E, 1), (T, E, E), levels, k=2, fractional_bits=fb)
         dt = time.perf_counter() - t0
-        s = out.contents
-        last = {"objects": int(s.n_objects), "size": int(s.size), "elided": int(s.elided), "external": int(s.external),
-                "snapshots": int(s.snapshots), "logs": int(s.logs), "stored_bytes": int(sum(s.objects[i].len for i in range(s.n_objects)))}
-        L.lib().dcdf_free_superchunk(out)
+        last = {"objects": len(b.objects), "size": int(b.size), "elided": int(b.elided), "external": int(b.external),
+                "snapshots": int(b.snapshots), "logs": int(b.logs), "stored_bytes": int(sum(len(o) for o in b.objects.values()))}
+        del b
         best = dt if best is None else min(best, dt)
     cells = T * E * E
     print(json.dumps({"entry": "dcdf_superchunk_build (device-resident [%d,%d,%d] int32, levels [%d,8])" % (T, E, E, levels[0]),
