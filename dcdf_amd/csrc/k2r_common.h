@@ -66,6 +66,13 @@ struct TileArgs {  // one Chunk::build input (device-visible copy of dcdf_tile_d
 };
 constexpr uint32_t PART_CMP = 1, PART_NOCMP = 2, PART_FAILED = 3;
 
+struct EncClass {  // one instantiation of the fused encoder kernel (k2r_launch.h; chosen by k2r_session_plan.h)
+    int log2s;     // 4..8 (sidelen 8 and below go to the universal kernel)
+    bool padded;
+    int vec;       // 0 generic loads, 1 int32 vector loads, 2 float32, 3 int64, 4 float64 vector loads (k2r_encode.h load_sub16)
+    bool operator==(const EncClass& o) const { return log2s == o.log2s && padded == o.padded && vec == o.vec; }
+};
+
 constexpr int NPROF = 20;
 struct TileResult {
     int32_t status;

@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <mutex>
@@ -11,22 +10,9 @@
 
 #include "../../include/dcdf_k2r.h"
 #include "k2r_common.h"
+#include "k2r_ref_tree.h"
 
 namespace k2r {
-
-// Tree depth as the reference computes it: ceil(ln(m) / ln(k)) in f64 (snapshot.rs:118-119, log.rs:124-125,
-// superchunk.rs:98-101).  NOT always the smallest H with k^H >= m: ln(125)/ln(5) = 3.0000000000000004, so a 125-wide tile
-// with k = 5 gets 4 levels and sidelen 625 (likewise k = 6, m = 216 -> 1296); a drop-in has to build and accept the same tree.
-inline uint32_t ref_levels(uint64_t m, uint32_t k) {
-    if (m <= 1) return 0;
-    const double e = std::ceil(std::log((double)m) / std::log((double)k));
-    return e > 0 ? (uint32_t)e : 0u;
-}
-inline uint64_t ref_sidelen(uint64_t m, uint32_t k) {
-    uint64_t s = 1;
-    for (uint32_t i = ref_levels(m, k); i > 0; i--) s *= k;
-    return s;
-}
 
 struct Runtime {
     bool ok = false;
@@ -243,17 +229,9 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
-}  // namespace k2r
-struct dcdf_encoder;
-namespace k2r {
-// The encoded bytes of a finished session, device slots -> pinned double buffer -> wherever `dst(tile, len)` says (called once
-// per tile with bytes, from worker threads; it may allocate the destination there).  k2r_capi_encode.hip.
-// `landed(tile)`, if given, runs on the worker thread right after a tile's bytes have been copied to their destination.
-int encoder_download(dcdf_encoder* e, const std::function<uint8_t*(size_t, uint64_t)>& dst,
-                     const std::function<void(size_t)>& landed = nullptr);
 // runs f(0..n) on a few host threads
 void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
-// how many: see host_threads() in k2r_capi_encode.hip (K2R_HOST_THREADS overrides)
+// how many: see host_threads() in k2r_host_batch.hip (K2R_HOST_THREADS overrides)
 int host_thread_count();
 
 inline int map_status(int32_t st) {

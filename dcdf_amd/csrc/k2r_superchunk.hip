@@ -37,7 +37,7 @@
 #include <vector>
 
 #include "k2r_encode.h"
-#include "k2r_runtime.h"
+#include "k2r_session.h"
 #include "k2r_sha256_host.h"
 
 namespace k2r {

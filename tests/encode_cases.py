@@ -6,7 +6,7 @@ walk the same table.
   views(L, dtype)       -> (name, (padded, loader), make(buffer) -> (byte_offset, strides, shape))
   contents(kind, ...)   -> (array, fractional_bits, round)
   error_tiles(L, dtype) -> (name, array, fractional_bits, round, code)
-  classify(...)         -> (log2_sidelen, padded, loader): validate_tile's rule (k2r_capi_encode.hip) restated
+  classify(...)         -> (log2_sidelen, padded, loader): validate_tile's rule (k2r_session_plan.h) restated
 """
 import zlib
 

@@ -35,7 +35,7 @@ static void run_l(const TileArgs& ta, TileResult* res, bool padded, int vec) {
 }
 
 // > 0: encode in speculative parts and splice (mirrors k_stitch): two parts [0, m) + [m, T), or g_parts parts of decreasing
-// length as k2r_capi_encode.hip's part_bounds cuts them
+// length as k2r_session_plan.h's part_bounds cuts them
 static uint32_t g_split_at = 0, g_parts = 0;
 extern "C" void sim_set_split(uint32_t m) { g_split_at = m; g_parts = 0; }
 extern "C" void sim_set_parts(uint32_t p) { g_parts = p; g_split_at = 0; }

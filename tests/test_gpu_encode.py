@@ -306,11 +306,13 @@ def test_speculative_parts_splice(dc, monkeypatch, parts):
     late = arrays[1].copy()
     late[20:] = np.random.default_rng(6).integers(0, 1 << 20, size=late[20:].shape)       # block boundaries in the second half only
     arrays.append(late)
-    arrays.append(arrays[2][:3].copy())                                                    # 3 instants: not split
+    # (a tile of fewer than 4 instants keeps its whole class from being split -- plan_split's rule, k2r_session_plan.h --, so
+    # the short one is encoded below, in a session of its own; tests/test_session_plan_host.py holds these shapes to a split)
     wide = arrays[0].copy()
     wide[0, 7, 7] = 300000                                                                 # instant 0 beyond 16 bits: no compact copy to share
     arrays.append(wide)
     arrays += [synth.cells(0xDCDF0003, 32 * s, 32 * s + 32, 0, 256, 256 * j, 256 * j + 256, np.int32) for s in range(3) for j in range(8)]
     assert_same(dc, arrays)
+    assert_same(dc, [arrays[2][:3].copy()])                                                # 3 instants: not split
     f = (arrays[5][:, :64, :64] // 2 / 8.0).astype(np.float32)
     assert_same(dc, [f], fractional_bits=3)

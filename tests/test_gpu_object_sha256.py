@@ -164,7 +164,7 @@ def test_failed_tiles_among_good_ones(dc):
 @pytest.fixture(scope="module")
 def split_tiles():
     """The long tiles of sha_cases.split_cases() and the table's side-16 tiles of four instants and more.  plan_split
-    (k2r_capi_encode.hip) splits the tiles of a kernel class only when EVERY tile of the class has at least four instants, so no
+    (k2r_session_plan.h) splits the tiles of a kernel class only when EVERY tile of the class has at least four instants, so no
     shorter tile of side 16 or 256 may join this session; the side-8 tiles (universal kernel, never split) ride along whole."""
     table = S.table()[:64]
     small = [c for c in table if c.array.shape[1] == 16 and c.array.shape[0] >= 4]
@@ -221,4 +221,68 @@ def test_universal_kernel_k3(dc):
     dig, _ = s.enc.object_sha256()
     s.check_digests(dig)
     s.check_bytes_and_cids()
+    s.close()
+
+
+def retry_tiles():
+    """Side-16 int32 tiles of 8 instants -- with K2R_PARTS=4 each is cut into [0, 4), [4, 6), [6, 8) -- on one base image, named
+    by what happens to their parts, plus a side-8 tile for the universal kernel.  `snap`: the instants the oracle stores as
+    Snapshots."""
+    rng = np.random.default_rng(0x5E55)
+    base = np.zeros((8, 16, 16), dtype=np.int32) + 7
+    base[:, :8, :8] = 9
+
+    def noise_at(t, span):
+        a = base.copy()
+        a[t] = rng.integers(0, span, size=(16, 16))
+        return a
+    tiles = [S.Case("smooth", base), S.Case("snapshot-in-first-part", noise_at(2, 50)), S.Case("snapshot-in-middle-part", noise_at(5, 50)),
+             S.Case("middle-part-then-too-big", noise_at(5, 1 << 20)), S.Case("too-big", rng.integers(0, 1 << 20, size=(8, 16, 16)).astype(np.int32)),
+             S.Case("universal-5x8x8", rng.integers(-9, 9, size=(5, 8, 8)).astype(np.int32))]
+    for c in tiles:
+        c.snap = O.chunk_build(c.array, want_snapshots=True)[3]
+    return tiles
+
+
+@pytest.mark.parametrize("cap", [256, 1024])
+def test_split_session_retries_and_runs_twice(dc, monkeypatch, cap):
+    """One session, split tiles, small slots, run() twice: the retry loop of dcdf_encoder_run and the plan's book-keeping behind it
+    (plan_retry, drop_parts: the parts of a tile that is whole from now on leave the queues and the splice tables) between two runs.
+    After each run digests, bytes, CIDs, counters and a gather must equal the oracle's.
+
+    cap = 256 is smaller than ANY 8-instant chunk of side 16 (the smallest, a constant tile, takes 334 bytes): every tile of the
+    class comes back ST_OUT_CAPACITY and is whole, in a worst-case slot, from the first retry on; the second run has no parts.
+    cap = 1024 is where the parts do different things, asserted below from the oracle's Snapshot positions and lengths: `smooth`
+    splices in both runs; a Snapshot in [1, 4) or in [4, 6) is ST_RESPLIT and the tile then fits whole; a wider one in [4, 6) is
+    ST_RESPLIT and then ST_OUT_CAPACITY (the second pass); `too-big` is ST_OUT_CAPACITY at once.  Nothing in the ABI tells a
+    spliced tile from a whole one: which tiles the plan splits is pinned on the CPU (tests/test_session_plan_host.py)."""
+    monkeypatch.setenv("K2R_SPLIT", "all")
+    monkeypatch.setenv("K2R_PARTS", "4")
+    tiles = retry_tiles()
+    smooth, first, middle, middle_big, big, universal = tiles
+    if cap == 1024:
+        assert smooth.snap == [0] and smooth.length <= cap
+        assert any(1 <= t < 4 for t in first.snap) and first.length <= cap
+        assert all(t == 0 or t >= 4 for t in middle.snap) and any(4 <= t < 6 for t in middle.snap) and middle.length <= cap
+        assert all(t == 0 or t >= 4 for t in middle_big.snap) and any(4 <= t < 6 for t in middle_big.snap) and middle_big.length > cap
+        assert big.length > cap
+    else:
+        assert all(c.length > cap for c in tiles[:5])
+    s = Session(tiles, out_cap_per_tile=cap)
+    assert [s.enc.tile_kernel(i) for i in range(6)] == [(4, 0, 1, 0)] * 5 + [(-1, -1, -1, (2 << 8) | 3)]
+    for run in (1, 2):
+        s.enc.run()
+        dig, _ = s.enc.object_sha256()
+        s.check_digests(dig, "cap %d, run %d: " % (cap, run))
+        s.check_bytes_and_cids()
+        buf, offs, lens, mm = s.enc.gather()
+        at = 0
+        for i, c in enumerate(tiles):
+            want = O.chunk_build(c.array, want_snapshots=True)
+            assert s.enc.result(i) == (0, c.length, want[1], want[2]), (run, c.name)
+            assert bytes(buf[int(offs[i]):int(offs[i]) + int(lens[i])]) == c.ref, (run, c.name)
+            flat = c.array.reshape(c.array.shape[0], -1)
+            np.testing.assert_array_equal(mm[at:at + len(flat)], np.stack([flat.min(1), flat.max(1)], axis=1), err_msg=c.name)
+            at += len(flat)
+        assert s.enc.total_bytes() == sum(c.length for c in tiles)
     s.close()

@@ -261,7 +261,7 @@ def test_speculative_halves():
         for m in (1, 2, 4, 5, 8):
             L.sim_set_split(m)
             assert check(a)[0] == ref
-        for p in (2, 3, 4):                                                  # parts of decreasing length (k2r_capi_encode.hip part_bounds)
+        for p in (2, 3, 4):                                                  # parts of decreasing length (k2r_session_plan.h part_bounds)
             L.sim_set_parts(p)
             assert check(a)[0] == ref
             big = np.concatenate([a, a[::-1], a])                            # 27 instants: parts at 14, 21, 24
