@@ -1,119 +1,16 @@
-// k2r_bulk.hip -- bulk decode of whole regions: the Snapshot of a block is decoded ONCE per region into an LDS max-pyramid,
-// then every instant of the block is a walk of its Log's own tree (T, eqB, Lmax) whose leaves are filled from that pyramid.
-//
-// Why that is the window walk's result (Log::_fill_window, log.rs:349-508): a Log node stores d = max_t - max_s itself (assigned,
-// not accumulated: log.rs:397-400), so the value the lock-step descent yields over a square is always d(log leaf) + S, S being the
-// Snapshot's running max_s where the descent stands:
-//   * Log leaf, eqB bit 0 (uniform, log.rs:452-467): every cell of the node's square is d + max_s(same node);
-//   * Log leaf with eqB bit 1, or the Log side already None: the descent goes on in the Snapshot alone with max_t fixed: every cell
-//     is d + s(cell);
-//   * Snapshot leaf above, Log goes on (log.rs:433-450): max_s stays the Snapshot leaf's value: every cell is d(cell-level log
-//     leaf) + that value.
-// So with P[l][node] = the Snapshot's own max_s of every node of side 2^l inside the region -- BELOW a Snapshot leaf the leaf's
-// value repeated, filled top-down from the tree (padded squares stay exact) -- the three cases read "d + P[l][node]" (uniform leaf
-// at level l) and "d + P[0][cell]" (the other two).  The root shortcuts of Log::fill_window (log.rs:315-327) are the same rule at
-// the root; they and everything above side 16 come ready-made from the chunk's side-16 table (TopEnt, k_top_table).  Lmin is
-// never read.
+// k2r_bulk.hip -- the four bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
+// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h).  All four walk a unit the same way; that
+// walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8, bulk_select16).  A thread
+// gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
 #include <hip/hip_runtime.h>
 
-#include "k2r_bulk.h"
+#include "k2r_bulk_walk.h"
 #include "k2r_hist.h"
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
 #include "k2r_space.h"
 
 namespace k2r {
-
-// Level l = nodes of side 2^l; the region holds (64 >> l)^2 of them, row-major.  Values of levels 0..4, walk state of levels 1..4.
-constexpr uint32_t BP_OFF[5] = {0u, 4096u, 5120u, 5376u, 5440u};
-constexpr uint32_t BP_SIZE = 5456u;  // 21 824 bytes of int32
-constexpr uint32_t BN_OFF[5] = {0u, 336u, 80u, 16u, 0u};  // (level 0 has no state: cells)
-constexpr uint32_t BN_SIZE = 1360u;
-// state word of a node during a Log's walk: the index of its first child in the Log tree (open), or resolved: every cell below
-// is d + P[l][its ancestor at level l] (BS_RES | l), or d itself (BS_CONST: a square the side-16 table already holds as one value)
-constexpr uint32_t BS_RES = 0x80000000u, BS_CONST = BS_RES | 7u;
-
-typedef __attribute__((address_space(1))) const TopEnt* gtopent;
-__device__ __forceinline__ TopEnt top_load(const TopEnt* p) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 x = *(__attribute__((address_space(1))) const u32x4*)p;
-    return TopEnt{x.x, x.y, (int32_t)x.z, (int32_t)x.w};
-}
-
-// One level of the Snapshot's pyramid: a lane per node of level PL with its four adjacent children (dac4 / rank_nib); a node
-// without children in the tree hands its value down.
-template <int PL>
-__device__ __forceinline__ void bulk_snap_level(gbytes gb, const TreeRef& S, const DacDesc& Sfull, int32_t* pyr, uint32_t* nst, uint32_t tid) {
-    constexpr uint32_t WP = BULK_REGION >> PL, NP = WP * WP;
-    for (uint32_t n = tid; n < NP; n += 256u) {
-        const uint32_t idx = nst[BN_OFF[PL] + n];
-        const int32_t pv = pyr[BP_OFF[PL] + n];
-        int32_t cv[4] = {pv, pv, pv, pv};
-        uint32_t ci[4] = {WQ_NONE, WQ_NONE, WQ_NONE, WQ_NONE};
-        if (idx != WQ_NONE) {
-            int32_t ds[4];
-            dac4<int32_t>(gb, S, Sfull, idx, ds);
-            uint32_t ts = 0, rs = 0;
-            if (PL > 1 && idx < S.T.len) rs = rank_nib(gb, S.T, idx, &ts);  // (children beyond T are cells: snapshot.rs:281-299)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                cv[c] = pv - ds[c];
-                if ((ts >> (3 - c)) & 1u) ci[c] = 1u + (rs + popc32(ts >> (4 - c))) * 4u;
-            }
-        }
-        const uint32_t pr = n / WP, pc = n % WP;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const uint32_t at = (2u * pr + (uint32_t)(c >> 1)) * (2u * WP) + 2u * pc + (uint32_t)(c & 1);
-            pyr[BP_OFF[PL - 1] + at] = cv[c];
-            if (PL > 1) nst[BN_OFF[PL - 1] + at] = ci[c];
-        }
-    }
-}
-// One level of a Log's walk (log.rs:392-505 without the Snapshot side): a lane per node of level PL; an open node reads its four
-// children's Lmax, T and eqB bits, a resolved one hands its state down.
-template <int PL>
-__device__ __forceinline__ void bulk_log_level(gbytes gb, const TreeRef& L, const DacDesc& Lfull, uint32_t* nst, int32_t* nd, uint32_t tid) {
-    constexpr uint32_t WP = BULK_REGION >> PL, NP = WP * WP;
-    for (uint32_t n = tid; n < NP; n += 256u) {
-        const uint32_t st = nst[BN_OFF[PL] + n];
-        const int32_t d = nd[BN_OFF[PL] + n];
-        uint32_t cs[4] = {st, st, st, st};
-        int32_t cd[4] = {d, d, d, d};
-        if (!(st & BS_RES)) {
-            int32_t dt[4];
-            dac4<int32_t>(gb, L, Lfull, st, dt);
-            const bool cells = st >= L.T.len;  // (malformed: children beyond T are cells, taken as "equal" like expand4)
-            uint32_t tt = 0, rt = 0, eq4 = 0xfu;
-            if (!cells) {
-                rt = rank_nib(gb, L.T, st, &tt);
-                // eqB has one bit per T = 0 node: child c's is the (zeros among the children before c)-th from eqB[st - rt] on
-                eq4 = gbm_get4(gb, L.E, st - rt);
-            }
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const uint32_t before = popc32(tt >> (4 - c));
-                cd[c] = dt[c];
-                if ((tt >> (3 - c)) & 1u) cs[c] = 1u + (rt + before) * 4u;
-                else cs[c] = ((eq4 >> (3u - ((uint32_t)c - before))) & 1u) ? BS_RES : (BS_RES | (uint32_t)(PL - 1));
-            }
-        }
-        const uint32_t pr = n / WP, pc = n % WP;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const uint32_t at = (2u * pr + (uint32_t)(c >> 1)) * (2u * WP) + 2u * pc + (uint32_t)(c & 1);
-            nst[BN_OFF[PL - 1] + at] = cs[c];
-            nd[BN_OFF[PL - 1] + at] = cd[c];
-        }
-    }
-}
-// d + P[l][ancestor of region cell (r, c) at level l] for a resolved state word
-__device__ __forceinline__ int32_t bulk_resolved(const int32_t* pyr, uint32_t st, int32_t d, uint32_t r, uint32_t c) {
-    if (st == BS_CONST) return d;
-    const uint32_t l = st & 7u;
-    const uint32_t off = l == 0 ? BP_OFF[0] : l == 1 ? BP_OFF[1] : l == 2 ? BP_OFF[2] : l == 3 ? BP_OFF[3] : BP_OFF[4];
-    return d + pyr[off + ((r >> l) << (6u - l)) + (c >> l)];
-}
 
 // MMBuffer3::set's conversions (store_typed, k2r_decode.h) for four cells of one row: chunk row r, columns c0 .. c0 + 3 (c0 a
 // multiple of 4), clipped to [left, right); `off` = element of (r, c0) in out.  One 16-byte store (two for 8-byte elements) when the
@@ -179,69 +76,10 @@ k_bulk_decode(const ChunkRef* __restrict__ chunks, const BulkUnit* __restrict__ 
         const BulkUnit U = units[u];
         const ChunkRef C = chunks[U.chunk];
         const gbytes gb = (gbytes)C.bytes;
-        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
         const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
-        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;  // (tid < 16: its side-16 square of the region)
-        const bool sq_in = r16 + qi < G && c16 + qj < G;
         uint32_t cur_snap = 0xffffffffu;
         for (uint32_t t = U.t0; t < U.t1; t++) {
-            const gdesc gD = (gdesc)C.descs + t;
-            const bool is_log = gD->is_log != 0;
-            const uint32_t snap = is_log ? gD->snap : t;
-            __syncthreads();  // (the previous instant's readers are done)
-            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
-                cur_snap = snap;
-                const TreeRef S = tree_ref((gdesc)C.descs + snap);
-                const DacDesc& Sfull = C.descs[snap].mx;  // (generic view: only for the rare values of three or more bytes)
-                if (tid < 16u) {
-                    int32_t v = 0;
-                    uint32_t idx = WQ_NONE;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
-                        v = e.mt + e.ms;
-                        idx = e.bs;
-                    }
-                    pyr[BP_OFF[4] + tid] = v;
-                    nst[BN_OFF[4] + tid] = idx;
-                }
-                __syncthreads();
-                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-            }
-            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
-            const DacDesc& Lfull = C.descs[t].mx;
-            if (is_log) {
-                if (tid < 16u) {
-                    uint32_t st = BS_CONST;
-                    int32_t d = 0;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
-                        if (e.bt != WQ_NONE) {
-                            st = e.bt;
-                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
-                            st = BS_RES;
-                            d = e.mt;
-                        } else {
-                            d = e.mt + e.ms;
-                        }
-                    }
-                    nst[BN_OFF[4] + tid] = st;
-                    nd[BN_OFF[4] + tid] = d;
-                }
-                __syncthreads();
-                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-            }
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
             // ---- nodes of side 2, two per task: their 2 x 4 cells, stored as two row segments ----
             const int64_t obase = (int64_t)U.out_off + (int64_t)(t - U.t0) * (int64_t)U.out_st - (int64_t)top * U.out_sr - (int64_t)left;
 #pragma unroll
@@ -250,23 +88,7 @@ k_bulk_decode(const ChunkRef* __restrict__ chunks, const BulkUnit* __restrict__ 
                 const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
                 if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
                 V v[2][4];
-#pragma unroll
-                for (uint32_t j = 0; j < 2u; j++) {
-                    const uint32_t n = rp * 32u + 2u * cg + j;
-                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
-                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
-                    if (!(st & BS_RES)) {
-                        V dt[4];
-                        dac4<V>(gb, L, Lfull, st, dt);
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
-                    } else {
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
-                    }
-                }
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
 #pragma unroll
                 for (uint32_t i = 0; i < 2u; i++) {
                     const uint32_t r = r0 + i;
@@ -286,7 +108,7 @@ uint32_t bulk_wanted_units() {
 
 int launch_bulk_decode(const ChunkRef* d_refs, const BulkUnit* d_units, uint32_t n, void* d_out, int32_t out_dtype) {
     if (n == 0) return DCDF_OK;
-    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    const dim3 grid = bulk_grid(n), block(256);
     switch (out_dtype) {
         case DCDF_I32: hipLaunchKernelGGL((k_bulk_decode<int32_t, ENC_I32>), grid, block, 0, 0, d_refs, d_units, n, d_out); break;
         case DCDF_I64: hipLaunchKernelGGL((k_bulk_decode<int32_t, ENC_I64>), grid, block, 0, 0, d_refs, d_units, n, d_out); break;
@@ -298,7 +120,19 @@ int launch_bulk_decode(const ChunkRef* d_refs, const BulkUnit* d_units, uint32_t
     return DCDF_OK;
 }
 
-// ---- reduction over time (k2r_reduce.h): the decode kernel with its stores replaced by per-cell accumulators ---------------
+// ---- what the folding kernels know of a leaf's encoding --------------------------------------------------------------------
+// 0: an integer leaf, x = (double)n.  1 / 2: a float32 / float64 leaf, stored 0 is NaN and x = from_fixed(n) (k2r_decode.h).
+__device__ __forceinline__ int leaf_kind(int32_t enc) { return enc == ENC_F32 ? 1 : enc == ENC_F64 ? 2 : 0; }
+// The sign mirror of a leaf's stored integers: key = (n ^ sg) - sg is n for sg = 0, -n for sg = -1, and its own inverse.
+// from_fixed is monotone in n, so a unit keeps its extremes as keys and widens them once.  x DEcreases in n exactly when
+// from_fixed's divisor (int64_t)1 << (fbits + 1) is negative: the shift into the sign bit, fbits == 62 (no leaf has more).
+__device__ __forceinline__ int32_t leaf_mirror(int kind, uint32_t fbits) { return kind != 0 && fbits == 62u ? -1 : 0; }
+// a unit's extreme from its key: NaN while the key is still at its sentinel `none` ("no value yet"), else the contract's x
+__device__ __forceinline__ double leaf_extreme(int32_t key, int32_t none, int32_t enc, uint32_t fbits, int32_t sg) {
+    return key == none ? __builtin_nan("") : reduce_widen(enc, fbits, (int64_t)((key ^ sg) - sg));
+}
+
+// ---- reduction over time (k2r_reduce.h): the walk's cells into per-cell accumulators ----------------------------------------
 // Four cells of one row of a state plane: p = element of chunk column c0 (a multiple of 4), clipped to [left, right).  Two
 // 16-byte accesses when the four cells are inside and p is aligned, single elements otherwise (bulk_store4's rule).
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -325,7 +159,7 @@ __device__ __forceinline__ void plane_store4(double* p, const double (&v)[4], ui
 // One instant of four cells into their accumulators.  KIND 0: an integer chunk, x = (double)n.  KIND 1 / 2: a float32 / float64
 // chunk, stored 0 is NaN and skipped, x = from_fixed (k2r_decode.h) with the division by +-2^(fbits + 1) written as the product
 // with its reciprocal (inv / invf): both are exact, so the bits are from_fixed's.  lo / hi hold the extremes as stored integers
-// (from_fixed is monotone in n; sg = -1 mirrors n when the divisor is negative, fbits = 62) and are converted once per unit.
+// (keys mirrored by sg, leaf_mirror) and are converted once per unit.
 template <uint32_t LIVE, int KIND>
 __device__ __forceinline__ void reduce_fold4(const int32_t (&v)[4], double (&s)[4], uint32_t (&cnt)[4], int32_t (&lo)[4], int32_t (&hi)[4],
                                              double inv, float invf, int32_t sg) {
@@ -352,11 +186,11 @@ __device__ __forceinline__ void reduce_fold4(const int32_t (&v)[4], double (&s)[
     }
 }
 
-// LIVE: the accumulators this instantiation carries (RA_*).  A thread owns the 16 cells k_bulk_decode stores per instant (two
-// groups of 2 rows x 4 columns); their accumulators stay in registers over the unit's instants.  SUM continues the chain of the
-// state plane: it is loaded before the first instant (0.0 when the unit starts its cube) and stored after the last.  COUNT, MIN
-// and MAX are merged into their planes at the end (identity NaN).  Cells outside the unit's rectangle are decoded as in
-// k_bulk_decode; their rows are not accumulated and nothing of them is written.
+// LIVE: the accumulators this instantiation carries (RA_*).  A thread owns the same 16 cells at every instant (its two tasks
+// of 2 rows x 4 columns, bulk_cells8); their accumulators stay in registers over the unit's instants.  SUM continues the chain
+// of the state plane: it is loaded before the first instant (0.0 when the unit starts its cube) and stored after the last.
+// COUNT, MIN and MAX are merged into their planes at the end (identity NaN).  Cells outside the unit's rectangle are decoded as
+// in k_bulk_decode; their rows are not accumulated and nothing of them is written.
 template <uint32_t LIVE>
 __global__ void __launch_bounds__(256)
 k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const ReduceUnit* __restrict__ units, uint32_t n_units,
@@ -370,16 +204,13 @@ k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ e
         const ReduceUnit U = units[u];
         const ChunkRef C = chunks[U.chunk];
         const int32_t enc = (int32_t)encs[U.chunk];
-        const int kind = enc == ENC_F32 ? 1 : enc == ENC_F64 ? 2 : 0;
+        const int kind = leaf_kind(enc);
         const int64_t div = (int64_t)1 << (C.fbits + 1u);  // from_fixed's divisor
         const double inv = 1.0 / (double)div;
         const float invf = 1.0f / (float)div;
-        const int32_t sg = kind != 0 && div < 0 ? -1 : 0;
+        const int32_t sg = leaf_mirror(kind, C.fbits);
         const gbytes gb = (gbytes)C.bytes;
-        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
         const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
-        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
-        const bool sq_in = r16 + qi < G && c16 + qj < G;
         double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, U.o_off, U.s_off, U.psz);
         double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, U.o_off, U.s_off, U.psz);
         double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, U.o_off, U.s_off, U.psz);
@@ -405,87 +236,15 @@ k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ e
         }
         uint32_t cur_snap = 0xffffffffu;
         for (uint32_t t = U.t0; t < U.t1; t++) {
-            const gdesc gD = (gdesc)C.descs + t;
-            const bool is_log = gD->is_log != 0;
-            const uint32_t snap = is_log ? gD->snap : t;
-            __syncthreads();  // (the previous instant's readers are done)
-            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
-                cur_snap = snap;
-                const TreeRef S = tree_ref((gdesc)C.descs + snap);
-                const DacDesc& Sfull = C.descs[snap].mx;
-                if (tid < 16u) {
-                    int32_t v = 0;
-                    uint32_t idx = WQ_NONE;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
-                        v = e.mt + e.ms;
-                        idx = e.bs;
-                    }
-                    pyr[BP_OFF[4] + tid] = v;
-                    nst[BN_OFF[4] + tid] = idx;
-                }
-                __syncthreads();
-                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-            }
-            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
-            const DacDesc& Lfull = C.descs[t].mx;
-            if (is_log) {
-                if (tid < 16u) {
-                    uint32_t st = BS_CONST;
-                    int32_t d = 0;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
-                        if (e.bt != WQ_NONE) {
-                            st = e.bt;
-                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
-                            st = BS_RES;
-                            d = e.mt;
-                        } else {
-                            d = e.mt + e.ms;
-                        }
-                    }
-                    nst[BN_OFF[4] + tid] = st;
-                    nd[BN_OFF[4] + tid] = d;
-                }
-                __syncthreads();
-                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-            }
-            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded where k_bulk_decode stores them ----
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded ----
 #pragma unroll
             for (uint32_t k = 0; k < 2u; k++) {
                 const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
                 const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
                 if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
                 V v[2][4];
-#pragma unroll
-                for (uint32_t j = 0; j < 2u; j++) {
-                    const uint32_t n = rp * 32u + 2u * cg + j;
-                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
-                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
-                    if (!(st & BS_RES)) {
-                        V dt[4];
-                        dac4<V>(gb, L, Lfull, st, dt);
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
-                    } else {
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
-                    }
-                }
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
 #pragma unroll
                 for (uint32_t i = 0; i < 2u; i++) {
                     const uint32_t r = r0 + i, a = 2u * k + i;
@@ -514,7 +273,7 @@ k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ e
                 double x[4], old[4];
 #pragma unroll
                 for (uint32_t e = 0; e < 4u; e++) {
-                    x[e] = lo[a][e] == INT32_MAX ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((lo[a][e] ^ sg) - sg));
+                    x[e] = leaf_extreme(lo[a][e], INT32_MAX, enc, C.fbits, sg);
                     old[e] = __builtin_nan("");
                 }
                 if (!U.init) plane_load4(p_min + at, old, c0, left, right);
@@ -526,7 +285,7 @@ k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ e
                 double x[4], old[4];
 #pragma unroll
                 for (uint32_t e = 0; e < 4u; e++) {
-                    x[e] = hi[a][e] == INT32_MIN ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((hi[a][e] ^ sg) - sg));
+                    x[e] = leaf_extreme(hi[a][e], INT32_MIN, enc, C.fbits, sg);
                     old[e] = __builtin_nan("");
                 }
                 if (!U.init) plane_load4(p_max + at, old, c0, left, right);
@@ -542,7 +301,7 @@ k_bulk_reduce(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ e
 int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const ReduceUnit* d_units, uint32_t n, double* d_dst, double* d_scr,
                        uint32_t ops) {
     if (n == 0) return DCDF_OK;
-    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    const dim3 grid = bulk_grid(n), block(256);
 #define K2R_REDUCE_CASE(L) \
     case L: hipLaunchKernelGGL((k_bulk_reduce<L>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_dst, d_scr, ops); break;
     switch (reduce_live(ops)) {
@@ -556,7 +315,7 @@ int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const Reduc
     return DCDF_OK;
 }
 
-// ---- reduction over space (k2r_space.h): the decode kernel with its stores replaced by one record per instant ----------------
+// ---- reduction over space (k2r_space.h): the walk's cells into one record per instant --------------------------------------
 // One instant of one selected cell into the thread's four values.  kind as in k_bulk_reduce (uniform over a unit).  m is the
 // integer the decoder divides (space_m): n itself, (float)(n - 1) -- which rounds beyond 2^24 -- or n - 1; |m| <= 2^30 here, so a
 // unit's 4096 cells stay below 2^43 in an int64.  lo / hi hold the extremes as stored integers, mirrored by sg (reduce_fold4's
@@ -578,10 +337,10 @@ __device__ __forceinline__ void space_fold1(int32_t n, bool sel, int kind, int64
 constexpr uint32_t SPACE_B = 16;  // instants whose wave results wait in LDS before one barrier flushes them
 
 // LIVE: the values this instantiation carries (RA_*; MIN and MAX go together, SUM and COUNT go together).  MASKED: the cube has
-// a mask.  A thread owns the 16 cells k_bulk_decode stores per instant; which of them count -- inside the unit's rectangle, and
-// their mask byte non-zero -- is one 16-bit word per unit (bit (2 k + i) * 4 + e), never looked up per instant.  Per instant the
-// thread folds its cells, the wave folds its lanes (__shfl_xor), and lane 0 leaves the wave's result in the instant's LDS slot;
-// every SPACE_B instants one barrier lets SPACE_B threads fold the four waves and write the records.
+// a mask.  Which of a thread's 16 cells count -- inside the unit's rectangle, and their mask byte non-zero -- is one 16-bit
+// word per unit (bulk_select16), never looked up per instant.  Per instant the thread folds its cells, the wave folds its
+// lanes (__shfl_xor), and lane 0 leaves the wave's result in the instant's LDS slot; every SPACE_B instants one barrier lets
+// SPACE_B threads fold the four waves and write the records.
 // (waves_per_eu: the allocator stays within 128 VGPRs -- k_bulk_decode's four waves per SIMD -- instead of 133-135; no scratch.)
 template <uint32_t LIVE, bool MASKED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
@@ -599,84 +358,14 @@ k_bulk_space(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ en
         const SpaceUnit U = units[u];
         const ChunkRef C = chunks[U.chunk];
         const int32_t enc = (int32_t)encs[U.chunk];
-        const int kind = enc == ENC_F32 ? 1 : enc == ENC_F64 ? 2 : 0;
-        const int32_t sg = kind != 0 && C.fbits == 62u ? -1 : 0;  // (from_fixed's divisor is negative)
+        const int kind = leaf_kind(enc);
+        const int32_t sg = leaf_mirror(kind, C.fbits);
         const gbytes gb = (gbytes)C.bytes;
-        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
-        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
-        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
-        const bool sq_in = r16 + qi < G && c16 + qj < G;
-        // the thread's selected cells
-        uint32_t sel = 0;
-#pragma unroll
-        for (uint32_t b = 0; b < 16u; b++) {
-            const uint32_t g = tid + 256u * (b >> 3), r = (uint32_t)U.rr + 2u * (g >> 4) + ((b >> 2) & 1u), c = (uint32_t)U.rc + 4u * (g & 15u) + (b & 3u);
-            bool in = r >= top && r < bottom && c >= left && c < right;
-            if constexpr (MASKED) {
-                if (in) in = ((const __attribute__((address_space(1))) uint8_t*)mask)[U.m_off + (uint64_t)(r - top) * U.m_sr + (c - left)] != 0;
-            }
-            sel |= in ? 1u << b : 0u;
-        }
+        const uint32_t sel = bulk_select16<MASKED>(U, mask, tid);  // the thread's cells that count
         uint32_t cur_snap = 0xffffffffu;
         for (uint32_t t = U.t0; t < U.t1; t++) {
-            const gdesc gD = (gdesc)C.descs + t;
-            const bool is_log = gD->is_log != 0;
-            const uint32_t snap = is_log ? gD->snap : t;
-            __syncthreads();  // (the previous instant's readers are done)
-            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
-                cur_snap = snap;
-                const TreeRef S = tree_ref((gdesc)C.descs + snap);
-                const DacDesc& Sfull = C.descs[snap].mx;
-                if (tid < 16u) {
-                    int32_t v = 0;
-                    uint32_t idx = WQ_NONE;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
-                        v = e.mt + e.ms;
-                        idx = e.bs;
-                    }
-                    pyr[BP_OFF[4] + tid] = v;
-                    nst[BN_OFF[4] + tid] = idx;
-                }
-                __syncthreads();
-                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-            }
-            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
-            const DacDesc& Lfull = C.descs[t].mx;
-            if (is_log) {
-                if (tid < 16u) {
-                    uint32_t st = BS_CONST;
-                    int32_t d = 0;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
-                        if (e.bt != WQ_NONE) {
-                            st = e.bt;
-                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
-                            st = BS_RES;
-                            d = e.mt;
-                        } else {
-                            d = e.mt + e.ms;
-                        }
-                    }
-                    nst[BN_OFF[4] + tid] = st;
-                    nd[BN_OFF[4] + tid] = d;
-                }
-                __syncthreads();
-                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-            }
-            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded where k_bulk_decode stores them ----
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded ----
             int64_t s = 0;
             uint32_t cnt = 0;
             int32_t lo = INT32_MAX, hi = INT32_MIN;  // (beyond every stored value of a narrow32 chunk: "no value yet")
@@ -686,23 +375,7 @@ k_bulk_space(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ en
                 const uint32_t sel8 = (sel >> (8u * k)) & 255u;
                 if (sel8 == 0) continue;  // (none of the group's cells counts)
                 V v[2][4];
-#pragma unroll
-                for (uint32_t j = 0; j < 2u; j++) {
-                    const uint32_t n = rp * 32u + 2u * cg + j;
-                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
-                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
-                    if (!(st & BS_RES)) {
-                        V dt[4];
-                        dac4<V>(gb, L, Lfull, st, dt);
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
-                    } else {
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
-                    }
-                }
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
 #pragma unroll
                 for (uint32_t i = 0; i < 2u; i++)
 #pragma unroll
@@ -743,8 +416,8 @@ k_bulk_space(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ en
                         (__attribute__((address_space(1))) SpacePartial*)recs + (U.rec + (uint64_t)(t - U.t0 - slot + tid));
                     o->hi = ts < 0 ? ~(uint64_t)0 : (uint64_t)0;
                     o->lo = (uint64_t)ts;
-                    o->mn = tl == INT32_MAX ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((tl ^ sg) - sg));
-                    o->mx = th == INT32_MIN ? __builtin_nan("") : reduce_widen(enc, C.fbits, (int64_t)((th ^ sg) - sg));
+                    o->mn = leaf_extreme(tl, INT32_MAX, enc, C.fbits, sg);
+                    o->mx = leaf_extreme(th, INT32_MIN, enc, C.fbits, sg);
                     o->cnt = tc;
                     o->scale = space_scale(enc, C.fbits);
                 }
@@ -757,7 +430,7 @@ k_bulk_space(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ en
 int launch_bulk_space(const ChunkRef* d_refs, const uint8_t* d_enc, const SpaceUnit* d_units, uint32_t n, const uint8_t* d_mask,
                       SpacePartial* d_recs, uint32_t live) {
     if (n == 0) return DCDF_OK;
-    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    const dim3 grid = bulk_grid(n), block(256);
     constexpr uint32_t EXT = RA_MIN | RA_MAX, ADD = RA_SUM | RA_COUNT;
     const uint32_t l = ((live & EXT) ? EXT : 0u) | ((live & ADD) ? ADD : 0u);
 #define K2R_SPACE_CASE(L)                                                                                                          \
@@ -774,7 +447,7 @@ int launch_bulk_space(const ChunkRef* d_refs, const uint8_t* d_enc, const SpaceU
     return DCDF_OK;
 }
 
-// ---- value histograms (k2r_hist.h): the decode kernel with its stores replaced by counts per instant and bin ------------------
+// ---- value histograms (k2r_hist.h): the walk's cells into counts per instant and bin ----------------------------------------
 // K2R_HIST_VARIANT (diagnostic builds for DESIGN.md section 4h only, tools/build_variant.sh; their counts are wrong on purpose):
 // 1 = the binning compiled out (no threshold search: every cell goes to the first bin), 2 = the LDS and global adds compiled out
 // (the bins are searched and folded into a register), 3 = the 16 searches of a thread one after the other instead of 8 in step.
@@ -785,12 +458,12 @@ constexpr uint32_t HIST_SLOTS = 16;     // instants whose counts wait in LDS bef
 constexpr uint32_t HIST_COUNTS = 1024;  // LDS counters: min(HIST_SLOTS, HIST_COUNTS / n_bins) instants of n_bins (4 at 256 bins)
 constexpr uint32_t HIST_THR = 512;      // entries of the largest threshold table (hist_steps(256) = 9)
 
-// MASKED: the cube has a mask.  A thread owns the 16 cells k_bulk_decode stores per instant and k_bulk_space's 16-bit word of those
-// that count.  The unit's leaf has one table of int32 thresholds (hist_thresholds32, made by the planner once per distinct encoding
-// and fractional bits), copied to LDS before the first instant; a cell's bin is a branch-free binary search of `steps` LDS reads --
-// integer compares only, nothing is widened.  The searches of a group's 8 cells advance together, step by step: a search is a
-// chain of dependent LDS reads, and 8 independent chains hide each other's latency (0.5 ms of 5.8 at 16 bins on the benchmark
-// cube).  The NaN code of a float leaf and cells outside the edges are dropped.
+// MASKED: the cube has a mask.  A thread owns its 16 cells of the walk and bulk_select16's word of those that count.  The unit's
+// leaf has one table of int32 thresholds (hist_thresholds32, made by the planner once per distinct encoding and fractional
+// bits), copied to LDS before the first instant; a cell's bin is a branch-free binary search of `steps` LDS reads -- integer
+// compares only, nothing is widened.  The searches of a group's 8 cells advance together, step by step: a search is a chain of
+// dependent LDS reads, and 8 independent chains hide each other's latency (0.5 ms of 5.8 at 16 bins on the benchmark cube,
+// DESIGN.md section 4h).  The NaN code of a float leaf and cells outside the edges are dropped.
 //
 // Smooth data puts most of a wave's cells into one bin.  A thread therefore adds a RUN of equal bins among its cells with one
 // LDS atomic; on a constant field that is one add per thread and instant.  (Combining the lanes' last runs across the wave
@@ -798,8 +471,8 @@ constexpr uint32_t HIST_THR = 512;      // entries of the largest threshold tabl
 // field, 3 % slower on real data)
 //
 // Every `slots` instants (or at the unit's end) one barrier lets the workgroup add the non-zero counters to the cube's rows --
-// device-scope 64-bit atomic adds, contiguous over (instant, bin) -- and clear them.
-// (waves_per_eu: k_bulk_space's reason; no scratch.)
+// device-scope 64-bit atomic adds, contiguous over (instant, bin) -- and clear them; the barrier bulk_instant begins the next
+// instant with puts the clears before its adds.  (waves_per_eu: k_bulk_space's reason; no scratch.)
 template <bool MASKED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_bulk_hist(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const HistUnit* __restrict__ units, uint32_t n_units,
@@ -817,86 +490,16 @@ k_bulk_hist(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ enc
         const HistUnit U = units[u];
         const ChunkRef C = chunks[U.chunk];
         const int32_t enc = (int32_t)encs[U.chunk];
-        const bool is_float = enc == ENC_F32 || enc == ENC_F64;
+        const bool is_float = leaf_kind(enc) != 0;
         const gbytes gb = (gbytes)C.bytes;
-        const uint32_t G = C.top_g, r16 = (uint32_t)U.rr >> 4, c16 = (uint32_t)U.rc >> 4;
-        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
-        const uint32_t qi = (tid >> 2) & 3u, qj = tid & 3u;
-        const bool sq_in = r16 + qi < G && c16 + qj < G;
         // the leaf's thresholds (read after the first instant's barriers; the previous unit's readers are behind its last barrier)
         for (uint32_t i = tid; i < ((uint32_t)1 << steps); i += 256u)
             s_thr[i] = ((const __attribute__((address_space(1))) int32_t*)thr)[U.thr + i];
-        // the thread's selected cells
-        uint32_t sel = 0;
-#pragma unroll
-        for (uint32_t b = 0; b < 16u; b++) {
-            const uint32_t g = tid + 256u * (b >> 3), r = (uint32_t)U.rr + 2u * (g >> 4) + ((b >> 2) & 1u), c = (uint32_t)U.rc + 4u * (g & 15u) + (b & 3u);
-            bool in = r >= top && r < bottom && c >= left && c < right;
-            if constexpr (MASKED) {
-                if (in) in = ((const __attribute__((address_space(1))) uint8_t*)mask)[U.m_off + (uint64_t)(r - top) * U.m_sr + (c - left)] != 0;
-            }
-            sel |= in ? 1u << b : 0u;
-        }
+        const uint32_t sel = bulk_select16<MASKED>(U, mask, tid);  // the thread's cells that count
         uint32_t cur_snap = 0xffffffffu, slot = 0;
         for (uint32_t t = U.t0; t < U.t1; t++) {
-            const gdesc gD = (gdesc)C.descs + t;
-            const bool is_log = gD->is_log != 0;
-            const uint32_t snap = is_log ? gD->snap : t;
-            __syncthreads();  // (the previous instant's readers are done, the flush's clears too)
-            if (snap != cur_snap) {  // a new block: its Snapshot's pyramid, once
-                cur_snap = snap;
-                const TreeRef S = tree_ref((gdesc)C.descs + snap);
-                const DacDesc& Sfull = C.descs[snap].mx;
-                if (tid < 16u) {
-                    int32_t v = 0;
-                    uint32_t idx = WQ_NONE;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)snap * G + r16 + qi) * G + c16 + qj);
-                        v = e.mt + e.ms;
-                        idx = e.bs;
-                    }
-                    pyr[BP_OFF[4] + tid] = v;
-                    nst[BN_OFF[4] + tid] = idx;
-                }
-                __syncthreads();
-                bulk_snap_level<4>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<3>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<2>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-                bulk_snap_level<1>(gb, S, Sfull, pyr, nst, tid);
-                __syncthreads();
-            }
-            const TreeRef L = tree_ref(gD);  // (only looked at when is_log)
-            const DacDesc& Lfull = C.descs[t].mx;
-            if (is_log) {
-                if (tid < 16u) {
-                    uint32_t st = BS_CONST;
-                    int32_t d = 0;
-                    if (sq_in) {
-                        const TopEnt e = top_load(C.top + ((size_t)t * G + r16 + qi) * G + c16 + qj);
-                        if (e.bt != WQ_NONE) {
-                            st = e.bt;
-                        } else if (e.bs != WQ_NONE) {  // the Log ended above ("equal", or its root): mt + s(cell)
-                            st = BS_RES;
-                            d = e.mt;
-                        } else {
-                            d = e.mt + e.ms;
-                        }
-                    }
-                    nst[BN_OFF[4] + tid] = st;
-                    nd[BN_OFF[4] + tid] = d;
-                }
-                __syncthreads();
-                bulk_log_level<4>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<3>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-                bulk_log_level<2>(gb, L, Lfull, nst, nd, tid);
-                __syncthreads();
-            }
-            // ---- nodes of side 2, two per task: their 2 x 4 cells, binned where k_bulk_decode stores them ----
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, binned ----
             uint32_t* const row = s_cnt + slot * n_bins;
             uint32_t run_bin = 0, run = 0;  // the thread's current run of equal bins
 #if K2R_HIST_VARIANT == 2
@@ -911,23 +514,7 @@ k_bulk_hist(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ enc
                 const uint32_t sel8 = (sel >> (8u * k)) & 255u;
                 if (sel8 == 0) continue;  // (none of the group's cells counts)
                 V v[2][4];
-#pragma unroll
-                for (uint32_t j = 0; j < 2u; j++) {
-                    const uint32_t n = rp * 32u + 2u * cg + j;
-                    const uint32_t st = is_log ? nst[BN_OFF[1] + n] : BS_RES;
-                    const V d = is_log ? nd[BN_OFF[1] + n] : (V)0;
-                    if (!(st & BS_RES)) {
-                        V dt[4];
-                        dac4<V>(gb, L, Lfull, st, dt);
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = dt[c] + pyr[(2u * rp + (c >> 1)) * 64u + 4u * cg + 2u * j + (c & 1u)];
-                    } else {
-#pragma unroll
-                        for (uint32_t c = 0; c < 4u; c++)
-                            v[c >> 1][2u * j + (c & 1u)] = bulk_resolved(pyr, st, d, 2u * rp + (c >> 1), 4u * cg + 2u * j + (c & 1u));
-                    }
-                }
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
                 uint32_t pos[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // hist_search32, the 8 searches in step
 #if K2R_HIST_VARIANT == 1
 #pragma unroll
@@ -990,7 +577,7 @@ int launch_bulk_hist(const ChunkRef* d_refs, const uint8_t* d_enc, const HistUni
     if (n_bins == 0 || n_bins > HIST_MAX_BINS) return DCDF_ERR_BAD_ARG;
     static_assert(((uint32_t)1 << 9) == HIST_THR && HIST_MAX_BINS + 2u <= HIST_THR, "the largest table fits s_thr");
     static_assert(HIST_COUNTS >= HIST_MAX_BINS, "one instant's counters fit s_cnt");
-    const dim3 grid(n < (1u << 20) ? n : (1u << 20)), block(256);
+    const dim3 grid = bulk_grid(n), block(256);
     const uint32_t steps = hist_steps(n_bins);
     if (d_mask) hipLaunchKernelGGL((k_bulk_hist<true>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
     else hipLaunchKernelGGL((k_bulk_hist<false>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
