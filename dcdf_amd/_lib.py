@@ -63,11 +63,14 @@ SYMBOLS = [
     "dcdf_value_bounds", "dcdf_chunk_search_values", "dcdf_query_search_values_batch", "dcdf_raster_search_values_batch",
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
     "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
-    "dcdf_raster_histogram_batch", "dcdf_histogram_bounds",
+    "dcdf_raster_histogram_batch", "dcdf_histogram_bounds", "dcdf_raster_spells_batch",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
 HIST_MAX_BINS = 256  # DCDF_HIST_MAX_BINS
+# dcdf_raster_spells_batch: the statistics, in plane order, and the "no hit" value of longest_start / first / last
+SPELL_OPS = {"count": 1, "longest": 2, "longest_start": 4, "first": 8, "last": 16}
+SPELL_NONE = 0xffffffff  # DCDF_SPELL_NONE
 
 
 def lib():
@@ -105,6 +108,9 @@ def lib():
         L.dcdf_raster_histogram_batch.restype = C.c_int
         L.dcdf_raster_histogram_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_spells_batch.restype = C.c_int
+        L.dcdf_raster_spells_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.dcdf_histogram_bounds.restype = C.c_int
         L.dcdf_histogram_bounds.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L

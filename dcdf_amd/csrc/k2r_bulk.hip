@@ -1,7 +1,7 @@
-// k2r_bulk.hip -- the four bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
-// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h).  All four walk a unit the same way; that
-// walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8, bulk_select16).  A thread
-// gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
+// k2r_bulk.hip -- the five bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
+// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h), spell statistics (k2r_spell.h).  All five
+// walk a unit the same way; that walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8,
+// bulk_select16).  A thread gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
 #include <hip/hip_runtime.h>
 
 #include "k2r_bulk_walk.h"
@@ -9,6 +9,7 @@
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
 #include "k2r_space.h"
+#include "k2r_spell.h"
 
 namespace k2r {
 
@@ -581,6 +582,150 @@ int launch_bulk_hist(const ChunkRef* d_refs, const uint8_t* d_enc, const HistUni
     const uint32_t steps = hist_steps(n_bins);
     if (d_mask) hipLaunchKernelGGL((k_bulk_hist<true>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
     else hipLaunchKernelGGL((k_bulk_hist<false>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- spell statistics (k2r_spell.h): the walk's cells into per-cell run states ----------------------------------------------
+// plane_load4's rule in its 4-byte form: one 16-byte access when the four cells are inside and p is aligned, single elements
+// otherwise.
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void plane_load4u(const uint32_t* p, uint32_t (&v)[4], uint32_t c0, uint32_t left, uint32_t right) {
+    if (c0 >= left && c0 + 4u <= right && ((uintptr_t)p & 15u) == 0) {
+        const u32x4_t a = *(const __attribute__((address_space(1))) u32x4_t*)p;
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (c0 + (uint32_t)e >= left && c0 + (uint32_t)e < right) v[e] = ((const __attribute__((address_space(1))) uint32_t*)p)[e];
+    }
+}
+__device__ __forceinline__ void plane_store4u(uint32_t* p, const uint32_t (&v)[4], uint32_t c0, uint32_t left, uint32_t right) {
+    if (c0 >= left && c0 + 4u <= right && ((uintptr_t)p & 15u) == 0) {
+        *(__attribute__((address_space(1))) u32x4_t*)p = u32x4_t{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (c0 + (uint32_t)e >= left && c0 + (uint32_t)e < right) ((__attribute__((address_space(1))) uint32_t*)p)[e] = v[e];
+    }
+}
+// one state word of four cells of a row, between its plane and the threads' SpellStates
+#define K2R_SPELL_LOAD(plane, field)                                                      \
+    {                                                                                     \
+        uint32_t w[4] = {st[a][0].field, st[a][1].field, st[a][2].field, st[a][3].field}; \
+        plane_load4u((plane) + at, w, c0, left, right);                                   \
+        _Pragma("unroll") for (uint32_t e = 0; e < 4u; e++) st[a][e].field = w[e];        \
+    }
+#define K2R_SPELL_STORE(plane, field)                                                           \
+    {                                                                                           \
+        const uint32_t w[4] = {st[a][0].field, st[a][1].field, st[a][2].field, st[a][3].field}; \
+        plane_store4u((plane) + at, w, c0, left, right);                                        \
+    }
+
+// GROUPS: the state this instantiation carries -- SG_COUNT: count; SG_RUNS: cur, longest, lstart; SG_ENDS: first, last.  A thread
+// owns the same 16 cells at every instant (its two tasks of 2 rows x 4 columns, bulk_cells8); their SpellStates stay in registers
+// over the unit's instants and every instant is one spell_step per cell: integer compares with the leaf's range (spell_hit32),
+// nothing is widened.  The state continues the planes': it is loaded before the first instant (spell_init when the unit starts
+// its cube) and stored after the last.  Words of a group that is not carried are never loaded nor stored, so their updates are
+// dead code.  Within a carried group a plane the caller did not ask for lives in scratch (spell_plane); FIRST without LAST (or the
+// reverse) is carried in registers but only the requested plane is touched.  Cells outside the unit's rectangle are decoded as in
+// k_bulk_decode; their rows are not accumulated and nothing of them is written.
+template <uint32_t GROUPS>
+__global__ void __launch_bounds__(256)
+k_bulk_spell(const ChunkRef* __restrict__ chunks, const SpellUnit* __restrict__ units, uint32_t n_units, uint32_t* dst, uint32_t* scr, uint32_t ops) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const SpellUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        const int32_t lo = U.lo, hi = U.hi;
+        const uint32_t flags = U.flags;
+        uint32_t* const p_cnt = spell_plane(SP_COUNT, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t* const p_lng = spell_plane(SP_LONGEST, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t* const p_lst = spell_plane(SP_LSTART, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t* const p_fst = spell_plane(SP_FIRST, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t* const p_las = spell_plane(SP_LAST, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t* const p_cur = spell_plane(SP_CUR, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        // states of row 2 k + i of the thread's cells
+        SpellState st[4][4];
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; a++) {
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) st[a][e] = spell_init();
+            const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+            if (!U.init && r >= top && r < bottom && c0 + 4u > left && c0 < right) {
+                const int64_t at = (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left);
+                if constexpr ((GROUPS & SG_COUNT) != 0) K2R_SPELL_LOAD(p_cnt, count)
+                if constexpr ((GROUPS & SG_RUNS) != 0) {
+                    K2R_SPELL_LOAD(p_cur, cur)
+                    K2R_SPELL_LOAD(p_lng, longest)
+                    if (ops & SP_LSTART) K2R_SPELL_LOAD(p_lst, lstart)
+                }
+                if constexpr ((GROUPS & SG_ENDS) != 0) {
+                    if (ops & SP_FIRST) K2R_SPELL_LOAD(p_fst, first)
+                    if (ops & SP_LAST) K2R_SPELL_LOAD(p_las, last)
+                }
+            }
+        }
+        uint32_t cur_snap = 0xffffffffu;
+        for (uint32_t t = U.t0; t < U.t1; t++) {
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+            const uint32_t ti = U.dt + (t - U.t0);  // counted from the cube's first instant
+            // ---- nodes of side 2, two per task: their 2 x 4 cells, folded ----
+#pragma unroll
+            for (uint32_t k = 0; k < 2u; k++) {
+                const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
+                if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
+                V v[2][4];
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
+#pragma unroll
+                for (uint32_t i = 0; i < 2u; i++) {
+                    const uint32_t r = r0 + i, a = 2u * k + i;
+                    if (r < top || r >= bottom) continue;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4u; c++) spell_step(st[a][c], ti, spell_hit32(v[i][c], lo, hi, flags));
+                }
+            }
+        }
+        // ---- the unit's states into the planes ----
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; a++) {
+            const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+            if (r < top || r >= bottom || c0 + 4u <= left || c0 >= right) continue;
+            const int64_t at = (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left);
+            if constexpr ((GROUPS & SG_COUNT) != 0) K2R_SPELL_STORE(p_cnt, count)
+            if constexpr ((GROUPS & SG_RUNS) != 0) {
+                K2R_SPELL_STORE(p_cur, cur)
+                K2R_SPELL_STORE(p_lng, longest)
+                if (ops & SP_LSTART) K2R_SPELL_STORE(p_lst, lstart)
+            }
+            if constexpr ((GROUPS & SG_ENDS) != 0) {
+                if (ops & SP_FIRST) K2R_SPELL_STORE(p_fst, first)
+                if (ops & SP_LAST) K2R_SPELL_STORE(p_las, last)
+            }
+        }
+        __syncthreads();
+    }
+}
+#undef K2R_SPELL_LOAD
+#undef K2R_SPELL_STORE
+
+int launch_bulk_spell(const ChunkRef* d_refs, const SpellUnit* d_units, uint32_t n, uint32_t* d_dst, uint32_t* d_scr, uint32_t ops) {
+    if (n == 0) return DCDF_OK;
+    const dim3 grid = bulk_grid(n), block(256);
+#define K2R_SPELL_CASE(G) \
+    case G: hipLaunchKernelGGL((k_bulk_spell<G>), grid, block, 0, 0, d_refs, d_units, n, d_dst, d_scr, ops); break;
+    switch (spell_groups(ops)) {
+        K2R_SPELL_CASE(1) K2R_SPELL_CASE(2) K2R_SPELL_CASE(3) K2R_SPELL_CASE(4) K2R_SPELL_CASE(5) K2R_SPELL_CASE(6) K2R_SPELL_CASE(7)
+        default: return DCDF_ERR_BAD_ARG;
+    }
+#undef K2R_SPELL_CASE
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

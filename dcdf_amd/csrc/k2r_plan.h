@@ -1,5 +1,5 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram: k2r_raster_region.hip) turn a
-// batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells: k2r_raster_region.hip)
+// turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
 // A cube is cut into pieces, one per leaf it meets (raster_pieces).  A piece is of one of three kinds: on an elided leaf (one
 // value per instant: dcdf_raster::d_vals), on a chunk the bulk kernels take (side-16 table, 32-bit values) -- it becomes one unit
@@ -16,6 +16,7 @@
 #include "k2r_items.h"
 #include "k2r_reduce.h"
 #include "k2r_space.h"
+#include "k2r_spell.h"
 
 // an elided piece of a decode: one value per instant over a rectangle of the window (k_raster_fill_const; outside the namespace,
 // where the kernels' mangled names have it)
@@ -466,6 +467,100 @@ inline int plan_histogram(const PlanRaster& g, const dcdf_cube* cubes, size_t nq
     P.walk.flush();
     // each part of a split unit adds to its own instants' rows
     plan_time_split(P.units, 0, wanted, [n_bins](HistUnit& v, uint32_t dt) { v.o_off += (uint64_t)dt * n_bins; });
+    return DCDF_OK;
+}
+
+// ---- spell statistics --------------------------------------------------------------------------------------------------------
+// plan_reduce_time's shape: the segments one after the other in ascending order (SegRange), within a segment one piece per cell,
+// each piece continuing the run state its cells' planes hold.  A unit's instants are never split over workgroups (no
+// plan_time_split): two workgroups on the same cells would have to merge runs.  lower[q] / upper[q] are translated once per
+// (cube, encoding, fractional bits) into the leaf's stored integers (value_bounds).  base[q] / sbase[q]: cube q's first output /
+// scratch plane.
+struct SpellPlan {
+    std::vector<SpellUnit> units;
+    std::vector<SpellFold> cfolds;
+    SlabCutter<SpellFold> walk;
+    std::vector<SegRange> ranges;
+    uint64_t stats[3] = {0, 0, 0};
+    explicit SpellPlan(uint64_t slab_cap) : walk(slab_cap) {}
+};
+inline int plan_spells(const PlanRaster& g, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq, const uint64_t* base,
+                       const uint64_t* sbase, bool node_wise, SpellPlan& P) {
+    struct Segment {
+        std::vector<SpellUnit> units;
+        std::vector<SpellFold> consts;
+        std::vector<WalkPiece<SpellFold>> walks;
+    };
+    struct LeafRange {
+        int32_t enc;
+        uint32_t fbits;
+        ValueRange vr;
+    };
+    std::vector<Segment> segs((g.T + g.cs - 1) / g.cs);
+    std::vector<LeafRange> cache;  // of one cube: a raster has few distinct (encoding, fractional bits)
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if (lower[q] != lower[q] || upper[q] != upper[q]) return DCDF_ERR_BAD_ARG;
+        if (cube_cells(c) == 0) continue;
+        cache.clear();
+        bool bad = false;
+        plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+            size_t at = 0;
+            while (at < cache.size() && (cache[at].enc != p.enc || cache[at].fbits != p.fbits)) at++;
+            if (at == cache.size()) {
+                cache.push_back(LeafRange{p.enc, p.fbits, ValueRange{}});
+                if (!value_bounds(p.enc, p.fbits, lower[q], upper[q], &cache[at].vr)) bad = true;
+            }
+            const ValueRange& vr = cache[at].vr;
+            Segment& S = segs[p.t0 / g.cs];
+            const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
+            const SpellRange64 r64 = spell_range64(vr);
+            const SpellFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
+                              (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc, p.dt, r64.flags, r64.lo, r64.hi};
+            if (p.kind == PIECE_CONST) S.consts.push_back(f);
+            else if (p.kind == PIECE_WALK) S.walks.push_back(WalkPiece<SpellFold>{p.leaf, p.k, f});
+            else {
+                const SpellRange32 r32 = spell_range32(vr);
+                plan_units(p, S.units, [&](SpellUnit& u) {
+                    u.sr = (uint32_t)wc;
+                    u.init = init;
+                    u.dt = p.dt;
+                    u.lo = r32.lo;
+                    u.hi = r32.hi;
+                    u.flags = r32.flags;
+                    u.o_off = f.o_off + unit_in_piece(u, p, wc);
+                    u.s_off = f.s_off + unit_in_piece(u, p, wc);
+                    u.psz = wr * wc;
+                });
+            }
+        });
+        if (bad) return DCDF_ERR_BAD_ARG;
+    }
+    for (Segment& S : segs) {
+        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
+        SegRange r{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0};
+        P.units.insert(P.units.end(), S.units.begin(), S.units.end());
+        P.cfolds.insert(P.cfolds.end(), S.consts.begin(), S.consts.end());
+        for (const WalkPiece<SpellFold>& w : S.walks)
+            P.walk.add(w.f.nt, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t a, uint32_t b, uint64_t src) {
+                SpellFold f = w.f;  // a part cut in time: its own slab, its own first instant
+                f.nt = b - a;
+                f.init = w.f.init && a == 0;
+                f.dt = w.f.dt + a;
+                f.src = src;
+                window_items(w.chunk, cube_instants(w.k, a, b), src, P.walk.items, node_wise);
+                P.walk.folds.push_back(f);
+            });
+        P.walk.flush();  // (a slab never spans two segments)
+        r.unit1 = P.units.size();
+        r.const1 = P.cfolds.size();
+        r.slab1 = P.walk.slabs.size();
+        P.ranges.push_back(r);
+        S = Segment{};
+        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull)
+            return DCDF_ERR_CAPACITY;
+    }
     return DCDF_OK;
 }
 

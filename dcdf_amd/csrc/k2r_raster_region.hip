@@ -1,5 +1,5 @@
-// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, reduce
-// over space, histogram -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, spell
+// statistics, reduce over space, histogram -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,7 @@
 
 using namespace k2r;
 
-// ---- what the four calls share -----------------------------------------------------------------------------------------------
+// ---- what the five calls share -----------------------------------------------------------------------------------------------
 // Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
 // error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
 enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
@@ -241,6 +241,103 @@ extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cu
         hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
                            dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr.as<double>(), ops);
         K2R_HIP(hipGetLastError());
+    }
+    return batch_epilogue(W, ev, true, kernel_ms);
+}
+// ---- spell statistics: per cell, the hits of a value range over time and their runs (k2r_spell.h) -----------------------------
+// reduce_time's shape: plan_spells (k2r_plan.h) gives the segments in ascending order, launched one after the other on the null
+// stream; every piece continues the run state its cells' planes hold.  The state planes are the output planes themselves (cube
+// q's requested planes in ascending bit order); cur, and LONGEST kept for LONGEST_START alone, live in pooled scratch planes.
+//
+// A thread per cell of a fallback piece (the window walk's slab of stored integers) or of an elided piece (one value per instant
+// from dcdf_raster::d_vals): its instants in order through spell_step, the hit test on the stored integer itself.
+__global__ void __launch_bounds__(256)
+k_spell_fold(const SpellFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, uint32_t* dst,
+             uint32_t* scr, uint32_t ops) {
+    const uint32_t live = spell_live(ops);
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const SpellFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols;
+        uint32_t* const p_cnt = spell_plane(SP_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        uint32_t* const p_lng = spell_plane(SP_LONGEST, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        uint32_t* const p_lst = spell_plane(SP_LSTART, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        uint32_t* const p_fst = spell_plane(SP_FIRST, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        uint32_t* const p_las = spell_plane(SP_LAST, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        uint32_t* const p_cur = spell_plane(SP_CUR, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
+            const uint64_t at = e / P.cols * P.sr + e % P.cols;
+            SpellState s = spell_init();
+            if (!P.init) {
+                if (live & SP_COUNT) s.count = p_cnt[at];
+                if (live & SP_LONGEST) s.longest = p_lng[at];
+                if (live & SP_LSTART) s.lstart = p_lst[at];
+                if (live & SP_FIRST) s.first = p_fst[at];
+                if (live & SP_LAST) s.last = p_las[at];
+                if (live & SP_CUR) s.cur = p_cur[at];
+            }
+            for (uint32_t t = 0; t < P.nt; t++) {
+                int64_t v = P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e];
+                if (P.enc == ENC_I32) v = (int64_t)(int32_t)v;  // (store_typed's conversion)
+                spell_step(s, P.dt + t, spell_hit64(v, P.lo, P.hi, P.flags));
+            }
+            if (live & SP_COUNT) p_cnt[at] = s.count;
+            if (live & SP_LONGEST) p_lng[at] = s.longest;
+            if (live & SP_LSTART) p_lst[at] = s.lstart;
+            if (live & SP_FIRST) p_fst[at] = s.first;
+            if (live & SP_LAST) p_las[at] = s.last;
+            if (live & SP_CUR) p_cur[at] = s.cur;
+        }
+    }
+}
+static void launch_spell_fold(const SpellFold* d_ps, size_t n, const int64_t* d_slab, const int64_t* d_vals, uint32_t* d_dst, uint32_t* d_scr,
+                              uint32_t ops) {
+    if (n) hipLaunchKernelGGL(k_spell_fold, dim3((uint32_t)std::min<size_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, (uint32_t)n, d_slab, d_vals, d_dst, d_scr, ops);
+}
+extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
+                                        uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    bool own = ops != 0 && ops <= SP_ALL && (nq == 0 || (lower && upper));
+    for (size_t q = 0; own && q < nq && q <= 0x7fffffffu; q++) own = lower[q] == lower[q] && upper[q] == upper[q];  // a NaN bound
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    const uint32_t live = spell_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
+    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
+    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
+    std::vector<uint64_t> sbase(nq, 0);
+    uint64_t scr_total = 0;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
+        sbase[q] = scr_total;
+        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
+    }
+    WindowOut W(planes.data(), nq, out, out_offset, sizeof(uint32_t), out_mem == DCDF_MEM_DEVICE);
+    SpellPlan P(reduce_slab_cells());
+    rc = plan_spells(r->plan(), cubes, lower, upper, nq, W.base.data(), sbase.data(), r->all_node, P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_scr;
+    WalkDev D;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    uint32_t* const d_dst = (uint32_t*)W.dst();
+    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(uint32_t)));
+    rc = upload_some(d_units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
+    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (rc != DCDF_OK) return rc;
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    for (const SegRange& g : P.ranges) {
+        launch_spell_fold(d_cfolds.as<SpellFold>() + g.const0, g.const1 - g.const0, nullptr, r->d_vals.as<int64_t>(), d_dst, d_scr.as<uint32_t>(), ops);
+        K2R_HIP(hipGetLastError());
+        rc = launch_bulk_spell(r->d_refs.as<ChunkRef>(), d_units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr.as<uint32_t>(), ops);
+        if (rc == DCDF_OK)
+            rc = D.run(r, P.walk.slabs, g.slab0, g.slab1, [&](const Slab& b) {
+                launch_spell_fold(D.folds.as<SpellFold>() + b.fold0, b.fold1 - b.fold0, D.slab.as<int64_t>(), nullptr, d_dst, d_scr.as<uint32_t>(), ops);
+            });
+        if (rc != DCDF_OK) return rc;
     }
     return batch_epilogue(W, ev, true, kernel_ms);
 }

@@ -395,6 +395,24 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return {n: np.full((bottom - top, right - left), 0.0 if n in ("sum", "count") else np.nan) for n in names}
         return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
 
+    def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
+        [rows, cols] uint32} for the names of `ops` ("count", "longest", "longest_start", "first", "last", or a DCDF_SPELL_*
+        bitmask).  Instant i, counted from `start`, is a hit when the value window() returns lies in [lower, upper] (search_values'
+        rule: NaN never hits, +-inf is unbounded); count = the hits, longest = the longest unbroken run of hits, longest_start =
+        where the first such run began, first / last = the first / last hit; SPELL_NONE (0xffffffff) where nothing hit.  Through
+        raster().spells: the encoded bytes are read once on the GPU and only the planes are written (dcdf_raster_spells_batch)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        bottom = R if bottom is None else bottom
+        right = Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        from .raster import EncodedRaster
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            EncodedRaster._spell_bounds(lower, upper, 1)
+            return EncodedRaster._spells_none(EncodedRaster.spell_ops(ops)[1], bottom - top, right - left)
+        return self.raster().spells(lower, upper, ops, start, stop, window=(top, bottom, left, right))
+
     def reduce_space(self, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
         """Per-instant statistics over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
         ([rows, cols] of the window, boolean or uint8) is non-zero when a mask is given: {name: ndarray [stop - start] float64} for

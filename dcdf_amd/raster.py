@@ -211,6 +211,89 @@ class EncodedRaster:
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
     @staticmethod
+    def spell_ops(ops):
+        """ops of spells / spells_flat as (bitmask, names in plane order): a DCDF_SPELL_* bitmask, one name or an iterable of
+        "count" / "longest" / "longest_start" / "first" / "last"."""
+        if isinstance(ops, (int, np.integer)):
+            mask = int(ops)
+        else:
+            mask = 0
+            for name in ([ops] if isinstance(ops, str) else ops):
+                if name not in L.SPELL_OPS:
+                    raise ValueError("spells: unknown statistic %r (one of %s)" % (name, ", ".join(L.SPELL_OPS)))
+                mask |= L.SPELL_OPS[name]
+        if not 0 < mask < 32:
+            raise ValueError("spells: ops %r is not a set of count, longest, longest_start, first, last" % (ops,))
+        return mask, [n for n, b in L.SPELL_OPS.items() if mask & b]
+
+    @staticmethod
+    def _spell_bounds(lower, upper, n):
+        """One (lower, upper) pair per cube as float64 arrays; a scalar is shared by all cubes.  NaN is refused."""
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,)))
+        if np.isnan(lo).any() or np.isnan(hi).any():
+            raise ValueError("spells: a NaN bound")
+        return lo, hi
+
+    def spells_flat(self, cubes, lower, upper, ops, out_device_ptr=None, out_offset=None):
+        """Per-cell spell statistics of dataset-level cubes [n, 6] through dcdf_raster_spells_batch: instant i of a cell (counted
+        from the cube's first) is a hit when its value lies in [lower[q], upper[q]] by value search's rule (search_values_flat:
+        NaN never hits, integer leaves compare exactly, +-inf is unbounded); cube q yields one [rows, cols] uint32 plane per
+        statistic of `ops` (spell_ops), in the order count, longest, longest_start, first, last; SPELL_NONE where there is no hit.
+        lower / upper: one value per cube, or a scalar for all.  Host form: returns (flat uint32 array, offsets uint64[n], kernel
+        ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset in
+        elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
+        leaves."""
+        mask, names = self.spell_ops(ops)
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        lo, hi = self._spell_bounds(lower, upper, len(q))
+        ms = C.c_float()
+        stats = np.zeros(3, dtype=np.uint64)
+        if out_device_ptr is None:
+            empty = (q[:, 1] == q[:, 0])
+            vol = np.abs((q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64) * np.uint64(len(names))
+            vol[empty] = 0  # (a cube without instants writes nothing)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = np.empty(max(1, int(vol.sum())), dtype=np.uint32)
+            L.check(L.lib().dcdf_raster_spells_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
+                                                     C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), C.c_void_p(out.ctypes.data),
+                                                     L.MEM_HOST, C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
+                    "raster_spells_batch")
+            return out, off, ms.value, stats
+        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_spells_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
+                                                 C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), C.c_void_p(out_device_ptr),
+                                                 L.MEM_DEVICE, C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
+                "raster_spells_batch")
+        return ms.value, stats
+
+    @staticmethod
+    def _spells_none(names, rows, cols):
+        return {n: np.full((rows, cols), 0 if n in ("count", "longest") else L.SPELL_NONE, dtype=np.uint32) for n in names}
+
+    def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, window=None):
+        """{statistic: ndarray [rows, cols] uint32} of the hits of [lower, upper] over the instants [start, stop) of the whole
+        raster, or of `window` = (top, bottom, left, right); instants are counted from `start`.  Without instants: zeros for count
+        and longest, SPELL_NONE for the others."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
+        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
+            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        mask, names = self.spell_ops(ops)
+        self._spell_bounds(lower, upper, 1)
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            return self._spells_none(names, rows, cols)
+        out, _, _, _ = self.spells_flat([[start, stop, top, bottom, left, right]], lower, upper, mask)
+        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+
+    @staticmethod
     def _mask_args(q, masks, what):
         """The mask arguments of dcdf_raster_reduce_space_batch / dcdf_raster_histogram_batch for the cubes q: (pointer, offsets,
         memory kind, what must stay alive over the call).  masks as reduce_space_flat documents them."""

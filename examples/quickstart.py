@@ -28,6 +28,18 @@ assert list(maps) == ["max", "count", "mean"] and (maps["max"] == a[8:24].max(0)
 assert (maps["mean"] == a[8:24].sum(0) / 16.0).all()
 flat, offsets, _, stats = R.reduce_time_flat([(0, 32, 10, 200, 0, 256)], ("min", "sum"))
 assert (flat.reshape(2, 190, 256) == np.stack([a[:, 10:200].min(0), a[:, 10:200].sum(0)])).all()
+spell = R.spells(500, np.inf, ("count", "longest", "first"), 8, 24)  # instants counted from 8; 0xffffffff where nothing hit
+hit = a[8:24] >= 500
+cur = np.zeros((256, 256), dtype=np.int64)
+best = cur.copy()
+for t in range(16):
+    cur = np.where(hit[t], cur + 1, 0)
+    best = np.maximum(best, cur)
+assert list(spell) == ["count", "longest", "first"] and (spell["count"] == hit.sum(0)).all() and (spell["longest"] == best).all()
+assert (spell["first"] == np.where(hit.any(0), hit.argmax(0), 0xffffffff)).all()
+flat, offsets, _, stats = R.spells_flat([(0, 32, 10, 200, 0, 256)], [99.5], [110.25], ("count", "last"))
+band = (a[:, 10:200] >= 100) & (a[:, 10:200] <= 110)
+assert (flat.reshape(2, 190, 256)[0] == band.sum(0)).all() and (flat.reshape(2, 190, 256)[1][band[31]] == 31).all()
 series = R.reduce_space(("mean", "max", "count"), 8, 24, window=(10, 200, 0, 256))
 assert list(series) == ["max", "count", "mean"] and (series["max"] == a[8:24, 10:200].max((1, 2))).all() and (series["count"] == 190 * 256).all()
 disc = (np.mgrid[0:256, 0:256][0] - 128) ** 2 + (np.mgrid[0:256, 0:256][1] - 128) ** 2 < 100 ** 2

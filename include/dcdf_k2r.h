@@ -270,6 +270,33 @@ int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_
 enum { DCDF_REDUCE_MIN = 1, DCDF_REDUCE_MAX = 2, DCDF_REDUCE_SUM = 4, DCDF_REDUCE_COUNT = 8, DCDF_REDUCE_MEAN = 16 };
 int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
                                   const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
+ * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
+ * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
+ * swapped, stats are the numbers dcdf_raster_decode_batch reports for the same cubes, a cube of zero volume writes nothing,
+ * nq == 0 is fine, stats and kernel_ms may be NULL.  lower[q] / upper[q] are cube q's own bounds, in HOST memory: reversed bounds
+ * are swapped, +-inf is unbounded, a NaN bound is DCDF_ERR_BAD_ARG.
+ *   hit     instant i of a cell -- i counts from the cube's first instant, after normalisation -- is a hit iff the cell's stored
+ *           integer lies in the set dcdf_value_bounds returns for the encoding and fractional bits of the leaf that holds the
+ *           cell: [lo, hi], less 0 when skip_zero.  It is value search's rule and nothing else: a float leaf's NaN never hits, an
+ *           integer leaf compares n itself with [ceil(lower), floor(upper)] (never rounded to double), a hit is exactly a cell
+ *           dcdf_raster_search_values_batch reports for the same bounds, and an elided leaf uses its per-instant value with the
+ *           eliding node's encoding and bits.
+ * Per cell, over i ascending, with cur = the length of the run of hits that ends at i:
+ *   DCDF_SPELL_COUNT          the number of hits
+ *   DCDF_SPELL_LONGEST        the largest cur reached; 0 when there is no hit
+ *   DCDF_SPELL_LONGEST_START  the i at which the first run of that length began (the state changes only when cur > longest: on
+ *                             ties the earliest run wins); DCDF_SPELL_NONE when there is no hit
+ *   DCDF_SPELL_FIRST / LAST   the first / last i that hit; DCDF_SPELL_NONE when there is none
+ * Cube q writes popcount(ops) planes in ascending bit order, each dense [rows][cols] uint32, from out + out_offset[q] (elements),
+ * host or device memory; nothing outside a cube's planes is written.  All of it is one sequential integer fold per cell whose
+ * state every piece of the work hands on, so the result depends on no cut of the work.
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 16; a NaN bound; NULL r, cubes, lower, upper, out or out_offset with nq > 0; an
+ * unknown out_mem.  DCDF_ERR_BOUNDS: a cube outside the raster.  DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+enum { DCDF_SPELL_COUNT = 1, DCDF_SPELL_LONGEST = 2, DCDF_SPELL_LONGEST_START = 4, DCDF_SPELL_FIRST = 8, DCDF_SPELL_LAST = 16 };
+#define DCDF_SPELL_NONE 0xffffffffu
+int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
+                             uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
 /* Reduce over space: per instant of each cube, statistics over its SELECTED cells -- a series over an area.  The call takes
  * plain and tiled rasters.  Cube q is [start, end) x [top, bottom) x [left, right) (reversed bounds are swapped); its cell (r, c)
  * is selected when mask == NULL, or when the byte mask[mask_offset[q] + (r - top) * cols + (c - left)] is non-zero: a dense
