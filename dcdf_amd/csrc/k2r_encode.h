@@ -1493,9 +1493,22 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
                 request_t(0, tn);
                 if (K2R_LEAN_PREFETCH == 1) request_w(0, wn);
 #endif
+                // Wave priority by progress (ex.prio: sixteen-wave workgroups only).  All waves do the same work here, yet with equal
+                // priorities a SIMD's issue slots go to its oldest wave first and the quarters of the workgroup finish a third apart
+                // (17 / 19 / 22 / 26 K cycles), the barrier waiting for the last.  A wave enters pass p at priority 3 - p: one that
+                // is a pass behind outranks the waves ahead of it on its SIMD, the finishing times close up, and every wave is
+                // back at 0 when it leaves the loop -- so at the barrier, at the `perr` exit behind it and in all other phases.
+                // (p is a constant once the loop is unrolled; straight-line code of the phase, the same for all lanes.)
+                auto ladder = [&](int p) {
+                    if (p == 0) ex.template prio<3>();
+                    else if (p == 1) ex.template prio<2>();
+                    else if (p == 2) ex.template prio<1>();
+                    else ex.template prio<0>();
+                };
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
                     sched_fence();
+                    ladder(p);
                     const uint32_t B = (ltid & ~63u) + BPP * (uint32_t)p + (lane >> 2);  // the block, and its owner's thread index
                     int32_t t[16];
                     uint32_t w[8];

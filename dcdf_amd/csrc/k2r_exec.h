@@ -133,6 +133,19 @@ struct GpuExec {
         f(tid, r);
     }
     __device__ __forceinline__ void barrier() { lds_barrier(); }
+
+    // Issue priority of the calling WAVE, 0 (the default) .. 3: where a SIMD holds several waves of the workgroup its VALU issue
+    // goes to the wave of the highest priority first and by age among equals, so without this the wave dispatched last takes the
+    // slots the older ones leave.  Emitted only for such workgroups (more than four waves); nothing elsewhere.
+    // s_setprio is a scalar instruction and ignores EXEC: call this under wave-uniform control flow only -- the straight-line code
+    // of a phase, or a branch on a readfirstlane'd value (a scalar branch around it).  Under a per-lane `if` the branch becomes an
+    // EXEC mask, the instruction runs whatever the mask holds, and every wave silently gets the priority.
+    static constexpr bool kPrio = NT / 64 > 4;
+    template <int P>
+    __device__ __forceinline__ void prio() {
+        static_assert(P >= 0 && P <= 3, "s_setprio takes 0..3");
+        if constexpr (kPrio) __builtin_amdgcn_s_setprio(P);
+    }
     // diagnostic builds only: attribute the cycles since the previous stamp to phase k (thread 0's view)
     __device__ __forceinline__ void stamp(int k) {
 #ifdef K2R_PROFILE
@@ -442,6 +455,8 @@ struct SimExec {
         for (int t = 0; t < NT; t++) f(t, regs[t]);
     }
     void barrier() {}
+    template <int P>
+    void prio() {}  // (threads run one after another: nothing to arbitrate)
     void wave_lds_fence() {}
     void barrier_global() {}
     void publish(uint32_t* flag, uint32_t value, uint32_t payload) {
