@@ -64,6 +64,7 @@ SYMBOLS = [
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
     "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
     "dcdf_raster_histogram_batch", "dcdf_histogram_bounds", "dcdf_raster_spells_batch",
+    "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -71,6 +72,7 @@ HIST_MAX_BINS = 256  # DCDF_HIST_MAX_BINS
 # dcdf_raster_spells_batch: the statistics, in plane order, and the "no hit" value of longest_start / first / last
 SPELL_OPS = {"count": 1, "longest": 2, "longest_start": 4, "first": 8, "last": 16}
 SPELL_NONE = 0xffffffff  # DCDF_SPELL_NONE
+ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
 
 
 def lib():
@@ -111,6 +113,11 @@ def lib():
         L.dcdf_raster_spells_batch.restype = C.c_int
         L.dcdf_raster_spells_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_int,
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_zonal_batch.restype = C.c_int
+        L.dcdf_raster_zonal_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_zonal_fold_limbs.restype = C.c_int
+        L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.dcdf_histogram_bounds.restype = C.c_int
         L.dcdf_histogram_bounds.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L
@@ -128,6 +135,18 @@ def space_fold_records(records):
     out = C.c_double()
     check(lib().dcdf_space_fold_records(hi.ctypes.data if n else None, lo.ctypes.data if n else None, sc.ctypes.data if n else None, n,
                                         C.byref(out)), "space_fold_records")
+    return out.value
+
+
+def zonal_fold_limbs(limbs):
+    """dcdf_zonal_fold_limbs (host only, no GPU): six int64 counters, limb i weighing 2^(32 i).  Returns their total / 2^63 as the
+    nearest double, ties to even."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(limbs, dtype=np.int64))
+    if a.shape != (6,):
+        raise ValueError("zonal_fold_limbs: six limbs")
+    out = C.c_double()
+    check(lib().dcdf_zonal_fold_limbs(a.ctypes.data, C.byref(out)), "zonal_fold_limbs")
     return out.value
 
 

@@ -1,5 +1,6 @@
-// k2r_bulk.hip -- the five bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
-// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h), spell statistics (k2r_spell.h).  All five
+// k2r_bulk.hip -- the six bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
+// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h), spell statistics (k2r_spell.h), zonal
+// statistics (k2r_zonal.h).  All six
 // walk a unit the same way; that walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8,
 // bulk_select16).  A thread gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include "k2r_runtime.h"
 #include "k2r_space.h"
 #include "k2r_spell.h"
+#include "k2r_zonal.h"
 
 namespace k2r {
 
@@ -582,6 +584,265 @@ int launch_bulk_hist(const ChunkRef* d_refs, const uint8_t* d_enc, const HistUni
     const uint32_t steps = hist_steps(n_bins);
     if (d_mask) hipLaunchKernelGGL((k_bulk_hist<true>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
     else hipLaunchKernelGGL((k_bulk_hist<false>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_mask, d_thr, n_bins, steps, d_out);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- zonal statistics (k2r_zonal.h): the walk's cells into one accumulator entry per (zone, instant) -----------------------
+// The label of the thread's cell b (bulk_select16's numbering and addresses, 2-byte elements): ZONAL_NONE outside the unit's
+// rectangle or for a label that names no zone.
+__device__ __forceinline__ uint32_t zonal_label(const ZonalUnit& U, const uint16_t* labels, uint32_t n_zones, uint32_t tid, uint32_t b) {
+    const uint32_t g = tid + 256u * (b >> 3), r = (uint32_t)U.rr + 2u * (g >> 4) + ((b >> 2) & 1u), c = (uint32_t)U.rc + 4u * (g & 15u) + (b & 3u);
+    if (!(r >= U.top && r < U.bottom && c >= U.left && c < U.right)) return ZONAL_NONE;
+    const uint32_t l = ((const __attribute__((address_space(1))) uint16_t*)labels)[U.m_off + (uint64_t)(r - U.top) * U.m_sr + (c - U.left)];
+    return l < n_zones ? l : ZONAL_NONE;
+}
+
+// LIVE: the values this instantiation carries (k_bulk_space's groups: MIN and MAX go together, SUM and COUNT go together; the
+// count is always kept, it says which entries hold anything).  A unit has one leaf, so inside it the sums are int64 sums of m and
+// the extremes mirrored int32 keys, as in k_bulk_space; what differs is where a cell's value goes.
+//
+// Per unit: the distinct labels of its selected cells are ranked -- a bitmap of 65536 bits in the first 8 KB of `pyr`, which is
+// dead until bulk_instant refills it, and a popcount scan behind it (zonal_rank; the scan's counts pass through `nst`) -- and the labels of the ranks [r0, r0 + ZONAL_ZL)
+// get the zone slots of this round: the list in LDS, each cell's slot in 4 bits of a register pair.  A unit with more distinct labels
+// walks its instants again for the next ZONAL_ZL ranks (rare: a unit is 64 x 64 cells of one zone, or of a few).  A unit whose
+// selected cells all carry one label skips the ranking (a min / max over the workgroup says so).
+//
+// Per instant: a unit of one zone folds as k_bulk_space does -- the thread's cells, the wave's lanes by __shfl_xor, one LDS
+// update per wave; otherwise a thread adds every RUN of equal slots among its 16 cells to the LDS accumulators of (instant slot,
+// zone slot) with LDS atomics (k_bulk_hist's run trick).  Every ZONAL_B instants, or at the round's end, one barrier lets the
+// workgroup add the entries that hold anything to the global accumulators (zonal_add) and clear them.
+// (waves_per_eu: k_bulk_space's reason; no scratch.)
+struct ZonalLds {  // one LDS accumulator: a unit's share of one (instant, zone), in the leaf's own integers
+    unsigned long long sum;
+    uint32_t cnt;
+    int32_t lo, hi;
+    uint32_t _pad;
+};
+template <uint32_t LIVE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_bulk_zonal(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const ZonalUnit* __restrict__ units, uint32_t n_units,
+             const uint16_t* __restrict__ labels, uint32_t n_zones, uint64_t* acc) {
+    typedef int32_t V;
+    constexpr uint32_t L1 = LIVE | RA_COUNT, NE = ZONAL_B * ZONAL_ZL;
+    constexpr bool EXT = (LIVE & (RA_MIN | RA_MAX)) != 0, ADD = (LIVE & RA_SUM) != 0;
+    static_assert(2u * ZONAL_BM_WORDS <= BP_SIZE, "the bitmap and its prefix counts fit the pyramid's array");
+    static_assert(ZONAL_ZL == 16, "a cell's slot is 4 bits");
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    __shared__ ZonalLds za[NE];  // [instant slot][zone slot]
+    __shared__ uint32_t zlist[ZONAL_ZL];
+    __shared__ uint32_t w_lo[4], w_hi[4];
+    const uint32_t tid = threadIdx.x;
+    uint32_t* const bm = (uint32_t*)pyr;
+    uint32_t* const pre = bm + ZONAL_BM_WORDS;
+    for (uint32_t i = tid; i < NE; i += 256u) za[i] = ZonalLds{0, 0u, INT32_MAX, INT32_MIN, 0u};  // (every flush leaves them so)
+    // One loop over (unit, round): the unit is read again for every round, so nothing of its label addresses outlives the ranking.
+    for (uint32_t u = blockIdx.x, r0 = 0; u < n_units;) {
+        const ZonalUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int32_t enc = (int32_t)encs[U.chunk];
+        const int kind = leaf_kind(enc);
+        const int32_t sg = leaf_mirror(kind, C.fbits);
+        const gbytes gb = (gbytes)C.bytes;
+        uint32_t n_distinct = 1;
+        {
+            // ---- the round's zone slots: sel = the thread's cells that count now, zs = their slots, 4 bits each ----
+            uint32_t sel = 0;
+            uint64_t zs = 0;
+            uint32_t lmin = ZONAL_NONE, lmax = 0;
+            uint32_t lab[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the labels of the thread's cells, two to a register; dead after the ranking
+#define K2R_ZONAL_LAB(b) ((lab[(b) >> 1] >> (16u * ((b) & 1u))) & 0xffffu)
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; b++) {
+                const uint32_t l = zonal_label(U, labels, n_zones, tid, b);
+                lab[b >> 1] |= l << (16u * (b & 1u));
+                if (l != ZONAL_NONE) {
+                    lmin = min(lmin, l);
+                    lmax = max(lmax, l);
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                lmin = min(lmin, __shfl_xor(lmin, off));
+                lmax = max(lmax, __shfl_xor(lmax, off));
+            }
+            if ((tid & 63u) == 0) {
+                w_lo[tid >> 6] = lmin;
+                w_hi[tid >> 6] = lmax;
+            }
+            __syncthreads();  // (also: the previous round's and unit's readers of pyr and zlist are done)
+            lmin = min(min(w_lo[0], w_lo[1]), min(w_lo[2], w_lo[3]));
+            lmax = max(max(w_hi[0], w_hi[1]), max(w_hi[2], w_hi[3]));
+            const bool any = lmin != ZONAL_NONE;  // a cell of the unit is in a zone (uniform: every thread read the same words)
+            const bool one = lmin == lmax;
+            if (!any) {
+                n_distinct = 0;
+            } else if (one) {
+                if (tid == 0) zlist[0] = lmin;
+#pragma unroll
+                for (uint32_t b = 0; b < 16u; b++) sel |= K2R_ZONAL_LAB(b) == lmin ? 1u << b : 0u;
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 8u; j++) bm[8u * tid + j] = 0u;
+                __syncthreads();
+                uint32_t prev = ZONAL_NONE;
+#pragma unroll
+                for (uint32_t b = 0; b < 16u; b++) {
+                    const uint32_t l = K2R_ZONAL_LAB(b);
+                    if (l != ZONAL_NONE && l != prev) atomicOr(bm + (l >> 5), 1u << (l & 31u));
+                    prev = l;
+                }
+                __syncthreads();
+                // the exclusive scan of the threads' counts, through `nst` (dead like `pyr`): groups of 16, then the groups' totals
+                const uint32_t mine = zonal_count8(bm, tid);
+                nst[tid] = mine;
+                __syncthreads();
+                if (tid < 16u) {
+                    uint32_t run = 0;
+                    for (uint32_t j = 0; j < 16u; j++) {
+                        const uint32_t c = nst[16u * tid + j];
+                        nst[16u * tid + j] = run;
+                        run += c;
+                    }
+                    nst[256u + tid] = run;
+                }
+                __syncthreads();
+                uint32_t start = nst[tid], total = 0;
+                for (uint32_t g = 0; g < 16u; g++) {
+                    const uint32_t c = nst[256u + g];
+                    start += g < (tid >> 4) ? c : 0u;
+                    total += c;
+                }
+                n_distinct = total;
+                zonal_prefix8(bm, pre, tid, start);
+                __syncthreads();
+#pragma unroll
+                for (uint32_t b = 0; b < 16u; b++) {
+                    const uint32_t l = K2R_ZONAL_LAB(b);
+                    if (l == ZONAL_NONE) continue;
+                    const uint32_t s = zonal_rank(bm, pre, l) - r0;  // (wraps beyond ZONAL_ZL below r0)
+                    if (s < ZONAL_ZL) {
+                        sel |= 1u << b;
+                        zs |= (uint64_t)s << (4u * b);
+                        zlist[s] = l;  // (every writer of a slot writes its one label)
+                    }
+                }
+            }
+            // ---- the unit's instants ----
+            uint32_t cur_snap = 0xffffffffu, slot = 0;
+            for (uint32_t t = U.t0; any && t < U.t1; t++) {
+                const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+                const uint32_t row = slot * ZONAL_ZL;
+                int64_t s = 0;
+                uint32_t cnt = 0;
+                int32_t lo = INT32_MAX, hi = INT32_MIN;  // (beyond every stored value of a narrow32 chunk: "no value yet")
+#define K2R_ZONAL_PUT(at)                                                              \
+    {                                                                                  \
+        ZonalLds* const za_e = za + (at);                                              \
+        if constexpr (ADD) atomicAdd(&za_e->sum, (unsigned long long)s);               \
+        atomicAdd(&za_e->cnt, cnt);                                                    \
+        if constexpr (EXT) {                                                           \
+            atomicMin(&za_e->lo, lo);                                                  \
+            atomicMax(&za_e->hi, hi);                                                  \
+        }                                                                              \
+    }
+                if (one) {
+#pragma unroll
+                    for (uint32_t k = 0; k < 2u; k++) {
+                        const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                        const uint32_t sel8 = (sel >> (8u * k)) & 255u;
+                        if (sel8 == 0) continue;  // (none of the group's cells counts)
+                        V v[2][4];
+                        bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
+#pragma unroll
+                        for (uint32_t i = 0; i < 2u; i++)
+#pragma unroll
+                            for (uint32_t c = 0; c < 4u; c++) space_fold1<L1>(v[i][c], ((sel8 >> (4u * i + c)) & 1u) != 0, kind, s, cnt, lo, hi, sg);
+                    }
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        if constexpr (ADD) s += __shfl_xor((long long)s, off);
+                        cnt += __shfl_xor(cnt, off);
+                        if constexpr (EXT) {
+                            lo = min(lo, __shfl_xor(lo, off));
+                            hi = max(hi, __shfl_xor(hi, off));
+                        }
+                    }
+                    if ((tid & 63u) == 0 && cnt != 0) K2R_ZONAL_PUT(row)
+                } else {
+                    uint32_t run_slot = 0;  // the thread's current run of equal slots: cnt != 0 while it holds anything
+#pragma unroll
+                    for (uint32_t k = 0; k < 2u; k++) {
+                        const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                        const uint32_t sel8 = (sel >> (8u * k)) & 255u;
+                        if (sel8 == 0) continue;
+                        V v[2][4];
+                        bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
+#pragma unroll
+                        for (uint32_t j = 0; j < 8u; j++) {
+                            const int32_t n = v[j >> 2][j & 3u];
+                            const bool on = ((sel8 >> j) & 1u) != 0 && (kind == 0 || n != 0);
+                            const uint32_t zslot = (uint32_t)(zs >> (4u * (8u * k + j))) & 15u;
+                            if (on) {
+                                if (cnt != 0 && zslot != run_slot) {
+                                    K2R_ZONAL_PUT(row + run_slot)
+                                    s = 0;
+                                    cnt = 0;
+                                    lo = INT32_MAX;
+                                    hi = INT32_MIN;
+                                }
+                                run_slot = zslot;
+                                space_fold1<L1>(n, true, kind, s, cnt, lo, hi, sg);
+                            }
+                        }
+                    }
+                    if (cnt != 0) K2R_ZONAL_PUT(row + run_slot)  // the thread's last run
+                }
+                // ---- the slots' entries into the global accumulators ----
+                if (slot + 1u == ZONAL_B || t + 1u == U.t1) {  // the slots 0 .. slot hold the instants t - slot .. t
+                    __syncthreads();
+                    for (uint32_t i = tid; i < (slot + 1u) * ZONAL_ZL; i += 256u) {
+                        const uint32_t c = za[i].cnt;
+                        if (c == 0) continue;
+                        const int64_t ts = (int64_t)za[i].sum;
+                        const int32_t tl = za[i].lo, th = za[i].hi;
+                        za[i] = ZonalLds{0, 0u, INT32_MAX, INT32_MIN, 0u};
+                        const uint64_t at = U.acc + (uint64_t)zlist[i % ZONAL_ZL] * U.a_st + (t - slot + i / ZONAL_ZL - U.t0);
+                        zonal_add(acc, at, ts < 0 ? ~(uint64_t)0 : (uint64_t)0, (uint64_t)ts, space_scale(enc, C.fbits), c,
+                                  EXT ? leaf_extreme(tl, INT32_MAX, enc, C.fbits, sg) : 0.0, EXT ? leaf_extreme(th, INT32_MIN, enc, C.fbits, sg) : 0.0, EXT, ADD);
+                    }
+                    slot = 0;
+                } else {
+                    slot += 1u;
+                }
+            }
+        }
+        __syncthreads();
+        r0 += ZONAL_ZL;
+        if (r0 >= n_distinct) {  // the unit's last round
+            u += gridDim.x;
+            r0 = 0;
+        }
+    }
+}
+#undef K2R_ZONAL_PUT
+#undef K2R_ZONAL_LAB
+
+int launch_bulk_zonal(const ChunkRef* d_refs, const uint8_t* d_enc, const ZonalUnit* d_units, uint32_t n, const uint16_t* d_labels,
+                      uint32_t n_zones, uint64_t* d_acc, uint32_t live) {
+    if (n == 0) return DCDF_OK;
+    const dim3 grid = bulk_grid(n), block(256);
+    constexpr uint32_t EXT = RA_MIN | RA_MAX, ADD = RA_SUM | RA_COUNT;
+    const uint32_t l = ((live & EXT) ? EXT : 0u) | ((live & ADD) ? ADD : 0u);
+#define K2R_ZONAL_CASE(L) \
+    case L: hipLaunchKernelGGL((k_bulk_zonal<L>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_labels, n_zones, d_acc); break;
+    switch (l) {
+        K2R_ZONAL_CASE(EXT) K2R_ZONAL_CASE(ADD) K2R_ZONAL_CASE(EXT | ADD)
+        default: return DCDF_ERR_BAD_ARG;
+    }
+#undef K2R_ZONAL_CASE
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

@@ -1,4 +1,4 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells: k2r_raster_region.hip)
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells, zonal: k2r_raster_region.hip)
 // turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
 // A cube is cut into pieces, one per leaf it meets (raster_pieces).  A piece is of one of three kinds: on an elided leaf (one
@@ -17,6 +17,7 @@
 #include "k2r_reduce.h"
 #include "k2r_space.h"
 #include "k2r_spell.h"
+#include "k2r_zonal.h"
 
 // an elided piece of a decode: one value per instant over a rectangle of the window (k_raster_fill_const; outside the namespace,
 // where the kernels' mangled names have it)
@@ -402,6 +403,93 @@ inline int plan_reduce_space(const PlanRaster& g, const dcdf_cube* cubes, size_t
             }
             if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
                 P.jobs.size() > 0x7ffffff0ull)
+                return DCDF_ERR_CAPACITY;
+        }
+    }
+    flush_batch();
+    return DCDF_OK;
+}
+
+// ---- zonal statistics ---------------------------------------------------------------------------------------------------------
+// plan_reduce_space's pieces and units, without records and jobs: every piece adds to the accumulator entries of its cube's (zone,
+// instant)s with integer atomics (k2r_zonal.h).  The entries -- ZONAL_BYTES each, n_zones per instant -- live in a scratch of at
+// most acc_cap bytes: the cubes' instants are cut into spans, a batch takes spans while their entries fit (a single instant
+// beyond the cap is a batch of its own), and the batches run one after the other over the same scratch: zero, accumulate, finish.
+// base[q]: cube q's first matrix; moff[q]: its first label, in elements.
+struct ZonalBatch {
+    size_t unit0, unit1, const0, const1, slab0, slab1, span0, span1;
+    uint64_t entries;
+};
+struct ZonalPlan {
+    std::vector<ZonalUnit> units;
+    std::vector<ZonalFold> cfolds;
+    SlabCutter<ZonalFold> walk;
+    std::vector<ZonalSpan> spans;
+    std::vector<ZonalBatch> batches;
+    uint64_t entries_max = 0;  // entries of the largest batch
+    uint32_t span_nt = 1;      // the longest span
+    uint64_t stats[3] = {0, 0, 0};
+    explicit ZonalPlan(uint64_t slab_cap) : walk(slab_cap) {}
+};
+inline int plan_zonal(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, uint32_t n_zones,
+                      bool node_wise, uint64_t acc_cap, uint32_t wanted, ZonalPlan& P) {
+    const uint64_t room = std::max<uint64_t>(1, acc_cap / (ZONAL_BYTES * n_zones));  // instants of one batch
+    uint64_t used = 0;                                                                // instants of the current batch
+    ZonalBatch cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    P.units.reserve(plan_reserve(nq));
+    P.spans.reserve(plan_reserve(nq));
+    auto flush_batch = [&] {
+        P.walk.flush();
+        // each part of a split unit adds to its own instants' entries
+        plan_time_split(P.units, cur.unit0, wanted, [](ZonalUnit& v, uint32_t dt) { v.acc += dt; });
+        cur.unit1 = P.units.size();
+        cur.const1 = P.cfolds.size();
+        cur.slab1 = P.walk.slabs.size();
+        cur.span1 = P.spans.size();
+        cur.entries = used * n_zones;
+        if (cur.span1 > cur.span0) P.batches.push_back(cur);
+        P.entries_max = std::max(P.entries_max, cur.entries);
+        used = 0;
+        cur = ZonalBatch{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0, P.spans.size(), 0, 0};
+    };
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint32_t NT = c.end - c.start;
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        for (uint32_t a = 0; a < NT;) {
+            if (used == room) flush_batch();
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(NT - a, room - used);
+            const uint64_t acc = used * n_zones;  // the span's entries: [zone][nt]
+            P.spans.push_back(ZonalSpan{acc, nt, 0u, base[q] + a, (uint64_t)NT, (uint64_t)n_zones * NT});
+            P.span_nt = std::max(P.span_nt, nt);
+            if (wr * wc != 0)
+                plan_pieces(g, dcdf_cube{c.start + a, c.start + a + nt, c.top, c.bottom, c.left, c.right}, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+                    const ZonalFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, p.enc, p.fbits, p.kind == PIECE_CONST, nt,
+                                      (uint64_t)p.leaf * g.cs + p.l.start, acc + p.dt, moff[q] + p.in_win};
+                    if (p.kind == PIECE_CONST) {
+                        P.cfolds.push_back(f);
+                    } else if (p.kind == PIECE_WALK) {
+                        P.walk.add(f.nt, (uint64_t)f.rows * f.cols, [&](uint32_t x, uint32_t y, uint64_t src) {
+                            ZonalFold w = f;
+                            w.nt = y - x;
+                            w.src = src;
+                            w.acc = f.acc + x;
+                            window_items(p.leaf, cube_instants(p.k, x, y), src, P.walk.items, node_wise);
+                            P.walk.folds.push_back(w);
+                        });
+                    } else {
+                        plan_units(p, P.units, [&](ZonalUnit& u) {
+                            u.m_sr = (uint32_t)wc;
+                            u.a_st = nt;
+                            u.acc = f.acc;
+                            u.m_off = f.m_off + unit_in_piece(u, p, wc);
+                        });
+                    }
+                });
+            used += nt;
+            a += nt;
+            if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
+                P.spans.size() > 0x7ffffff0ull)
                 return DCDF_ERR_CAPACITY;
         }
     }

@@ -1,5 +1,5 @@
 // k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, spell
-// statistics, reduce over space, histogram -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// statistics, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,7 @@
 
 using namespace k2r;
 
-// ---- what the five calls share -----------------------------------------------------------------------------------------------
+// ---- what the six calls share -----------------------------------------------------------------------------------------------
 // Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
 // error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
 enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
@@ -681,5 +681,196 @@ extern "C" int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube
                                d_edges.as<double>(), n_bins, d_dst);
         });
     if (rc != DCDF_OK) return rc;
+    return batch_epilogue(W, ev, true, kernel_ms);
+}
+// ---- zonal statistics: per (zone, instant) of a cube, reduce_space's statistics over the cells that carry the zone's label ----
+// The plan is plan_zonal's (k2r_plan.h), the accumulators and their arithmetic k2r_zonal.h's.  A batch of the plan: its entries
+// zeroed, every piece's adds (elided pieces, the bulk kernel's units, the window walk's slabs), then k_zonal_finish.
+//
+// The labels: cube q's elements start at p[moff[q]] -- in the caller's device array, or in a pooled copy of the host arrays of the
+// cubes that have instants, one after the other (CubeMasks with 2-byte elements).
+struct CubeLabels {
+    std::vector<uint64_t> moff;
+    uint64_t total = 0;
+    const uint16_t* p;
+    bool host;
+    DevBuf d_labels;
+    CubeLabels(const dcdf_cube* cubes, size_t nq, const uint16_t* labels, const uint64_t* label_offset, int label_mem)
+        : moff(nq, 0), p(labels), host(label_mem == DCDF_MEM_HOST) {
+        for (size_t q = 0; q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            if (c.end == c.start) continue;
+            moff[q] = host ? total : label_offset[q];
+            total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+        }
+    }
+    int stage(const dcdf_cube* cubes, size_t nq, const uint64_t* label_offset) {
+        if (!host) return DCDF_OK;
+        K2R_HIP(d_labels.alloc_pooled(std::max<uint64_t>(total, 1) * sizeof(uint16_t)));
+        for (size_t q = 0; q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            const uint64_t n = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+            if (c.end == c.start || n == 0) continue;
+            K2R_HIP(hipMemcpy((uint16_t*)d_labels.p + moff[q], p + label_offset[q], n * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
+        p = (const uint16_t*)d_labels.p;
+        return DCDF_OK;
+    }
+};
+// A thread takes a run of consecutive cells of the piece (row-major) and folds every run of equal labels among them into one
+// add per (zone, instant): neighbours mostly share a zone.  A piece of the window walk's slab: a workgroup per (piece, instant),
+// the cells' stored integers widened by the leaf's own encoding, two-limb sums since |m| <= 2^63.  An elided piece (blockIdx.y == 0
+// alone): per run of n cells of one zone and per instant, value x n (space_mul_m).
+__global__ void __launch_bounds__(256)
+k_zonal_fold(const ZonalFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+             const uint16_t* __restrict__ labels, uint32_t n_zones, uint64_t* acc, uint32_t live) {
+    const bool ext = (live & (RA_MIN | RA_MAX)) != 0, add = (live & RA_SUM) != 0;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const ZonalFold P = ps[p];
+        const uint64_t cells = (uint64_t)P.rows * P.cols, per = (cells + blockDim.x - 1) / blockDim.x;
+        const uint64_t e0 = std::min<uint64_t>(cells, threadIdx.x * per), e1 = std::min<uint64_t>(cells, e0 + per);
+        const uint32_t scale = space_scale(P.enc, P.fbits);
+        if (P.elided && blockIdx.y != 0) continue;
+        for (uint32_t t = P.elided ? 0u : blockIdx.y; t < (P.elided ? 1u : P.nt); t += gridDim.y) {
+            SpaceAcc a{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+            uint32_t run = ZONAL_NONE;  // the label of the current run; a.cnt: its cells (elided) or its non-NaN values
+            for (uint64_t e = e0; e <= e1; e++) {
+                uint32_t l = ZONAL_NONE;
+                if (e < e1) {
+                    l = labels[P.m_off + e / P.cols * P.m_sr + e % P.cols];
+                    if (l >= n_zones) l = ZONAL_NONE;
+                }
+                if (l != run) {  // (e == e1 closes the last run)
+                    if (run != ZONAL_NONE && a.cnt != 0) {
+                        if (!P.elided) {
+                            zonal_add(acc, P.acc + (uint64_t)run * P.a_st + t, a.hi, a.lo, scale, a.cnt, a.mn, a.mx, ext, add);
+                        } else {
+                            for (uint32_t i = 0; i < P.nt; i++) {
+                                const int64_t v = vals[P.src + i];
+                                const double x = reduce_widen(P.enc, P.fbits, v);
+                                if (x != x) continue;
+                                uint64_t hi, lo;
+                                space_mul_m(hi, lo, space_m(P.enc, v), a.cnt);
+                                zonal_add(acc, P.acc + (uint64_t)run * P.a_st + i, hi, lo, scale, a.cnt, x, x, ext, add);
+                            }
+                        }
+                    }
+                    a = SpaceAcc{0, 0, __builtin_nan(""), __builtin_nan(""), 0};
+                    run = l;
+                }
+                if (l == ZONAL_NONE) continue;
+                if (P.elided) {
+                    a.cnt += 1u;
+                    continue;
+                }
+                const int64_t v = slab[P.src + (uint64_t)t * cells + e];
+                const double x = reduce_widen(P.enc, P.fbits, v);
+                if (x == x) {
+                    space_add_m(a.hi, a.lo, space_m(P.enc, v));
+                    a.cnt += 1u;
+                    a.mn = fmin(a.mn, x);
+                    a.mx = fmax(a.mx, x);
+                }
+            }
+        }
+    }
+}
+// A thread per (zone, instant) of a span: the limbs into one 192-bit integer and one rounding, the keys back into doubles, one
+// division for the mean; the span's part of the cube's matrices by plain stores.
+__global__ void __launch_bounds__(256)
+k_zonal_finish(const ZonalSpan* __restrict__ spans, uint32_t n, uint32_t n_zones, const uint64_t* __restrict__ acc, double* dst, uint32_t ops) {
+    for (uint32_t s = blockIdx.x; s < n; s += gridDim.x) {
+        const ZonalSpan S = spans[s];
+        const uint64_t entries = (uint64_t)n_zones * S.nt;
+        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < entries; e += (uint64_t)gridDim.y * blockDim.x) {
+            const __attribute__((address_space(1))) uint64_t* const A = (const __attribute__((address_space(1))) uint64_t*)acc + (S.acc + e) * ZONAL_WORDS;
+            const uint64_t cnt = A[ZA_CNT], kmin = A[ZA_MIN], kmax = A[ZA_MAX];
+            int64_t limbs[6];
+#pragma unroll
+            for (uint32_t i = 0; i < 6u; i++) limbs[i] = (int64_t)A[ZA_LIMB + i];
+            U192 v;
+            zonal_fold(limbs, v);
+            const double sum = space_round(v);
+            __attribute__((address_space(1))) double* o = (__attribute__((address_space(1))) double*)dst + (S.o_off + e / S.nt * S.o_zone + e % S.nt);
+            if (ops & RA_MIN) { *o = kmin ? zonal_unkey(~kmin) : __builtin_nan(""); o += S.o_stat; }
+            if (ops & RA_MAX) { *o = kmax ? zonal_unkey(kmax) : __builtin_nan(""); o += S.o_stat; }
+            if (ops & RA_SUM) { *o = sum; o += S.o_stat; }
+            if (ops & RA_COUNT) { *o = (double)cnt; o += S.o_stat; }
+            if (ops & ROP_MEAN) *o = cnt == 0 ? __builtin_nan("") : sum / (double)cnt;
+        }
+    }
+}
+// bytes of one batch's accumulators (K2R_ZONAL_ACC_BYTES overrides: tests of the batch cut); 72 per (zone, instant)
+static uint64_t zonal_acc_cap() {
+    const char* e = std::getenv("K2R_ZONAL_ACC_BYTES");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : (uint64_t)128 << 20;
+}
+extern "C" int dcdf_zonal_fold_limbs(const int64_t limbs[6], double* sum) {
+    if (!limbs || !sum) return DCDF_ERR_BAD_ARG;
+    const int64_t l[6] = {limbs[0], limbs[1], limbs[2], limbs[3], limbs[4], limbs[5]};
+    U192 v;
+    if (!zonal_fold(l, v)) return DCDF_ERR_BAD_ARG;
+    *sum = space_round(v);
+    return DCDF_OK;
+}
+extern "C" int dcdf_raster_zonal_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
+                                       const uint64_t* label_offset, int label_mem, uint32_t n_zones, double* out, int out_mem,
+                                       const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const bool own = ops != 0 && ops <= (RA_ALL | ROP_MEAN) && n_zones >= 1 && n_zones <= 65535u && (nq == 0 || (labels && label_offset)) &&
+                     (label_mem == DCDF_MEM_HOST || label_mem == DCDF_MEM_DEVICE);
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    const uint32_t live = reduce_live(ops), n_out = popc32(ops);
+    // where the matrices go: cube q's are n_out "instants" of [zones][instants] to WindowOut
+    std::vector<dcdf_cube> mats(nq, dcdf_cube{});
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (c.end != c.start) mats[q] = dcdf_cube{0, n_out, 0, n_zones, 0, c.end - c.start};
+    }
+    WindowOut W(mats.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    CubeLabels M(cubes, nq, labels, label_offset, label_mem);
+    ZonalPlan P(reduce_slab_cells());
+    rc = plan_zonal(r->plan(), cubes, nq, W.base.data(), M.moff.data(), n_zones, r->all_node, zonal_acc_cap(), bulk_wanted_units(), P);
+    if (rc != DCDF_OK) return rc;
+    put_stats(stats, P.stats);
+    if (W.total == 0) return DCDF_OK;
+    DevBuf d_units, d_cfolds, d_spans, d_acc;
+    WalkDev D;
+    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    double* const d_dst = (double*)W.dst();
+    rc = M.stage(cubes, nq, label_offset);
+    if (rc != DCDF_OK) return rc;
+    K2R_HIP(d_acc.alloc_pooled(P.entries_max * ZONAL_BYTES));
+    rc = upload_some(d_units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
+    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (rc != DCDF_OK) return rc;
+    K2R_HIP(upload(d_spans, P.spans));
+    EventPair ev;
+    K2R_HIP(ev.create());
+    K2R_HIP(hipEventRecord(ev.e0, 0));
+    uint64_t* const acc = d_acc.as<uint64_t>();
+    for (const ZonalBatch& b : P.batches) {
+        K2R_HIP(hipMemsetAsync(acc, 0, b.entries * ZONAL_BYTES, 0));
+        if (b.const1 > b.const0) {
+            hipLaunchKernelGGL(k_zonal_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
+                               d_cfolds.as<ZonalFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), M.p, n_zones, acc, live);
+            K2R_HIP(hipGetLastError());
+        }
+        rc = launch_bulk_zonal(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ZonalUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
+                               n_zones, acc, live);
+        if (rc == DCDF_OK)
+            rc = D.run(r, P.walk.slabs, b.slab0, b.slab1, [&](const Slab& sl) {
+                hipLaunchKernelGGL(k_zonal_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
+                                   dim3(256), 0, 0, D.folds.as<ZonalFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr,
+                                   M.p, n_zones, acc, live);
+            });
+        if (rc != DCDF_OK) return rc;
+        const uint64_t big = (uint64_t)n_zones * P.span_nt;
+        hipLaunchKernelGGL(k_zonal_finish, dim3((uint32_t)std::min<size_t>(b.span1 - b.span0, 1u << 16), (uint32_t)std::min<uint64_t>((big + 255) / 256, 4096)),
+                           dim3(256), 0, 0, d_spans.as<ZonalSpan>() + b.span0, (uint32_t)(b.span1 - b.span0), n_zones, acc, d_dst, ops);
+        K2R_HIP(hipGetLastError());
+    }
     return batch_epilogue(W, ev, true, kernel_ms);
 }

@@ -429,6 +429,37 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return {n: np.empty(0, dtype=np.float64) for n in EncodedRaster.reduce_ops(ops)[1]}
         return self.raster().reduce_space(ops, start, stop, window=(top, bottom, left, right), mask=mask)
 
+    def zonal(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """Per-zone, per-instant statistics over the window [top, bottom) x [left, right): `labels` is any integer array [rows,
+        cols] of the window of zone ids, negative = no zone.  Returns (ids, {name: ndarray [len(ids), stop - start] float64}): ids
+        are the distinct non-negative ids ascending (np.unique), row i of every matrix is zone ids[i]; the statistics are
+        reduce_space's for the zone's cells (the sum exact, rounded once; a zone whose cells are all NaN gets NaN, NaN, +0.0, 0,
+        NaN).  More than 65535 distinct ids: ValueError.  Through raster().zonal: the encoded bytes are read once on the GPU
+        whatever the number of zones (dcdf_raster_zonal_batch)."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else stop
+        bottom = R if bottom is None else bottom
+        right = Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        from . import _lib
+        from .raster import EncodedRaster
+        names = EncodedRaster.reduce_ops(ops)[1]
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.shape != (bottom - top, right - left):
+            raise ValueError("zonal: the labels are %s %r, the window integers %r" % (lab.dtype, lab.shape, (bottom - top, right - left)))
+        inside = lab >= 0
+        ids, inv = np.unique(lab[inside], return_inverse=True)
+        if ids.size > 65535:
+            raise ValueError("zonal: %d distinct zone ids, at most 65535" % ids.size)
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            return ids, {n: np.empty((ids.size, 0), dtype=np.float64) for n in names}
+        if ids.size == 0:
+            nan = {"sum": 0.0, "count": 0.0}
+            return ids, {n: np.full((0, stop - start), nan.get(n, np.nan)) for n in names}
+        dense = np.full(lab.shape, _lib.ZONE_NONE, dtype=np.uint16)
+        dense[inside] = inv.astype(np.uint16)
+        return ids, self.raster().zonal(ops, dense, start, stop, window=(top, bottom, left, right), n_zones=ids.size)
+
     def histogram(self, edges, start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
         """Per-instant value histogram over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
         ([rows, cols] of the window, boolean or uint8) is non-zero when a mask is given: ndarray [stop - start, bins] uint64, the

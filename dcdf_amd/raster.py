@@ -380,6 +380,98 @@ class EncodedRaster:
         return {n: out[i * nt:(i + 1) * nt] for i, n in enumerate(names)}
 
     @staticmethod
+    def _label_args(q, labels, what):
+        """The label arguments of dcdf_raster_zonal_batch for the cubes q: (pointer, offsets, memory kind, what must stay alive over
+        the call, the largest label below ZONE_NONE or -1 when unknown).  labels as zonal_flat documents them."""
+        if isinstance(labels, tuple) and len(labels) == 2 and isinstance(labels[0], (int, np.integer)):
+            keep = np.ascontiguousarray(np.asarray(labels[1], dtype=np.uint64))
+            if keep.shape != (len(q),):
+                raise ValueError("%s: %d label offsets for %d cubes" % (what, keep.size, len(q)))
+            return C.c_void_p(int(labels[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE, keep, -1
+        labels = list(labels)
+        if len(labels) != len(q):
+            raise ValueError("%s: %d label arrays for %d cubes" % (what, len(labels), len(q)))
+        rows = np.abs(q[:, 3].astype(np.int64) - q[:, 2])
+        cols = np.abs(q[:, 5].astype(np.int64) - q[:, 4])
+        parts = []
+        for i, m in enumerate(labels):
+            m = np.asarray(m)
+            if m.dtype != np.uint16:
+                raise ValueError("%s: labels %d are %s, not uint16" % (what, i, m.dtype))
+            if m.shape != (int(rows[i]), int(cols[i])):
+                raise ValueError("%s: labels %d have shape %r, their cube %r" % (what, i, m.shape, (int(rows[i]), int(cols[i]))))
+            parts.append(m.ravel())
+        loff = np.zeros(len(q), dtype=np.uint64)
+        if len(q) > 1:
+            loff[1:] = np.cumsum([p.size for p in parts])[:-1]
+        flat = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=np.uint16)]))
+        named = flat[:-1][flat[:-1] != L.ZONE_NONE]
+        return C.c_void_p(flat.ctypes.data), C.c_void_p(loff.ctypes.data), L.MEM_HOST, (flat, loff), int(named.max()) if named.size else -1
+
+    def zonal_flat(self, cubes, ops, labels, n_zones, out_device_ptr=None, out_offset=None):
+        """Zonal statistics of dataset-level cubes [n, 6] through dcdf_raster_zonal_batch: reduce_space_flat's statistics for every
+        zone of a label raster at once, from one walk of the encoded bytes.  labels: one uint16 array [rows, cols] per (normalised)
+        cube -- cell (r, c) belongs to zone labels[r, c] when that is < n_zones; ZONE_NONE (0xffff) and every other value >= n_zones
+        belong to no zone -- or (device pointer, offsets uint64[n] in elements) of label arrays already on the device.  Cube q
+        yields one [n_zones, instants] float64 matrix per statistic of `ops` (reduce_ops), in the order min, max, sum, count, mean;
+        a zone without a non-NaN cell gets NaN, NaN, +0.0, 0, NaN.  Host form: returns (flat float64 array, offsets uint64[n], kernel
+        ms, stats): cube q's part is flat[offsets[q]:] shaped (series, n_zones, instants).  Device form (out_device_ptr + out_offset
+        in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
+        leaves."""
+        mask, names = self.reduce_ops(ops)
+        n_zones = int(n_zones)
+        if not 1 <= n_zones <= 65535:
+            raise ValueError("zonal: n_zones %d outside 1 .. 65535" % n_zones)
+        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        ms = C.c_float()
+        stats = np.zeros(3, dtype=np.uint64)
+        l_ptr, l_off, l_mem, keep, _ = self._label_args(q, labels, "zonal")
+        if out_device_ptr is None:
+            vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(len(names) * n_zones)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = np.empty(max(1, int(vol.sum())), dtype=np.float64)
+            L.check(L.lib().dcdf_raster_zonal_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), l_ptr, l_off, l_mem,
+                                                    C.c_uint32(n_zones), C.c_void_p(out.ctypes.data), L.MEM_HOST, C.c_void_p(off.ctypes.data),
+                                                    C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_zonal_batch")
+            return out, off, ms.value, stats
+        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_zonal_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), l_ptr, l_off, l_mem,
+                                                C.c_uint32(n_zones), C.c_void_p(out_device_ptr), L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
+                                                C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_zonal_batch")
+        return ms.value, stats
+
+    def zonal(self, ops, labels, start=0, stop=None, window=None, n_zones=None):
+        """{statistic: ndarray [n_zones, stop - start] float64} per zone of `labels` -- uint16 [rows, cols] of the whole raster, or
+        of `window` = (top, bottom, left, right); ZONE_NONE and labels >= n_zones are in no zone -- at every instant of [start,
+        stop).  n_zones defaults to the largest label present, ZONE_NONE apart, plus 1 (at least 1).  Without instants: empty
+        matrices."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
+        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
+            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        bits, names = self.reduce_ops(ops)
+        lab = np.asarray(labels)
+        if lab.dtype != np.uint16 or lab.shape != (bottom - top, right - left):
+            raise ValueError("zonal: the labels are %s %r, the window uint16 %r" % (lab.dtype, lab.shape, (bottom - top, right - left)))
+        if n_zones is None:
+            named = lab[lab != L.ZONE_NONE]
+            n_zones = int(named.max()) + 1 if named.size else 1
+        n_zones = int(n_zones)
+        if not 1 <= n_zones <= 65535:
+            raise ValueError("zonal: n_zones %d outside 1 .. 65535" % n_zones)
+        nt = stop - start
+        if nt == 0:
+            return {n: np.empty((n_zones, 0), dtype=np.float64) for n in names}
+        out, _, _, _ = self.zonal_flat([[start, stop, top, bottom, left, right]], bits, [lab], n_zones)
+        return {n: out[i * n_zones * nt:(i + 1) * n_zones * nt].reshape(n_zones, nt) for i, n in enumerate(names)}
+
+    @staticmethod
     def _edges(edges):
         """Histogram edges as float64 [bins + 1]: 1 .. 256 bins, no NaN, strictly increasing (-inf first and +inf last are fine)."""
         e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))

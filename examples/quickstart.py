@@ -47,4 +47,8 @@ flat, offsets, _, stats = R.reduce_space_flat([(0, 32, 0, 256, 0, 256)], ("sum",
 assert all(flat[t] == math.fsum(a[t][disc].tolist()) and flat[32 + t] == flat[t] / disc.sum() for t in range(32))
 counts = R.histogram([0, 250, 500, 750, 1000], 8, 24, mask=disc)
 assert counts.shape == (16, 4) and all((counts[t] == np.histogram(a[8 + t][disc], [0, 250, 500, 750, 1000])[0]).all() for t in range(16))
+blocks = (np.arange(256)[:, None] // 64 * 4 + np.arange(256)[None, :] // 64).astype(np.uint16)
+zones = R.zonal(("mean", "count"), blocks, 8, 24)
+assert list(zones) == ["count", "mean"] and zones["mean"].shape == (16, 16) and (zones["count"] == 64 * 64).all()
+assert all(zones["mean"][z, t] == math.fsum(a[8 + t][blocks == z].tolist()) / 4096.0 for z in range(16) for t in range(16))
 print("readme example ok")

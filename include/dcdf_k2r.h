@@ -322,6 +322,35 @@ int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_cube* cubes,
  * bits; *sum = that integer / 2^63 as the nearest double, ties to even.  Pure host function; no GPU, no HIP call (so it is
  * testable on a CPU-only machine).  DCDF_ERR_BAD_ARG: a NULL pointer, a scale beyond those bits. */
 int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum);
+/* Zonal statistics: per instant of each cube, reduce_space's statistics for EVERY zone of a label raster at once -- one walk of
+ * the encoded bytes, a [zones][instants] matrix per statistic.  The call takes plain and tiled rasters (elided leaves included).
+ * Cubes, ops (DCDF_REDUCE_*), out_mem, stats and kernel_ms are exactly dcdf_raster_reduce_space_batch's: reversed bounds are
+ * swapped, stats are the numbers dcdf_raster_decode_batch reports for the same cubes, nq == 0 is fine.
+ *   labels   a dense row-major [rows][cols] array of uint16 per (normalised) cube; cube q's starts at element label_offset[q];
+ *            host or device memory (label_mem).  Cell (r, c) belongs to zone labels[label_offset[q] + (r - top) * cols + (c - left)]
+ *            when that value is < n_zones; DCDF_ZONE_NONE and every other value >= n_zones belong to no zone.  Nothing is
+ *            validated per cell.  1 <= n_zones <= 65535, shared by all cubes.
+ *   x        of a cell: reduce_space's x.  Per zone and instant, over the zone's cells:
+ *   DCDF_REDUCE_MIN / MAX   fmin / fmax over the non-NaN x; NaN when there is none.  When both -0.0 and +0.0 occur in one zone
+ *                           and instant, -0.0 is the minimum and +0.0 the maximum.
+ *   DCDF_REDUCE_COUNT       the number of non-NaN x; 0 when there is none
+ *   DCDF_REDUCE_SUM         the EXACT real sum of the non-NaN x, rounded once, ties to even (math.fsum); +0.0 when there is none
+ *   DCDF_REDUCE_MEAN        SUM / COUNT (one IEEE division); NaN when COUNT is 0
+ *            "None" covers a zone no cell carries, a zone whose cells are all NaN, and a cube without rows or columns.  Every
+ *            piece of the work adds to integer accumulators, so the result depends on no order and on no cut of the work.
+ * Cube q writes popcount(ops) matrices in ascending bit order, each dense [n_zones][instants] float64, from out + out_offset[q]
+ * (elements), host or device memory.  A cube without instants writes nothing; nothing outside a cube's matrices is written.
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 16; n_zones of 0 or above 65535; NULL labels, label_offset, cubes, out or out_offset
+ * with nq > 0; an unknown *_mem.  DCDF_ERR_BOUNDS: a cube outside the raster.  DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+#define DCDF_ZONE_NONE 0xffffu
+int dcdf_raster_zonal_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
+                            const uint64_t* label_offset, int label_mem, uint32_t n_zones, double* out, int out_mem,
+                            const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* The arithmetic DCDF_REDUCE_SUM of dcdf_raster_zonal_batch rests on, as the device runs it: a (zone, instant)'s sum at the 2^-63
+ * scale is kept in six int64 counters, limb i weighing 2^(32 i); *sum = (the sum of limbs[i] * 2^(32 i)) / 2^63 as the nearest
+ * double, ties to even, +0.0 for 0.  Pure host function; no GPU, no HIP call.  DCDF_ERR_BAD_ARG: a NULL pointer, a total that is
+ * no 192-bit two's complement integer. */
+int dcdf_zonal_fold_limbs(const int64_t limbs[6], double* sum);
 /* Value histograms: per instant of each cube, how many of its SELECTED cells fall into every bin of shared edges -- the
  * distribution of values over an area.  The call takes plain and tiled rasters (elided leaves included).  Cubes, the mask
  * (mask, mask_offset, mask_mem) and stats are exactly dcdf_raster_reduce_space_batch's: reversed bounds are swapped, a non-zero
