@@ -153,6 +153,12 @@ inline void plan_time_split(std::vector<U>& units, size_t from, uint32_t wanted,
 struct Slab {
     size_t item0, item1, fold0, fold1;
 };
+// the instants [a, b) of a walk piece's cube
+inline dcdf_cube cube_instants(dcdf_cube k, uint32_t a, uint32_t b) {
+    k.end = k.start + b;
+    k.start += a;
+    return k;
+}
 template <class Fold>
 struct SlabCutter {
     uint64_t cap, used = 0, slab_max = 0;  // cells: the bound, of the current slab, of the largest
@@ -184,6 +190,19 @@ struct SlabCutter {
             if (cut < nt) flush();
         }
     }
+    // The walk piece on leaf `chunk` over the chunk-level cube k, whose fold without the slab offset is f: every part gets f with
+    // its own nt and src, and own(fold, a) moves what else depends on the part's first instant a (counted from k's).
+    template <class F>
+    K2R_PLAN_INLINE void add_piece(uint32_t chunk, const dcdf_cube& k, const Fold& f, bool node_wise, F&& own) {
+        add(k.end - k.start, (uint64_t)f.rows * f.cols, [&](uint32_t a, uint32_t b, uint64_t src) {
+            Fold w = f;
+            w.nt = b - a;
+            w.src = src;
+            own(w, a);
+            window_items(chunk, cube_instants(k, a, b), src, items, node_wise);
+            folds.push_back(w);
+        });
+    }
 };
 // a walk piece kept until its slab is known: the leaf, the chunk-level cube, and its fold without the slab offset
 template <class Fold>
@@ -192,12 +211,87 @@ struct WalkPiece {
     dcdf_cube k;
     Fold f;
 };
-// the instants [a, b) of a walk piece's cube
-inline dcdf_cube cube_instants(dcdf_cube k, uint32_t a, uint32_t b) {
-    k.end = k.start + b;
-    k.start += a;
-    return k;
-}
+
+// ---- what every reduction plan carries ---------------------------------------------------------------------------------------
+// The three lists a launch reads -- bulk units, elided folds, the walk's slabs -- and the cells of each kind.  A PlanRange is a
+// stretch of all three that is launched together: mark() opens one at the lists' ends, close() ends it there.
+struct PlanRange {
+    size_t unit0, unit1, const0, const1, slab0, slab1;
+};
+template <class Unit, class Fold>
+struct ReducePlan {
+    std::vector<Unit> units;
+    std::vector<Fold> cfolds;
+    SlabCutter<Fold> walk;
+    uint64_t stats[3] = {0, 0, 0};
+    explicit ReducePlan(uint64_t slab_cap) : walk(slab_cap) {}
+    // what a launch's 32-bit counts cannot take
+    bool full() const { return units.size() > 0x3fffffffull || walk.items.size() > 0xfffffff0ull || cfolds.size() + walk.folds.size() > 0xfffffff0ull; }
+    PlanRange mark() const { return PlanRange{units.size(), 0, cfolds.size(), 0, walk.slabs.size(), 0}; }
+    void close(PlanRange& r) const {
+        r.unit1 = units.size();
+        r.const1 = cfolds.size();
+        r.slab1 = walk.slabs.size();
+    }
+    // The end of a batch whose work is independent in time (reduce_space, zonal, histogram): the last slab, the few-units split of
+    // the batch's own units (plan_time_split: advance), the range.
+    template <class F>
+    void close_batch(PlanRange& r, uint32_t wanted, F&& advance) {
+        walk.flush();
+        plan_time_split(units, r.unit0, wanted, advance);
+        close(r);
+    }
+};
+// reduce_time and spells: within a time segment every cell of a cube lies in exactly one piece, so the work of one segment never
+// shares a cell; the segments are launched one after the other in ascending order (ranges), and each piece continues the state its
+// cells' planes hold.  The pieces are gathered per segment (put) and appended segment by segment (assemble).
+using SegRange = PlanRange;
+template <class Unit, class Fold>
+struct SegmentPlan : ReducePlan<Unit, Fold> {
+    std::vector<SegRange> ranges;
+    using ReducePlan<Unit, Fold>::ReducePlan;
+};
+template <class Unit, class Fold>
+struct SegmentBuckets {
+    struct Segment {
+        std::vector<Unit> units;
+        std::vector<Fold> consts;
+        std::vector<WalkPiece<Fold>> walks;
+    };
+    const uint32_t cs;
+    std::vector<Segment> segs;
+    explicit SegmentBuckets(const PlanRaster& g) : cs(g.cs), segs((g.T + g.cs - 1) / g.cs) {}
+    // piece p with fold f into its segment; own(u) sets a bulk unit's own fields
+    template <class F>
+    K2R_PLAN_INLINE void put(const Piece& p, const Fold& f, F&& own) {
+        Segment& S = segs[p.t0 / cs];
+        if (p.kind == PIECE_CONST) S.consts.push_back(f);
+        else if (p.kind == PIECE_WALK) S.walks.push_back(WalkPiece<Fold>{p.leaf, p.k, f});
+        else plan_units(p, S.units, own);
+    }
+    // own(fold, a): SlabCutter::add_piece's, after init -- a part cut in time holds the cube's first instant only when it is the
+    // piece's first
+    template <class F>
+    int assemble(SegmentPlan<Unit, Fold>& P, bool node_wise, F&& own) {
+        for (Segment& S : segs) {
+            if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
+            SegRange r = P.mark();
+            P.units.insert(P.units.end(), S.units.begin(), S.units.end());
+            P.cfolds.insert(P.cfolds.end(), S.consts.begin(), S.consts.end());
+            for (const WalkPiece<Fold>& w : S.walks)
+                P.walk.add_piece(w.chunk, w.k, w.f, node_wise, [&](Fold& f, uint32_t a) {
+                    f.init = f.init && a == 0;
+                    own(f, a);
+                });
+            P.walk.flush();  // (a slab never spans two segments)
+            P.close(r);
+            P.ranges.push_back(r);
+            S = Segment{};
+            if (P.full()) return DCDF_ERR_CAPACITY;
+        }
+        return DCDF_OK;
+    }
+};
 
 // ---- decode ------------------------------------------------------------------------------------------------------------------
 // base[q]: element of cube q's first cell in the output; all three lists write that one array
@@ -232,75 +326,34 @@ inline int plan_decode(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, c
 }
 
 // ---- reduce over time --------------------------------------------------------------------------------------------------------
-// Within a time segment every cell of a cube lies in exactly one piece, so the work of one segment never shares a cell; the
-// segments are launched one after the other in ascending order (SegRange), and each piece continues the running sum of its cells'
-// state plane.  base[q] / sbase[q]: cube q's first output / scratch plane.
-struct SegRange {
-    size_t unit0, unit1, const0, const1, slab0, slab1;
-};
-struct TimePlan {
-    std::vector<ReduceUnit> units;
-    std::vector<FoldPiece> cfolds;
-    SlabCutter<FoldPiece> walk;
-    std::vector<SegRange> ranges;
+// A SegmentPlan: each piece continues the running sum of its cells' state plane.  base[q] / sbase[q]: cube q's first output /
+// scratch plane.
+struct TimePlan : SegmentPlan<ReduceUnit, FoldPiece> {
     std::vector<MeanPiece> means;
-    uint64_t stats[3] = {0, 0, 0};
-    explicit TimePlan(uint64_t slab_cap) : walk(slab_cap) {}
+    using SegmentPlan::SegmentPlan;
 };
 inline int plan_reduce_time(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* sbase, bool node_wise,
                             TimePlan& P) {
-    struct Segment {
-        std::vector<ReduceUnit> units;
-        std::vector<FoldPiece> consts;
-        std::vector<WalkPiece<FoldPiece>> walks;
-    };
-    std::vector<Segment> segs((g.T + g.cs - 1) / g.cs);
+    SegmentBuckets<ReduceUnit, FoldPiece> B(g);
     for (size_t q = 0; q < nq; q++) {
         const dcdf_cube c = norm_cube(cubes[q]);
         const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
         if (cube_cells(c) == 0) continue;
         P.means.push_back(MeanPiece{base[q], sbase[q], wr * wc});
         plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
-            Segment& S = segs[p.t0 / g.cs];
             const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
             const FoldPiece f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
                               (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc};
-            if (p.kind == PIECE_CONST) S.consts.push_back(f);
-            else if (p.kind == PIECE_WALK) S.walks.push_back(WalkPiece<FoldPiece>{p.leaf, p.k, f});
-            else
-                plan_units(p, S.units, [&](ReduceUnit& u) {
-                    u.sr = (uint32_t)wc;
-                    u.init = init;
-                    u.o_off = f.o_off + unit_in_piece(u, p, wc);
-                    u.s_off = f.s_off + unit_in_piece(u, p, wc);
-                    u.psz = wr * wc;
-                });
+            B.put(p, f, [&](ReduceUnit& u) {
+                u.sr = (uint32_t)wc;
+                u.init = init;
+                u.o_off = f.o_off + unit_in_piece(u, p, wc);
+                u.s_off = f.s_off + unit_in_piece(u, p, wc);
+                u.psz = wr * wc;
+            });
         });
     }
-    for (Segment& S : segs) {
-        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
-        SegRange r{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0};
-        P.units.insert(P.units.end(), S.units.begin(), S.units.end());
-        P.cfolds.insert(P.cfolds.end(), S.consts.begin(), S.consts.end());
-        for (const WalkPiece<FoldPiece>& w : S.walks)
-            P.walk.add(w.f.nt, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t a, uint32_t b, uint64_t src) {
-                FoldPiece f = w.f;
-                f.nt = b - a;
-                f.init = w.f.init && a == 0;
-                f.src = src;
-                window_items(w.chunk, cube_instants(w.k, a, b), src, P.walk.items, node_wise);
-                P.walk.folds.push_back(f);
-            });
-        P.walk.flush();  // (a slab never spans two segments)
-        r.unit1 = P.units.size();
-        r.const1 = P.cfolds.size();
-        r.slab1 = P.walk.slabs.size();
-        P.ranges.push_back(r);
-        S = Segment{};
-        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull)
-            return DCDF_ERR_CAPACITY;
-    }
-    return DCDF_OK;
+    return B.assemble(P, node_wise, [](FoldPiece&, uint32_t) {});
 }
 
 // ---- reduce over space -------------------------------------------------------------------------------------------------------
@@ -308,38 +361,30 @@ inline int plan_reduce_time(const PlanRaster& g, const dcdf_cube* cubes, size_t 
 // their records form one block [slot][instant] (a SpaceJob) that k_space_finish folds into the cube's series.  The jobs are
 // taken in batches whose records fit rec_cap (a job beyond it alone: a huge cube's segment is cut in time first); the batches
 // run one after the other over the same scratch.  base[q]: cube q's series; moff[q]: its mask's first byte.
-struct SpaceBatch {
-    size_t unit0, unit1, const0, const1, slab0, slab1, job0, job1;
+struct SpaceBatch : PlanRange {
+    size_t job0, job1;
     uint32_t job_nt;  // the longest job
 };
-struct SpacePlan {
-    std::vector<SpaceUnit> units;
-    std::vector<SpaceFold> cfolds;
-    SlabCutter<SpaceFold> walk;
+struct SpacePlan : ReducePlan<SpaceUnit, SpaceFold> {
     std::vector<SpaceJob> jobs;
     std::vector<SpaceBatch> batches;
     uint64_t rec_max = 0;  // records of the largest batch
-    uint64_t stats[3] = {0, 0, 0};
-    explicit SpacePlan(uint64_t slab_cap) : walk(slab_cap) {}
+    using ReducePlan::ReducePlan;
 };
 inline int plan_reduce_space(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, bool node_wise,
                              uint64_t rec_cap, uint32_t wanted, SpacePlan& P) {
     uint64_t rec_used = 0;
-    SpaceBatch cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    SpaceBatch cur{P.mark(), 0, 0, 0};
     P.units.reserve(plan_reserve(nq));
     P.jobs.reserve(plan_reserve(nq));
     auto flush_batch = [&] {
-        P.walk.flush();
         // each part of a split unit writes its own instants' records
-        plan_time_split(P.units, cur.unit0, wanted, [](SpaceUnit& v, uint32_t dt) { v.rec += dt; });
-        cur.unit1 = P.units.size();
-        cur.const1 = P.cfolds.size();
-        cur.slab1 = P.walk.slabs.size();
+        P.close_batch(cur, wanted, [](SpaceUnit& v, uint32_t dt) { v.rec += dt; });
         cur.job1 = P.jobs.size();
         if (cur.job1 > cur.job0) P.batches.push_back(cur);
         P.rec_max = std::max(P.rec_max, rec_used);
         rec_used = 0;
-        cur = SpaceBatch{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0, P.jobs.size(), 0, 0};
+        cur = SpaceBatch{P.mark(), P.jobs.size(), 0, 0};
     };
     std::vector<SpaceUnit> tu;  // the pieces of one (cube, segment), before they are cut into jobs
     std::vector<SpaceFold> tc;
@@ -388,22 +433,13 @@ inline int plan_reduce_space(const PlanRaster& g, const dcdf_cube* cubes, size_t
                     rec += jn;
                 }
                 for (const WalkPiece<SpaceFold>& w : tw) {
-                    P.walk.add(jn, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t x, uint32_t y, uint64_t src) {
-                        SpaceFold f = w.f;
-                        f.nt = y - x;
-                        f.src = src;
-                        f.rec = rec + x;
-                        window_items(w.chunk, cube_instants(w.k, a + x, a + y), src, P.walk.items, node_wise);
-                        P.walk.folds.push_back(f);
-                    });
+                    P.walk.add_piece(w.chunk, cube_instants(w.k, a, a + jn), w.f, node_wise, [&](SpaceFold& f, uint32_t x) { f.rec = rec + x; });
                     rec += jn;
                 }
                 rec_used = rec;
                 cur.job_nt = std::max(cur.job_nt, jn);
             }
-            if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
-                P.jobs.size() > 0x7ffffff0ull)
-                return DCDF_ERR_CAPACITY;
+            if (P.full() || P.jobs.size() > 0x7ffffff0ull) return DCDF_ERR_CAPACITY;
         }
     }
     flush_batch();
@@ -416,28 +452,25 @@ inline int plan_reduce_space(const PlanRaster& g, const dcdf_cube* cubes, size_t
 // most acc_cap bytes: the cubes' instants are cut into spans, a batch takes spans while their entries fit (a single instant
 // beyond the cap is a batch of its own), and the batches run one after the other over the same scratch: zero, accumulate, finish.
 // base[q]: cube q's first matrix; moff[q]: its first label, in elements.
-struct ZonalBatch {
-    size_t unit0, unit1, const0, const1, slab0, slab1, span0, span1;
+struct ZonalBatch : PlanRange {
+    size_t span0, span1;
     uint64_t entries;
 };
-struct ZonalPlan {
-    std::vector<ZonalUnit> units;
-    std::vector<ZonalFold> cfolds;
-    SlabCutter<ZonalFold> walk;
+struct ZonalPlan : ReducePlan<ZonalUnit, ZonalFold> {
     std::vector<ZonalSpan> spans;
     std::vector<ZonalBatch> batches;
     uint64_t entries_max = 0;  // entries of the largest batch
     uint32_t span_nt = 1;      // the longest span
-    uint64_t stats[3] = {0, 0, 0};
-    explicit ZonalPlan(uint64_t slab_cap) : walk(slab_cap) {}
+    using ReducePlan::ReducePlan;
 };
 inline int plan_zonal(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, uint32_t n_zones,
                       bool node_wise, uint64_t acc_cap, uint32_t wanted, ZonalPlan& P) {
     const uint64_t room = std::max<uint64_t>(1, acc_cap / (ZONAL_BYTES * n_zones));  // instants of one batch
     uint64_t used = 0;                                                                // instants of the current batch
-    ZonalBatch cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ZonalBatch cur{PlanRange{0, 0, 0, 0, 0, 0}, 0, 0, 0};
     P.units.reserve(plan_reserve(nq));
     P.spans.reserve(plan_reserve(nq));
+    // (the batch end and the walk part are written out, not close_batch / add_piece: with those this function alone was 8 % slower)
     auto flush_batch = [&] {
         P.walk.flush();
         // each part of a split unit adds to its own instants' entries
@@ -450,7 +483,7 @@ inline int plan_zonal(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, co
         if (cur.span1 > cur.span0) P.batches.push_back(cur);
         P.entries_max = std::max(P.entries_max, cur.entries);
         used = 0;
-        cur = ZonalBatch{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0, P.spans.size(), 0, 0};
+        cur = ZonalBatch{PlanRange{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0}, P.spans.size(), 0, 0};
     };
     for (size_t q = 0; q < nq; q++) {
         const dcdf_cube c = norm_cube(cubes[q]);
@@ -501,13 +534,9 @@ inline int plan_zonal(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, co
 // Every piece adds its counts to the cube's own [instants][bins] array (base[q]) with integer atomics, so the work of all
 // segments and cubes goes into one launch of each kind.  thr: the thresholds of every distinct (encoding, fractional bits) among
 // the bulk kernel's leaves (hist_thresholds32), 2^hist_steps(n_bins) entries each, translated once.
-struct HistPlan {
-    std::vector<HistUnit> units;
-    std::vector<HistFold> cfolds;
-    SlabCutter<HistFold> walk;
+struct HistPlan : ReducePlan<HistUnit, HistFold> {
     std::vector<int32_t> thr;
-    uint64_t stats[3] = {0, 0, 0};
-    explicit HistPlan(uint64_t slab_cap) : walk(slab_cap) {}
+    using ReducePlan::ReducePlan;
 };
 inline int plan_histogram(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, const uint64_t* moff, const double* edges,
                           uint32_t n_bins, bool node_wise, uint32_t wanted, HistPlan& P) {
@@ -524,14 +553,7 @@ inline int plan_histogram(const PlanRaster& g, const dcdf_cube* cubes, size_t nq
             if (p.kind == PIECE_CONST) {
                 P.cfolds.push_back(f);
             } else if (p.kind == PIECE_WALK) {
-                P.walk.add(f.nt, (uint64_t)f.rows * f.cols, [&](uint32_t x, uint32_t y, uint64_t src) {
-                    HistFold w = f;
-                    w.nt = y - x;
-                    w.src = src;
-                    w.o_off = f.o_off + (uint64_t)x * n_bins;
-                    window_items(p.leaf, cube_instants(p.k, x, y), src, P.walk.items, node_wise);
-                    P.walk.folds.push_back(w);
-                });
+                P.walk.add_piece(p.leaf, p.k, f, node_wise, [&](HistFold& w, uint32_t x) { w.o_off += (uint64_t)x * n_bins; });
             } else {
                 auto it = leaf_thr.find({p.enc, p.fbits});
                 if (it == leaf_thr.end()) {
@@ -548,43 +570,28 @@ inline int plan_histogram(const PlanRaster& g, const dcdf_cube* cubes, size_t nq
                 });
             }
         });
-        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull ||
-            P.thr.size() > 0x7fffffffull)
-            return DCDF_ERR_CAPACITY;
+        if (P.full() || P.thr.size() > 0x7fffffffull) return DCDF_ERR_CAPACITY;
     }
-    P.walk.flush();
-    // each part of a split unit adds to its own instants' rows
-    plan_time_split(P.units, 0, wanted, [n_bins](HistUnit& v, uint32_t dt) { v.o_off += (uint64_t)dt * n_bins; });
+    // one batch; each part of a split unit adds to its own instants' rows
+    PlanRange all{};
+    P.close_batch(all, wanted, [n_bins](HistUnit& v, uint32_t dt) { v.o_off += (uint64_t)dt * n_bins; });
     return DCDF_OK;
 }
 
 // ---- spell statistics --------------------------------------------------------------------------------------------------------
-// plan_reduce_time's shape: the segments one after the other in ascending order (SegRange), within a segment one piece per cell,
-// each piece continuing the run state its cells' planes hold.  A unit's instants are never split over workgroups (no
+// A SegmentPlan: each piece continues the run state its cells' planes hold.  A unit's instants are never split over workgroups (no
 // plan_time_split): two workgroups on the same cells would have to merge runs.  lower[q] / upper[q] are translated once per
 // (cube, encoding, fractional bits) into the leaf's stored integers (value_bounds).  base[q] / sbase[q]: cube q's first output /
 // scratch plane.
-struct SpellPlan {
-    std::vector<SpellUnit> units;
-    std::vector<SpellFold> cfolds;
-    SlabCutter<SpellFold> walk;
-    std::vector<SegRange> ranges;
-    uint64_t stats[3] = {0, 0, 0};
-    explicit SpellPlan(uint64_t slab_cap) : walk(slab_cap) {}
-};
+using SpellPlan = SegmentPlan<SpellUnit, SpellFold>;
 inline int plan_spells(const PlanRaster& g, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq, const uint64_t* base,
                        const uint64_t* sbase, bool node_wise, SpellPlan& P) {
-    struct Segment {
-        std::vector<SpellUnit> units;
-        std::vector<SpellFold> consts;
-        std::vector<WalkPiece<SpellFold>> walks;
-    };
     struct LeafRange {
         int32_t enc;
         uint32_t fbits;
         ValueRange vr;
     };
-    std::vector<Segment> segs((g.T + g.cs - 1) / g.cs);
+    SegmentBuckets<SpellUnit, SpellFold> B(g);
     std::vector<LeafRange> cache;  // of one cube: a raster has few distinct (encoding, fractional bits)
     for (size_t q = 0; q < nq; q++) {
         const dcdf_cube c = norm_cube(cubes[q]);
@@ -601,55 +608,26 @@ inline int plan_spells(const PlanRaster& g, const dcdf_cube* cubes, const double
                 if (!value_bounds(p.enc, p.fbits, lower[q], upper[q], &cache[at].vr)) bad = true;
             }
             const ValueRange& vr = cache[at].vr;
-            Segment& S = segs[p.t0 / g.cs];
             const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
             const SpellRange64 r64 = spell_range64(vr);
             const SpellFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
                               (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc, p.dt, r64.flags, r64.lo, r64.hi};
-            if (p.kind == PIECE_CONST) S.consts.push_back(f);
-            else if (p.kind == PIECE_WALK) S.walks.push_back(WalkPiece<SpellFold>{p.leaf, p.k, f});
-            else {
-                const SpellRange32 r32 = spell_range32(vr);
-                plan_units(p, S.units, [&](SpellUnit& u) {
-                    u.sr = (uint32_t)wc;
-                    u.init = init;
-                    u.dt = p.dt;
-                    u.lo = r32.lo;
-                    u.hi = r32.hi;
-                    u.flags = r32.flags;
-                    u.o_off = f.o_off + unit_in_piece(u, p, wc);
-                    u.s_off = f.s_off + unit_in_piece(u, p, wc);
-                    u.psz = wr * wc;
-                });
-            }
+            const SpellRange32 r32 = p.kind == PIECE_BULK ? spell_range32(vr) : SpellRange32{};  // the units' alone
+            B.put(p, f, [&](SpellUnit& u) {
+                u.sr = (uint32_t)wc;
+                u.init = init;
+                u.dt = p.dt;
+                u.lo = r32.lo;
+                u.hi = r32.hi;
+                u.flags = r32.flags;
+                u.o_off = f.o_off + unit_in_piece(u, p, wc);
+                u.s_off = f.s_off + unit_in_piece(u, p, wc);
+                u.psz = wr * wc;
+            });
         });
         if (bad) return DCDF_ERR_BAD_ARG;
     }
-    for (Segment& S : segs) {
-        if (S.units.empty() && S.consts.empty() && S.walks.empty()) continue;
-        SegRange r{P.units.size(), 0, P.cfolds.size(), 0, P.walk.slabs.size(), 0};
-        P.units.insert(P.units.end(), S.units.begin(), S.units.end());
-        P.cfolds.insert(P.cfolds.end(), S.consts.begin(), S.consts.end());
-        for (const WalkPiece<SpellFold>& w : S.walks)
-            P.walk.add(w.f.nt, (uint64_t)w.f.rows * w.f.cols, [&](uint32_t a, uint32_t b, uint64_t src) {
-                SpellFold f = w.f;  // a part cut in time: its own slab, its own first instant
-                f.nt = b - a;
-                f.init = w.f.init && a == 0;
-                f.dt = w.f.dt + a;
-                f.src = src;
-                window_items(w.chunk, cube_instants(w.k, a, b), src, P.walk.items, node_wise);
-                P.walk.folds.push_back(f);
-            });
-        P.walk.flush();  // (a slab never spans two segments)
-        r.unit1 = P.units.size();
-        r.const1 = P.cfolds.size();
-        r.slab1 = P.walk.slabs.size();
-        P.ranges.push_back(r);
-        S = Segment{};
-        if (P.units.size() > 0x3fffffffull || P.walk.items.size() > 0xfffffff0ull || P.cfolds.size() + P.walk.folds.size() > 0xfffffff0ull)
-            return DCDF_ERR_CAPACITY;
-    }
-    return DCDF_OK;
+    return B.assemble(P, node_wise, [](SpellFold& f, uint32_t a) { f.dt += a; });  // a part cut in time: its own first instant
 }
 
 #undef K2R_PLAN_INLINE

@@ -31,11 +31,22 @@ static int upload_some(DevBuf& d, const std::vector<T>& v) {
     if (!v.empty()) K2R_HIP(upload(d, v));
     return DCDF_OK;
 }
-// cells of one fallback slab (K2R_REDUCE_SLAB_CELLS overrides: tests of the slab cut)
-static uint64_t reduce_slab_cells() {
-    const char* e = std::getenv("K2R_REDUCE_SLAB_CELLS");
+// A cap a test may override through the environment (read on every call: the tests change it between calls of one process).
+static uint64_t env_cap(const char* name, uint64_t dflt) {
+    const char* e = std::getenv(name);
     const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (uint64_t)1 << 22;
+    return v > 0 ? (uint64_t)v : dflt;
+}
+static uint64_t reduce_slab_cells() { return env_cap("K2R_REDUCE_SLAB_CELLS", (uint64_t)1 << 22); }  // cells of one fallback slab
+static uint64_t space_record_cap() { return env_cap("K2R_SPACE_RECORDS", (uint64_t)6 << 20); }      // records of a batch, 40 bytes each
+static uint64_t zonal_acc_cap() { return env_cap("K2R_ZONAL_ACC_BYTES", (uint64_t)128 << 20); }     // 72 bytes per (zone, instant)
+// A fold kernel over n pieces on the null stream: a column of gy workgroups per piece.
+template <auto Kernel, class Fold, class... Args>
+static int launch_fold(uint32_t gy, const Fold* d_ps, size_t n, Args... args) {
+    if (n == 0) return DCDF_OK;
+    hipLaunchKernelGGL(Kernel, dim3((uint32_t)std::min<size_t>(n, 1u << 20), gy), dim3(256), 0, 0, d_ps, (uint32_t)n, args...);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
 }
 // the window walk's share of a plan on the device: its items, its folds, and the slab both kinds of launch meet in
 struct WalkDev {
@@ -48,52 +59,101 @@ struct WalkDev {
         return rc;
     }
     // the slabs [s0, s1) one after the other: the walk decodes a slab's items as stored integers (DCDF_I64: store_typed leaves n
-    // as it is) -- one launch whatever mix of encodings its chunks have --, then fold(slab) launches the call's fold kernel
-    template <class F>
-    int run(const dcdf_raster* r, const std::vector<Slab>& slabs, size_t s0, size_t s1, F&& fold) const {
-        for (size_t s = s0; s < s1; s++) {
-            const Slab& b = slabs[s];
-            const int rc = launch_window_items_dev(r->d_refs, items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), slab.p, DCDF_I64, nullptr,
-                                                   nullptr, r->all_node, r->all_narrow);
+    // as it is) -- one launch whatever mix of encodings its chunks have --, then the call's fold kernel reads the slab
+    template <auto Kernel, class Fold, class... Args>
+    int run(const dcdf_raster* r, const SlabCutter<Fold>& w, const PlanRange& g, uint32_t gy, Args... args) const {
+        for (size_t s = g.slab0; s < g.slab1; s++) {
+            const Slab& b = w.slabs[s];
+            int rc = launch_window_items_dev(r->d_refs, items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), slab.p, DCDF_I64, nullptr, nullptr,
+                                             r->all_node, r->all_narrow);
+            if (rc == DCDF_OK) rc = launch_fold<Kernel>(gy, folds.as<Fold>() + b.fold0, b.fold1 - b.fold0, slab.as<int64_t>(), nullptr, args...);
             if (rc != DCDF_OK) return rc;
-            fold(b);
-            K2R_HIP(hipGetLastError());
         }
         return DCDF_OK;
     }
 };
-// The masks of reduce_space and histogram: cube q's bytes start at p[moff[q]] -- in the caller's device array, or in a pooled copy
-// of the host masks of the cubes that have instants, one after the other (stage()).
-struct CubeMasks {
+// One array of T per cube -- the masks of reduce_space and histogram (optional: a null array stages nothing), the labels of zonal
+// (mandatory; their pooled copy holds at least one element: MIN).  Cube q's elements start at p[moff[q]] -- in the caller's device
+// array, or in a pooled copy of the host arrays of the cubes that have instants, one after the other (stage()).
+template <class T, uint64_t MIN>
+struct CubeArrays {
     std::vector<uint64_t> moff;
     uint64_t total = 0;
-    const uint8_t* p;
+    const T* p;
     bool host;
-    DevBuf d_mask;
-    static bool args_ok(const uint8_t* mask, const uint64_t* mask_offset, int mask_mem) {
-        return !mask || (mask_offset && (mask_mem == DCDF_MEM_HOST || mask_mem == DCDF_MEM_DEVICE));
-    }
-    CubeMasks(const dcdf_cube* cubes, size_t nq, const uint8_t* mask, const uint64_t* mask_offset, int mask_mem)
-        : moff(nq, 0), p(mask), host(mask && mask_mem == DCDF_MEM_HOST) {
-        for (size_t q = 0; mask && q < nq; q++) {
+    DevBuf d_copy;
+    static bool args_ok(const T* a, const uint64_t* offset, int mem) { return !a || (offset && (mem == DCDF_MEM_HOST || mem == DCDF_MEM_DEVICE)); }
+    CubeArrays(const dcdf_cube* cubes, size_t nq, const T* a, const uint64_t* offset, int mem) : moff(nq, 0), p(a), host(a && mem == DCDF_MEM_HOST) {
+        for (size_t q = 0; a && q < nq; q++) {
             const dcdf_cube c = norm_cube(cubes[q]);
             if (c.end == c.start) continue;
-            moff[q] = host ? total : mask_offset[q];
+            moff[q] = host ? total : offset[q];
             total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
         }
     }
-    int stage(const dcdf_cube* cubes, size_t nq, const uint64_t* mask_offset) {
+    int stage(const dcdf_cube* cubes, size_t nq, const uint64_t* offset) {
         if (!host) return DCDF_OK;
-        K2R_HIP(d_mask.alloc_pooled(total));
+        K2R_HIP(d_copy.alloc_pooled(std::max<uint64_t>(total, MIN) * sizeof(T)));
         for (size_t q = 0; q < nq; q++) {
             const dcdf_cube c = norm_cube(cubes[q]);
-            const uint64_t bytes = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-            if (c.end == c.start || bytes == 0) continue;
-            K2R_HIP(hipMemcpy((uint8_t*)d_mask.p + moff[q], p + mask_offset[q], bytes, hipMemcpyHostToDevice));
+            const uint64_t n = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
+            if (c.end == c.start || n == 0) continue;
+            K2R_HIP(hipMemcpy((T*)d_copy.p + moff[q], p + offset[q], n * sizeof(T), hipMemcpyHostToDevice));
         }
-        p = (const uint8_t*)d_mask.p;
+        p = (const T*)d_copy.p;
         return DCDF_OK;
     }
+};
+using CubeMasks = CubeArrays<uint8_t, 0>;
+using CubeLabels = CubeArrays<uint16_t, 1>;
+// Where the planes of reduce_time and spells go: cube q's output is n_out "instants" of [rows][cols] to WindowOut, its n_scr
+// scratch planes start at element sbase[q] of a pooled array of scr_total elements.
+struct PlaneLayout {
+    std::vector<dcdf_cube> planes;
+    std::vector<uint64_t> sbase;
+    uint64_t scr_total = 0;
+    PlaneLayout(const dcdf_cube* cubes, size_t nq, uint32_t n_out, uint32_t n_scr) : planes(nq, dcdf_cube{}), sbase(nq, 0) {
+        for (size_t q = 0; q < nq; q++) {
+            const dcdf_cube c = norm_cube(cubes[q]);
+            if (cube_cells(c) == 0) continue;
+            planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
+            sbase[q] = scr_total;
+            scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
+        }
+    }
+};
+// What follows a successful plan in reduce_time, spells, reduce_space and zonal (decode and histogram keep their own lines, see
+// DESIGN.md "Speed"), in this order (a call's own allocations and uploads go between the steps):
+// begin -- the stats out; `nothing` when no cell is written, else the host form's stage --, upload, start -- the events, e0
+// recorded --, the launches, end (batch_epilogue).
+struct RegionRun {
+    DevBuf units, cfolds;
+    WalkDev walk;
+    EventPair ev;
+    bool nothing = false;
+    int begin(WindowOut& W, uint64_t stats[3], const uint64_t cells[3]) {
+        put_stats(stats, cells);
+        nothing = W.total == 0;
+        if (!nothing && !W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+        return DCDF_OK;
+    }
+    template <class Plan>
+    int upload(const Plan& P) {
+        int rc = upload_some(units, P.units);
+        if (rc == DCDF_OK) rc = upload_some(cfolds, P.cfolds);
+        return rc == DCDF_OK ? walk.upload(P.walk) : rc;
+    }
+    int start() {
+        K2R_HIP(ev.create());
+        K2R_HIP(hipEventRecord(ev.e0, 0));
+        return DCDF_OK;
+    }
+    // the elided pieces of range g, one value per instant from dcdf_raster::d_vals (the range's slabs: walk.run)
+    template <auto Kernel, class Fold, class... Args>
+    int fold_consts(const dcdf_raster* r, const PlanRange& g, uint32_t gy, Args... args) const {
+        return launch_fold<Kernel>(gy, cfolds.as<Fold>() + g.const0, g.const1 - g.const0, nullptr, r->d_vals.as<int64_t>(), args...);
+    }
+    int end(const WindowOut& W, bool record, float* kernel_ms) const { return batch_epilogue(W, ev, record, kernel_ms); }
 };
 
 // ---- decompress: whole regions, block by block (k2r_bulk.hip) ---------------------------------------------------------------
@@ -185,54 +245,33 @@ __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict
         }
     }
 }
-static void launch_reduce_fold(const FoldPiece* d_ps, size_t n, const int64_t* d_slab, const int64_t* d_vals, double* d_dst, double* d_scr,
-                               uint32_t ops) {
-    if (n) hipLaunchKernelGGL(k_reduce_fold, dim3((uint32_t)std::min<size_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, (uint32_t)n, d_slab, d_vals, d_dst, d_scr, ops);
-}
 extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
                                              const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
     int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
     if (rc != DCDF_OK || nq == 0) return rc;
     const uint32_t live = reduce_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
-    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
-    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
-    std::vector<uint64_t> sbase(nq, 0);
-    uint64_t scr_total = 0;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (cube_cells(c) == 0) continue;
-        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
-        sbase[q] = scr_total;
-        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
-    }
-    WindowOut W(planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    const PlaneLayout L(cubes, nq, n_out, n_scr);
+    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
     TimePlan P(reduce_slab_cells());
-    rc = plan_reduce_time(r->plan(), cubes, nq, W.base.data(), sbase.data(), r->all_node, P);
+    rc = plan_reduce_time(r->plan(), cubes, nq, W.base.data(), L.sbase.data(), r->all_node, P);
     if (rc != DCDF_OK) return rc;
-    put_stats(stats, P.stats);
-    if (W.total == 0) return DCDF_OK;
-    DevBuf d_units, d_cfolds, d_means, d_scr;
-    WalkDev D;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    DevBuf d_means, d_scr;
+    RegionRun R;
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
     double* const d_dst = (double*)W.dst();
-    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(double)));
-    rc = upload_some(d_units, P.units);
-    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
-    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(double)));
+    rc = R.upload(P);
     if (rc != DCDF_OK) return rc;
     if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
+    rc = R.start();
+    if (rc != DCDF_OK) return rc;
     for (const SegRange& g : P.ranges) {
-        launch_reduce_fold(d_cfolds.as<FoldPiece>() + g.const0, g.const1 - g.const0, nullptr, r->d_vals.as<int64_t>(), d_dst, d_scr.as<double>(), ops);
-        K2R_HIP(hipGetLastError());
-        rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                d_dst, d_scr.as<double>(), ops);
+        rc = R.fold_consts<k_reduce_fold, FoldPiece>(r, g, 16, d_dst, d_scr.as<double>(), ops);
         if (rc == DCDF_OK)
-            rc = D.run(r, P.walk.slabs, g.slab0, g.slab1, [&](const Slab& b) {
-                launch_reduce_fold(D.folds.as<FoldPiece>() + b.fold0, b.fold1 - b.fold0, D.slab.as<int64_t>(), nullptr, d_dst, d_scr.as<double>(), ops);
-            });
+            rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), R.units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                    d_dst, d_scr.as<double>(), ops);
+        if (rc == DCDF_OK) rc = R.walk.run<k_reduce_fold>(r, P.walk, g, 16, d_dst, d_scr.as<double>(), ops);
         if (rc != DCDF_OK) return rc;
     }
     if (ops & ROP_MEAN) {
@@ -242,7 +281,7 @@ extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cu
                            dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr.as<double>(), ops);
         K2R_HIP(hipGetLastError());
     }
-    return batch_epilogue(W, ev, true, kernel_ms);
+    return R.end(W, true, kernel_ms);
 }
 // ---- spell statistics: per cell, the hits of a value range over time and their runs (k2r_spell.h) -----------------------------
 // reduce_time's shape: plan_spells (k2r_plan.h) gives the segments in ascending order, launched one after the other on the null
@@ -289,10 +328,6 @@ k_spell_fold(const SpellFold* __restrict__ ps, uint32_t n, const int64_t* __rest
         }
     }
 }
-static void launch_spell_fold(const SpellFold* d_ps, size_t n, const int64_t* d_slab, const int64_t* d_vals, uint32_t* d_dst, uint32_t* d_scr,
-                              uint32_t ops) {
-    if (n) hipLaunchKernelGGL(k_spell_fold, dim3((uint32_t)std::min<size_t>(n, 1u << 20), 16), dim3(256), 0, 0, d_ps, (uint32_t)n, d_slab, d_vals, d_dst, d_scr, ops);
-}
 extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
                                         uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
     bool own = ops != 0 && ops <= SP_ALL && (nq == 0 || (lower && upper));
@@ -300,46 +335,28 @@ extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* c
     int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
     if (rc != DCDF_OK || nq == 0) return rc;
     const uint32_t live = spell_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
-    // where the planes go: cube q's are n_out "instants" of [rows][cols] to WindowOut
-    std::vector<dcdf_cube> planes(nq, dcdf_cube{});
-    std::vector<uint64_t> sbase(nq, 0);
-    uint64_t scr_total = 0;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (cube_cells(c) == 0) continue;
-        planes[q] = dcdf_cube{0, n_out, c.top, c.bottom, c.left, c.right};
-        sbase[q] = scr_total;
-        scr_total += (uint64_t)n_scr * (c.bottom - c.top) * (c.right - c.left);
-    }
-    WindowOut W(planes.data(), nq, out, out_offset, sizeof(uint32_t), out_mem == DCDF_MEM_DEVICE);
+    const PlaneLayout L(cubes, nq, n_out, n_scr);
+    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(uint32_t), out_mem == DCDF_MEM_DEVICE);
     SpellPlan P(reduce_slab_cells());
-    rc = plan_spells(r->plan(), cubes, lower, upper, nq, W.base.data(), sbase.data(), r->all_node, P);
+    rc = plan_spells(r->plan(), cubes, lower, upper, nq, W.base.data(), L.sbase.data(), r->all_node, P);
     if (rc != DCDF_OK) return rc;
-    put_stats(stats, P.stats);
-    if (W.total == 0) return DCDF_OK;
-    DevBuf d_units, d_cfolds, d_scr;
-    WalkDev D;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    DevBuf d_scr;
+    RegionRun R;
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
     uint32_t* const d_dst = (uint32_t*)W.dst();
-    if (scr_total) K2R_HIP(d_scr.alloc_pooled(scr_total * sizeof(uint32_t)));
-    rc = upload_some(d_units, P.units);
-    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
-    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(uint32_t)));
+    rc = R.upload(P);
+    if (rc == DCDF_OK) rc = R.start();
     if (rc != DCDF_OK) return rc;
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
     for (const SegRange& g : P.ranges) {
-        launch_spell_fold(d_cfolds.as<SpellFold>() + g.const0, g.const1 - g.const0, nullptr, r->d_vals.as<int64_t>(), d_dst, d_scr.as<uint32_t>(), ops);
-        K2R_HIP(hipGetLastError());
-        rc = launch_bulk_spell(r->d_refs.as<ChunkRef>(), d_units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr.as<uint32_t>(), ops);
+        rc = R.fold_consts<k_spell_fold, SpellFold>(r, g, 16, d_dst, d_scr.as<uint32_t>(), ops);
         if (rc == DCDF_OK)
-            rc = D.run(r, P.walk.slabs, g.slab0, g.slab1, [&](const Slab& b) {
-                launch_spell_fold(D.folds.as<SpellFold>() + b.fold0, b.fold1 - b.fold0, D.slab.as<int64_t>(), nullptr, d_dst, d_scr.as<uint32_t>(), ops);
-            });
+            rc = launch_bulk_spell(r->d_refs.as<ChunkRef>(), R.units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr.as<uint32_t>(), ops);
+        if (rc == DCDF_OK) rc = R.walk.run<k_spell_fold>(r, P.walk, g, 16, d_dst, d_scr.as<uint32_t>(), ops);
         if (rc != DCDF_OK) return rc;
     }
-    return batch_epilogue(W, ev, true, kernel_ms);
+    return R.end(W, true, kernel_ms);
 }
 // ---- reduce over space: per-instant min / max / sum / count / mean of the selected cells of a cube (k2r_space.h) ------------
 // The plan is plan_reduce_space's (k2r_plan.h): records of the pieces in a pooled scratch array, in blocks [slot][instant] that
@@ -493,12 +510,6 @@ k_space_finish(const SpaceJob* __restrict__ jobs, uint32_t n, const SpacePartial
         }
     }
 }
-// records of one batch of the plan (K2R_SPACE_RECORDS overrides: tests of the batch cut); 40 bytes each
-static uint64_t space_record_cap() {
-    const char* e = std::getenv("K2R_SPACE_RECORDS");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (uint64_t)6 << 20;
-}
 extern "C" int dcdf_space_fold_records(const uint64_t* hi, const uint64_t* lo, const uint32_t* scale, size_t n, double* sum) {
     if ((n && (!hi || !lo || !scale)) || !sum) return DCDF_ERR_BAD_ARG;
     U192 acc{0, 0, 0};
@@ -527,44 +538,32 @@ extern "C" int dcdf_raster_reduce_space_batch(const dcdf_raster* r, const dcdf_c
     SpacePlan P(reduce_slab_cells());
     rc = plan_reduce_space(r->plan(), cubes, nq, W.base.data(), M.moff.data(), r->all_node, space_record_cap(), bulk_wanted_units(), P);
     if (rc != DCDF_OK) return rc;
-    put_stats(stats, P.stats);
-    if (W.total == 0) return DCDF_OK;
-    DevBuf d_units, d_cfolds, d_jobs, d_recs;
-    WalkDev D;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    DevBuf d_jobs, d_recs;
+    RegionRun R;
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
     double* const d_dst = (double*)W.dst();
     rc = M.stage(cubes, nq, mask_offset);
     if (rc != DCDF_OK) return rc;
     K2R_HIP(d_recs.alloc_pooled(P.rec_max * sizeof(SpacePartial)));
-    rc = upload_some(d_units, P.units);
-    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
-    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    rc = R.upload(P);
     if (rc != DCDF_OK) return rc;
     K2R_HIP(upload(d_jobs, P.jobs));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
+    rc = R.start();
+    if (rc != DCDF_OK) return rc;
     SpacePartial* const recs = d_recs.as<SpacePartial>();
     for (const SpaceBatch& b : P.batches) {
-        if (b.const1 > b.const0) {
-            hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
-                               d_cfolds.as<SpaceFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), M.p, recs);
-            K2R_HIP(hipGetLastError());
-        }
-        rc = launch_bulk_space(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<SpaceUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
-                               recs, live);
+        rc = R.fold_consts<k_space_fold, SpaceFold>(r, b, 1, M.p, recs);
         if (rc == DCDF_OK)
-            rc = D.run(r, P.walk.slabs, b.slab0, b.slab1, [&](const Slab& sl) {
-                hipLaunchKernelGGL(k_space_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
-                                   dim3(256), 0, 0, D.folds.as<SpaceFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr,
-                                   M.p, recs);
-            });
+            rc = launch_bulk_space(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), R.units.as<SpaceUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
+                                   recs, live);
+        if (rc == DCDF_OK) rc = R.walk.run<k_space_fold>(r, P.walk, b, std::min<uint32_t>(P.walk.fold_nt, 1024), M.p, recs);
         if (rc != DCDF_OK) return rc;
         hipLaunchKernelGGL(k_space_finish, dim3((uint32_t)std::min<size_t>(b.job1 - b.job0, 1u << 20), std::min<uint32_t>(b.job_nt, 1024)), dim3(256), 0,
                            0, d_jobs.as<SpaceJob>() + b.job0, (uint32_t)(b.job1 - b.job0), recs, d_dst, ops);
         K2R_HIP(hipGetLastError());
     }
-    return batch_epilogue(W, ev, true, kernel_ms);
+    return R.end(W, true, kernel_ms);
 }
 // ---- value histograms: per instant, how many selected cells of a cube fall into every bin of shared edges (k2r_hist.h) -------
 // The plan is plan_histogram's (k2r_plan.h).  Every piece adds its counts to the cube's own [instants][bins] array with device-scope
@@ -674,49 +673,23 @@ extern "C" int dcdf_raster_histogram_batch(const dcdf_raster* r, const dcdf_cube
     }
     rc = launch_bulk_hist(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<HistUnit>(), (uint32_t)P.units.size(), M.p, d_thr.as<int32_t>(),
                           n_bins, d_dst);
-    if (rc == DCDF_OK)
-        rc = D.run(r, P.walk.slabs, 0, P.walk.slabs.size(), [&](const Slab& sl) {
-            hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
-                               dim3(256), 0, 0, D.folds.as<HistFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr, M.p,
-                               d_edges.as<double>(), n_bins, d_dst);
-        });
+    for (size_t s = 0; rc == DCDF_OK && s < P.walk.slabs.size(); s++) {
+        const Slab& sl = P.walk.slabs[s];
+        rc = launch_window_items_dev(r->d_refs, D.items.as<WinItem>() + sl.item0, (uint32_t)(sl.item1 - sl.item0), D.slab.p, DCDF_I64, nullptr, nullptr,
+                                     r->all_node, r->all_narrow);
+        if (rc != DCDF_OK) break;
+        hipLaunchKernelGGL(k_hist_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
+                           dim3(256), 0, 0, D.folds.as<HistFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr, M.p,
+                           d_edges.as<double>(), n_bins, d_dst);
+        K2R_HIP(hipGetLastError());
+    }
     if (rc != DCDF_OK) return rc;
     return batch_epilogue(W, ev, true, kernel_ms);
 }
 // ---- zonal statistics: per (zone, instant) of a cube, reduce_space's statistics over the cells that carry the zone's label ----
 // The plan is plan_zonal's (k2r_plan.h), the accumulators and their arithmetic k2r_zonal.h's.  A batch of the plan: its entries
 // zeroed, every piece's adds (elided pieces, the bulk kernel's units, the window walk's slabs), then k_zonal_finish.
-//
-// The labels: cube q's elements start at p[moff[q]] -- in the caller's device array, or in a pooled copy of the host arrays of the
-// cubes that have instants, one after the other (CubeMasks with 2-byte elements).
-struct CubeLabels {
-    std::vector<uint64_t> moff;
-    uint64_t total = 0;
-    const uint16_t* p;
-    bool host;
-    DevBuf d_labels;
-    CubeLabels(const dcdf_cube* cubes, size_t nq, const uint16_t* labels, const uint64_t* label_offset, int label_mem)
-        : moff(nq, 0), p(labels), host(label_mem == DCDF_MEM_HOST) {
-        for (size_t q = 0; q < nq; q++) {
-            const dcdf_cube c = norm_cube(cubes[q]);
-            if (c.end == c.start) continue;
-            moff[q] = host ? total : label_offset[q];
-            total += (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-        }
-    }
-    int stage(const dcdf_cube* cubes, size_t nq, const uint64_t* label_offset) {
-        if (!host) return DCDF_OK;
-        K2R_HIP(d_labels.alloc_pooled(std::max<uint64_t>(total, 1) * sizeof(uint16_t)));
-        for (size_t q = 0; q < nq; q++) {
-            const dcdf_cube c = norm_cube(cubes[q]);
-            const uint64_t n = (uint64_t)(c.bottom - c.top) * (c.right - c.left);
-            if (c.end == c.start || n == 0) continue;
-            K2R_HIP(hipMemcpy((uint16_t*)d_labels.p + moff[q], p + label_offset[q], n * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-        p = (const uint16_t*)d_labels.p;
-        return DCDF_OK;
-    }
-};
+// The labels are CubeLabels.
 // A thread takes a run of consecutive cells of the piece (row-major) and folds every run of equal labels among them into one
 // add per (zone, instant): neighbours mostly share a zone.  A piece of the window walk's slab: a workgroup per (piece, instant),
 // the cells' stored integers widened by the leaf's own encoding, two-limb sums since |m| <= 2^63.  An elided piece (blockIdx.y == 0
@@ -800,12 +773,6 @@ k_zonal_finish(const ZonalSpan* __restrict__ spans, uint32_t n, uint32_t n_zones
         }
     }
 }
-// bytes of one batch's accumulators (K2R_ZONAL_ACC_BYTES overrides: tests of the batch cut); 72 per (zone, instant)
-static uint64_t zonal_acc_cap() {
-    const char* e = std::getenv("K2R_ZONAL_ACC_BYTES");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (uint64_t)128 << 20;
-}
 extern "C" int dcdf_zonal_fold_limbs(const int64_t limbs[6], double* sum) {
     if (!limbs || !sum) return DCDF_ERR_BAD_ARG;
     const int64_t l[6] = {limbs[0], limbs[1], limbs[2], limbs[3], limbs[4], limbs[5]};
@@ -833,44 +800,32 @@ extern "C" int dcdf_raster_zonal_batch(const dcdf_raster* r, const dcdf_cube* cu
     ZonalPlan P(reduce_slab_cells());
     rc = plan_zonal(r->plan(), cubes, nq, W.base.data(), M.moff.data(), n_zones, r->all_node, zonal_acc_cap(), bulk_wanted_units(), P);
     if (rc != DCDF_OK) return rc;
-    put_stats(stats, P.stats);
-    if (W.total == 0) return DCDF_OK;
-    DevBuf d_units, d_cfolds, d_spans, d_acc;
-    WalkDev D;
-    if (!W.to_dev) K2R_HIP(W.stage.alloc_pooled(W.total * W.es));
+    DevBuf d_spans, d_acc;
+    RegionRun R;
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
     double* const d_dst = (double*)W.dst();
     rc = M.stage(cubes, nq, label_offset);
     if (rc != DCDF_OK) return rc;
     K2R_HIP(d_acc.alloc_pooled(P.entries_max * ZONAL_BYTES));
-    rc = upload_some(d_units, P.units);
-    if (rc == DCDF_OK) rc = upload_some(d_cfolds, P.cfolds);
-    if (rc == DCDF_OK) rc = D.upload(P.walk);
+    rc = R.upload(P);
     if (rc != DCDF_OK) return rc;
     K2R_HIP(upload(d_spans, P.spans));
-    EventPair ev;
-    K2R_HIP(ev.create());
-    K2R_HIP(hipEventRecord(ev.e0, 0));
+    rc = R.start();
+    if (rc != DCDF_OK) return rc;
     uint64_t* const acc = d_acc.as<uint64_t>();
     for (const ZonalBatch& b : P.batches) {
         K2R_HIP(hipMemsetAsync(acc, 0, b.entries * ZONAL_BYTES, 0));
-        if (b.const1 > b.const0) {
-            hipLaunchKernelGGL(k_zonal_fold, dim3((uint32_t)std::min<size_t>(b.const1 - b.const0, 1u << 20), 1), dim3(256), 0, 0,
-                               d_cfolds.as<ZonalFold>() + b.const0, (uint32_t)(b.const1 - b.const0), nullptr, r->d_vals.as<int64_t>(), M.p, n_zones, acc, live);
-            K2R_HIP(hipGetLastError());
-        }
-        rc = launch_bulk_zonal(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), d_units.as<ZonalUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
-                               n_zones, acc, live);
+        rc = R.fold_consts<k_zonal_fold, ZonalFold>(r, b, 1, M.p, n_zones, acc, live);
         if (rc == DCDF_OK)
-            rc = D.run(r, P.walk.slabs, b.slab0, b.slab1, [&](const Slab& sl) {
-                hipLaunchKernelGGL(k_zonal_fold, dim3((uint32_t)std::min<size_t>(sl.fold1 - sl.fold0, 1u << 20), std::min<uint32_t>(P.walk.fold_nt, 1024)),
-                                   dim3(256), 0, 0, D.folds.as<ZonalFold>() + sl.fold0, (uint32_t)(sl.fold1 - sl.fold0), D.slab.as<int64_t>(), nullptr,
-                                   M.p, n_zones, acc, live);
-            });
+            rc = launch_bulk_zonal(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), R.units.as<ZonalUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), M.p,
+                                   n_zones, acc, live);
+        if (rc == DCDF_OK) rc = R.walk.run<k_zonal_fold>(r, P.walk, b, std::min<uint32_t>(P.walk.fold_nt, 1024), M.p, n_zones, acc, live);
         if (rc != DCDF_OK) return rc;
         const uint64_t big = (uint64_t)n_zones * P.span_nt;
         hipLaunchKernelGGL(k_zonal_finish, dim3((uint32_t)std::min<size_t>(b.span1 - b.span0, 1u << 16), (uint32_t)std::min<uint64_t>((big + 255) / 256, 4096)),
                            dim3(256), 0, 0, d_spans.as<ZonalSpan>() + b.span0, (uint32_t)(b.span1 - b.span0), n_zones, acc, d_dst, ops);
         K2R_HIP(hipGetLastError());
     }
-    return batch_epilogue(W, ev, true, kernel_ms);
+    return R.end(W, true, kernel_ms);
 }

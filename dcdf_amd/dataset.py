@@ -371,9 +371,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         """The instants [start, stop) of the whole variable, decompressed: what window(start, stop, 0, rows, 0, cols) returns,
         through raster().decode -- every chunk is decoded block by block in one call (dcdf_raster_decode_batch), elided tiles,
         nested levels and offset leaves included."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        self._check(start, stop, 0, R, 0, Cc)
+        stop, R, Cc = self._region(start, stop, 0, None, 0, None)
         if start == stop:
             return np.zeros((0, R, Cc), dtype=self.dtype)
         return self.raster().decode(start, stop, dtype=self.dtype)
@@ -384,11 +382,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         values window() returns widened to float64, NaN cells skipped; the sum is sequential in instant order.  Through
         raster().reduce_time: the encoded bytes are read once on the GPU and only the planes are written
         (dcdf_raster_reduce_time_batch)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        bottom = R if bottom is None else bottom
-        right = Cc if right is None else right
-        self._check(start, stop, top, bottom, left, right)
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
             from .raster import EncodedRaster
             names = EncodedRaster.reduce_ops(ops)[1]
@@ -402,11 +396,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         rule: NaN never hits, +-inf is unbounded); count = the hits, longest = the longest unbroken run of hits, longest_start =
         where the first such run began, first / last = the first / last hit; SPELL_NONE (0xffffffff) where nothing hit.  Through
         raster().spells: the encoded bytes are read once on the GPU and only the planes are written (dcdf_raster_spells_batch)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        bottom = R if bottom is None else bottom
-        right = Cc if right is None else right
-        self._check(start, stop, top, bottom, left, right)
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         from .raster import EncodedRaster
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
             EncodedRaster._spell_bounds(lower, upper, 1)
@@ -419,11 +409,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         the names of `ops`, over the values window() returns widened to float64, NaN cells skipped; the sum is the exact sum
         rounded once (math.fsum).  Through raster().reduce_space: the encoded bytes are read once on the GPU and only the series
         are written (dcdf_raster_reduce_space_batch)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        bottom = R if bottom is None else bottom
-        right = Cc if right is None else right
-        self._check(start, stop, top, bottom, left, right)
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
             from .raster import EncodedRaster
             return {n: np.empty(0, dtype=np.float64) for n in EncodedRaster.reduce_ops(ops)[1]}
@@ -436,11 +422,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         reduce_space's for the zone's cells (the sum exact, rounded once; a zone whose cells are all NaN gets NaN, NaN, +0.0, 0,
         NaN).  More than 65535 distinct ids: ValueError.  Through raster().zonal: the encoded bytes are read once on the GPU
         whatever the number of zones (dcdf_raster_zonal_batch)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        bottom = R if bottom is None else bottom
-        right = Cc if right is None else right
-        self._check(start, stop, top, bottom, left, right)
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         from . import _lib
         from .raster import EncodedRaster
         names = EncodedRaster.reduce_ops(ops)[1]
@@ -466,11 +448,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         number of values window() returns, widened to float64, in every bin of `edges` (bins + 1 increasing values; edges[b] <= x
         < edges[b + 1], the last bin closed, NaN cells and values outside the edges counted nowhere).  Through raster().histogram:
         the encoded bytes are read once on the GPU and only the counts are written (dcdf_raster_histogram_batch)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else stop
-        bottom = R if bottom is None else bottom
-        right = Cc if right is None else right
-        self._check(start, stop, top, bottom, left, right)
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         from .raster import EncodedRaster
         e = EncodedRaster._edges(edges)
         if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
@@ -573,6 +551,13 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
     # ---- routing ----------------------------------------------------------------------------------------------------------
     def _root(self):
         return self._resolver.node(self.cid)
+
+    def _region(self, start, stop, top, bottom, left, right):
+        """(stop, bottom, right) of a region method -- None = the variable's last instant / row / column --, the region checked."""
+        T, R, Cc = self.shape
+        stop, bottom, right = T if stop is None else stop, R if bottom is None else bottom, Cc if right is None else right
+        self._check(start, stop, top, bottom, left, right)
+        return stop, bottom, right
 
     def _check(self, start, stop, top, bottom, left, right):  # mmarray.rs:218-229 panics; here an IndexError
         t, r, c = self.shape

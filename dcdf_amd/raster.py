@@ -85,29 +85,63 @@ class EncodedRaster:
         except Exception:
             pass
 
+    # ---- the region calls (dcdf_raster_*_batch over whole cubes) ----------------------------------------------------------------
+    @staticmethod
+    def _cubes(cubes):
+        return np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+
+    @staticmethod
+    def _extent(q, lo):
+        """|q[:, lo + 1] - q[:, lo]| as int64 (reversed bounds are reordered, geom.rs:83-103)"""
+        return np.abs(q[:, lo + 1].astype(np.int64) - q[:, lo])
+
+    def _region_call(self, name, q, counts, dtype, args, zeroed=False, stats=True, out_device_ptr=None, out_offset=None):
+        """dcdf_raster_<name>_batch over the cubes q, in either form.  Host form (out_device_ptr None): cube i gets counts()[i]
+        elements of dtype, one cube after the other; returns (flat array, offsets uint64[n], kernel ms, stats).  Device form: the
+        caller's out_offset; returns (kernel ms, stats).  args(n, out, mem, off, stats): the call's arguments between the cubes and
+        the kernel ms, in its own order.  stats = False: the call has none, and none is returned."""
+        ms = C.c_float()
+        st = np.zeros(3, dtype=np.uint64) if stats else None
+        if out_device_ptr is None:
+            vol = counts().astype(np.uint64)
+            off = np.zeros(len(q), dtype=np.uint64)
+            if len(q) > 1:
+                off[1:] = np.cumsum(vol)[:-1]
+            out = (np.zeros if zeroed else np.empty)(max(1, int(vol.sum())), dtype=dtype)
+            ptr, mem = out.ctypes.data, L.MEM_HOST
+        else:
+            off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+            out, ptr, mem = None, out_device_ptr, L.MEM_DEVICE
+        entry = "raster_%s_batch" % name
+        own = args(C.c_size_t(len(q)), C.c_void_p(ptr), mem, C.c_void_p(off.ctypes.data), None if st is None else C.c_void_p(st.ctypes.data))
+        L.check(getattr(L.lib(), "dcdf_" + entry)(self._handle(), C.c_void_p(q.ctypes.data), *own, C.byref(ms)), entry)
+        tail = (ms.value,) if st is None else (ms.value, st)
+        return tail if out is None else (out, off) + tail
+
+    def _window_args(self, start, stop, window):
+        """(start, stop, top, bottom, left, right) of a whole-raster method: stop defaults to the last instant, window = (top,
+        bottom, left, right) to all cells; both inside the raster."""
+        T, R, Cc = self.shape
+        stop = T if stop is None else int(stop)
+        start = int(start)
+        if not 0 <= start <= stop <= T:
+            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
+        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
+            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        return start, stop, top, bottom, left, right
+
     def fill_windows_flat(self, cubes, dtype=np.int64, out_device_ptr=None, out_offset=None):
         """fill_window of dataset-level cubes [n, 6] through dcdf_raster_fill_window_batch.  Host form: returns (flat array of
         dtype, offsets uint64[n], kernel ms): window q is flat[offsets[q]:] shaped (t, r, c).  Device form (out_device_ptr +
         out_offset in elements): the windows are written there, returns kernel ms."""
         from .chunk import _ENC
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        q = self._cubes(cubes)
         dtype = np.dtype(dtype)
-        ms = C.c_float()
-        if out_device_ptr is None:
-            vol = np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64)  # (reversed bounds are reordered, geom.rs:83-103)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=dtype)
-            L.check(L.lib().dcdf_raster_fill_window_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
-                                                          C.c_void_p(out.ctypes.data), _ENC[dtype], L.MEM_HOST, C.c_void_p(off.ctypes.data),
-                                                          C.byref(ms)), "raster_fill_window_batch")
-            return out, off, ms.value
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_fill_window_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
-                                                      C.c_void_p(out_device_ptr), _ENC[dtype], L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
-                                                      C.byref(ms)), "raster_fill_window_batch")
-        return ms.value
+        res = self._region_call("fill_window", q, lambda: self._extent(q, 0) * self._extent(q, 2) * self._extent(q, 4), dtype,
+                                lambda n, out, mem, off, stats: (n, out, _ENC[dtype], mem, off), stats=False, out_device_ptr=out_device_ptr,
+                                out_offset=out_offset)
+        return res[0] if out_device_ptr is not None else res
 
     def decode_flat(self, cubes, dtype=np.int64, out_device_ptr=None, out_offset=None):
         """Decompress dataset-level cubes [n, 6] through dcdf_raster_decode_batch: the values fill_windows_flat returns, bit for
@@ -115,25 +149,11 @@ class EncodedRaster:
         offsets uint64[n], kernel ms, stats); device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).
         stats = uint64[3]: cells written by the bulk kernel, by the fallback walk, by the elided fill."""
         from .chunk import _ENC
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        q = self._cubes(cubes)
         dtype = np.dtype(dtype)
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
-        if out_device_ptr is None:
-            vol = np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64)  # (reversed bounds are reordered, geom.rs:83-103)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=dtype)
-            L.check(L.lib().dcdf_raster_decode_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
-                                                     C.c_void_p(out.ctypes.data), _ENC[dtype], L.MEM_HOST, C.c_void_p(off.ctypes.data),
-                                                     C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_decode_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_decode_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)),
-                                                 C.c_void_p(out_device_ptr), _ENC[dtype], L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
-                                                 C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_decode_batch")
-        return ms.value, stats
+        return self._region_call("decode", q, lambda: self._extent(q, 0) * self._extent(q, 2) * self._extent(q, 4), dtype,
+                                 lambda n, out, mem, off, stats: (n, out, _ENC[dtype], mem, off, stats), out_device_ptr=out_device_ptr,
+                                 out_offset=out_offset)
 
     def decode(self, start=0, stop=None, dtype=np.int64):
         """The instants [start, stop) of the whole raster, decompressed: ndarray [stop - start, rows, cols] of dtype."""
@@ -148,20 +168,29 @@ class EncodedRaster:
         return out[:(stop - start) * R * Cc].reshape(stop - start, R, Cc)
 
     @staticmethod
-    def reduce_ops(ops):
-        """ops of reduce_time / reduce_time_flat as (bitmask, names in plane order): a DCDF_REDUCE_* bitmask, one name or an
-        iterable of "min" / "max" / "sum" / "count" / "mean"."""
+    def _ops(ops, table, what):
+        """reduce_ops / spell_ops over their table of {name: bit}"""
         if isinstance(ops, (int, np.integer)):
             mask = int(ops)
         else:
             mask = 0
             for name in ([ops] if isinstance(ops, str) else ops):
-                if name not in L.REDUCE_OPS:
-                    raise ValueError("reduce_time: unknown statistic %r (one of %s)" % (name, ", ".join(L.REDUCE_OPS)))
-                mask |= L.REDUCE_OPS[name]
+                if name not in table:
+                    raise ValueError("%s: unknown statistic %r (one of %s)" % (what, name, ", ".join(table)))
+                mask |= table[name]
         if not 0 < mask < 32:
-            raise ValueError("reduce_time: ops %r is not a set of min, max, sum, count, mean" % (ops,))
-        return mask, [n for n, b in L.REDUCE_OPS.items() if mask & b]
+            raise ValueError("%s: ops %r is not a set of %s" % (what, ops, ", ".join(table)))
+        return mask, [n for n, b in table.items() if mask & b]
+
+    @staticmethod
+    def reduce_ops(ops):
+        """ops of reduce_time / reduce_time_flat as (bitmask, names in plane order): a DCDF_REDUCE_* bitmask, one name or an
+        iterable of "min" / "max" / "sum" / "count" / "mean"."""
+        return EncodedRaster._ops(ops, L.REDUCE_OPS, "reduce_time")
+
+    def _planes(self, q, n):
+        """elements of n [rows, cols] planes per cube (a cube without instants writes nothing)"""
+        return np.where(q[:, 1] == q[:, 0], 0, self._extent(q, 2) * self._extent(q, 4) * n)
 
     def reduce_time_flat(self, cubes, ops, out_device_ptr=None, out_offset=None):
         """Per-cell statistics over time of dataset-level cubes [n, 6] through dcdf_raster_reduce_time_batch: cube q yields one
@@ -171,38 +200,15 @@ class EncodedRaster:
         form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk
         kernel, by the fallback walk, from elided leaves."""
         mask, names = self.reduce_ops(ops)
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
-        if out_device_ptr is None:
-            empty = (q[:, 1] == q[:, 0])
-            vol = np.abs((q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64) * np.uint64(len(names))
-            vol[empty] = 0  # (a cube without instants writes nothing)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=np.float64)
-            L.check(L.lib().dcdf_raster_reduce_time_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)), C.c_uint32(mask),
-                                                          C.c_void_p(out.ctypes.data), L.MEM_HOST, C.c_void_p(off.ctypes.data),
-                                                          C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_time_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_reduce_time_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_size_t(len(q)), C.c_uint32(mask),
-                                                      C.c_void_p(out_device_ptr), L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
-                                                      C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_time_batch")
-        return ms.value, stats
+        q = self._cubes(cubes)
+        return self._region_call("reduce_time", q, lambda: self._planes(q, len(names)), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), out, mem, off, stats), out_device_ptr=out_device_ptr,
+                                 out_offset=out_offset)
 
     def reduce_time(self, ops, start=0, stop=None, window=None):
         """{statistic: ndarray [rows, cols] float64} over the instants [start, stop) of the whole raster, or of `window` =
         (top, bottom, left, right).  Without instants: NaN planes, count 0 and sum 0."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
-        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
-        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
-            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.reduce_ops(ops)
         rows, cols = bottom - top, right - left
         if start == stop or rows * cols == 0:
@@ -214,17 +220,7 @@ class EncodedRaster:
     def spell_ops(ops):
         """ops of spells / spells_flat as (bitmask, names in plane order): a DCDF_SPELL_* bitmask, one name or an iterable of
         "count" / "longest" / "longest_start" / "first" / "last"."""
-        if isinstance(ops, (int, np.integer)):
-            mask = int(ops)
-        else:
-            mask = 0
-            for name in ([ops] if isinstance(ops, str) else ops):
-                if name not in L.SPELL_OPS:
-                    raise ValueError("spells: unknown statistic %r (one of %s)" % (name, ", ".join(L.SPELL_OPS)))
-                mask |= L.SPELL_OPS[name]
-        if not 0 < mask < 32:
-            raise ValueError("spells: ops %r is not a set of count, longest, longest_start, first, last" % (ops,))
-        return mask, [n for n, b in L.SPELL_OPS.items() if mask & b]
+        return EncodedRaster._ops(ops, L.SPELL_OPS, "spells")
 
     @staticmethod
     def _spell_bounds(lower, upper, n):
@@ -245,29 +241,11 @@ class EncodedRaster:
         elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
         leaves."""
         mask, names = self.spell_ops(ops)
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        q = self._cubes(cubes)
         lo, hi = self._spell_bounds(lower, upper, len(q))
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
-        if out_device_ptr is None:
-            empty = (q[:, 1] == q[:, 0])
-            vol = np.abs((q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).astype(np.uint64) * np.uint64(len(names))
-            vol[empty] = 0  # (a cube without instants writes nothing)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=np.uint32)
-            L.check(L.lib().dcdf_raster_spells_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
-                                                     C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), C.c_void_p(out.ctypes.data),
-                                                     L.MEM_HOST, C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
-                    "raster_spells_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_spells_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
-                                                 C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), C.c_void_p(out_device_ptr),
-                                                 L.MEM_DEVICE, C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
-                "raster_spells_batch")
-        return ms.value, stats
+        return self._region_call("spells", q, lambda: self._planes(q, len(names)), np.uint32,
+                                 lambda n, out, mem, off, stats: (C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), n, C.c_uint32(mask), out, mem,
+                                                                  off, stats), out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     @staticmethod
     def _spells_none(names, rows, cols):
@@ -277,14 +255,7 @@ class EncodedRaster:
         """{statistic: ndarray [rows, cols] uint32} of the hits of [lower, upper] over the instants [start, stop) of the whole
         raster, or of `window` = (top, bottom, left, right); instants are counted from `start`.  Without instants: zeros for count
         and longest, SPELL_NONE for the others."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
-        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
-        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
-            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.spell_ops(ops)
         self._spell_bounds(lower, upper, 1)
         rows, cols = bottom - top, right - left
@@ -294,22 +265,38 @@ class EncodedRaster:
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
     @staticmethod
+    def _device_arrays(q, arrays, what, noun):
+        """One array per cube (masks, labels) already on the device, given as (device pointer, offsets uint64[n]): (pointer, offsets,
+        memory kind, what must stay alive over the call); None when `arrays` is not of that form."""
+        if not (isinstance(arrays, tuple) and len(arrays) == 2 and isinstance(arrays[0], (int, np.integer))):
+            return None
+        keep = np.ascontiguousarray(np.asarray(arrays[1], dtype=np.uint64))
+        if keep.shape != (len(q),):
+            raise ValueError("%s: %d %s offsets for %d cubes" % (what, keep.size, noun, len(q)))
+        return C.c_void_p(int(arrays[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE, keep
+
+    @staticmethod
+    def _host_arrays(parts, dtype):
+        """The same for host arrays: the cubes' flat parts one after the other, one spare element behind them."""
+        off = np.zeros(len(parts), dtype=np.uint64)
+        if len(parts) > 1:
+            off[1:] = np.cumsum([p.size for p in parts])[:-1]
+        flat = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=dtype)]))
+        return C.c_void_p(flat.ctypes.data), C.c_void_p(off.ctypes.data), L.MEM_HOST, (flat, off)
+
+    @staticmethod
     def _mask_args(q, masks, what):
         """The mask arguments of dcdf_raster_reduce_space_batch / dcdf_raster_histogram_batch for the cubes q: (pointer, offsets,
         memory kind, what must stay alive over the call).  masks as reduce_space_flat documents them."""
-        m_ptr, m_off, m_mem, keep = None, None, L.MEM_HOST, None
-        if isinstance(masks, tuple) and len(masks) == 2 and isinstance(masks[0], (int, np.integer)):
-            keep = np.ascontiguousarray(np.asarray(masks[1], dtype=np.uint64))
-            if keep.shape != (len(q),):
-                raise ValueError("%s: %d mask offsets for %d cubes" % (what, keep.size, len(q)))
-            m_ptr, m_off, m_mem = C.c_void_p(int(masks[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE
-        elif masks is not None:
+        dev = EncodedRaster._device_arrays(q, masks, what, "mask")
+        if dev is not None:
+            return dev
+        if masks is not None:
             masks = list(masks)
             if len(masks) != len(q):
                 raise ValueError("%s: %d masks for %d cubes" % (what, len(masks), len(q)))
             if any(m is not None for m in masks):
-                rows = np.abs(q[:, 3].astype(np.int64) - q[:, 2])
-                cols = np.abs(q[:, 5].astype(np.int64) - q[:, 4])
+                rows, cols = EncodedRaster._extent(q, 2), EncodedRaster._extent(q, 4)
                 parts = []
                 for i, m in enumerate(masks):
                     shape = (int(rows[i]), int(cols[i]))
@@ -320,13 +307,8 @@ class EncodedRaster:
                     if m.shape != shape:
                         raise ValueError("%s: mask %d has shape %r, its cube %r" % (what, i, m.shape, shape))
                     parts.append((m != 0).astype(np.uint8).ravel())
-                moff = np.zeros(len(q), dtype=np.uint64)
-                if len(q) > 1:
-                    moff[1:] = np.cumsum([p.size for p in parts])[:-1]
-                flat_mask = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=np.uint8)]))
-                keep = (flat_mask, moff)
-                m_ptr, m_off = C.c_void_p(flat_mask.ctypes.data), C.c_void_p(moff.ctypes.data)
-        return m_ptr, m_off, m_mem, keep
+                return EncodedRaster._host_arrays(parts, np.uint8)
+        return None, None, L.MEM_HOST, None
 
     def reduce_space_flat(self, cubes, ops, masks=None, out_device_ptr=None, out_offset=None):
         """Per-instant statistics over the selected cells of dataset-level cubes [n, 6] through dcdf_raster_reduce_space_batch: cube
@@ -338,38 +320,17 @@ class EncodedRaster:
         instants).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells
         read by the bulk kernel, by the fallback walk, from elided leaves."""
         mask, names = self.reduce_ops(ops)
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
+        q = self._cubes(cubes)
         m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "reduce_space")
-        if out_device_ptr is None:
-            vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(len(names))
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=np.float64)
-            L.check(L.lib().dcdf_raster_reduce_space_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), m_ptr, m_off,
-                                                           m_mem, C.c_void_p(out.ctypes.data), L.MEM_HOST, C.c_void_p(off.ctypes.data),
-                                                           C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_space_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_reduce_space_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), m_ptr, m_off,
-                                                       m_mem, C.c_void_p(out_device_ptr), L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
-                                                       C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_reduce_space_batch")
-        return ms.value, stats
+        return self._region_call("reduce_space", q, lambda: self._extent(q, 0) * len(names), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), m_ptr, m_off, m_mem, out, mem, off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def reduce_space(self, ops, start=0, stop=None, window=None, mask=None):
         """{statistic: ndarray [stop - start] float64} over the cells of the whole raster, or of `window` = (top, bottom, left,
         right), at every instant of [start, stop); mask: [rows, cols] of the window, non-zero = the cell is selected.  Without
         instants: empty arrays."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
-        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
-        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
-            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         bits, names = self.reduce_ops(ops)
         if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
             raise ValueError("reduce_space: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
@@ -383,16 +344,13 @@ class EncodedRaster:
     def _label_args(q, labels, what):
         """The label arguments of dcdf_raster_zonal_batch for the cubes q: (pointer, offsets, memory kind, what must stay alive over
         the call, the largest label below ZONE_NONE or -1 when unknown).  labels as zonal_flat documents them."""
-        if isinstance(labels, tuple) and len(labels) == 2 and isinstance(labels[0], (int, np.integer)):
-            keep = np.ascontiguousarray(np.asarray(labels[1], dtype=np.uint64))
-            if keep.shape != (len(q),):
-                raise ValueError("%s: %d label offsets for %d cubes" % (what, keep.size, len(q)))
-            return C.c_void_p(int(labels[0])), C.c_void_p(keep.ctypes.data), L.MEM_DEVICE, keep, -1
+        dev = EncodedRaster._device_arrays(q, labels, what, "label")
+        if dev is not None:
+            return dev + (-1,)
         labels = list(labels)
         if len(labels) != len(q):
             raise ValueError("%s: %d label arrays for %d cubes" % (what, len(labels), len(q)))
-        rows = np.abs(q[:, 3].astype(np.int64) - q[:, 2])
-        cols = np.abs(q[:, 5].astype(np.int64) - q[:, 4])
+        rows, cols = EncodedRaster._extent(q, 2), EncodedRaster._extent(q, 4)
         parts = []
         for i, m in enumerate(labels):
             m = np.asarray(m)
@@ -401,12 +359,10 @@ class EncodedRaster:
             if m.shape != (int(rows[i]), int(cols[i])):
                 raise ValueError("%s: labels %d have shape %r, their cube %r" % (what, i, m.shape, (int(rows[i]), int(cols[i]))))
             parts.append(m.ravel())
-        loff = np.zeros(len(q), dtype=np.uint64)
-        if len(q) > 1:
-            loff[1:] = np.cumsum([p.size for p in parts])[:-1]
-        flat = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=np.uint16)]))
+        host = EncodedRaster._host_arrays(parts, np.uint16)
+        flat = host[3][0]
         named = flat[:-1][flat[:-1] != L.ZONE_NONE]
-        return C.c_void_p(flat.ctypes.data), C.c_void_p(loff.ctypes.data), L.MEM_HOST, (flat, loff), int(named.max()) if named.size else -1
+        return host + (int(named.max()) if named.size else -1,)
 
     def zonal_flat(self, cubes, ops, labels, n_zones, out_device_ptr=None, out_offset=None):
         """Zonal statistics of dataset-level cubes [n, 6] through dcdf_raster_zonal_batch: reduce_space_flat's statistics for every
@@ -422,39 +378,18 @@ class EncodedRaster:
         n_zones = int(n_zones)
         if not 1 <= n_zones <= 65535:
             raise ValueError("zonal: n_zones %d outside 1 .. 65535" % n_zones)
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
+        q = self._cubes(cubes)
         l_ptr, l_off, l_mem, keep, _ = self._label_args(q, labels, "zonal")
-        if out_device_ptr is None:
-            vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(len(names) * n_zones)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.empty(max(1, int(vol.sum())), dtype=np.float64)
-            L.check(L.lib().dcdf_raster_zonal_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), l_ptr, l_off, l_mem,
-                                                    C.c_uint32(n_zones), C.c_void_p(out.ctypes.data), L.MEM_HOST, C.c_void_p(off.ctypes.data),
-                                                    C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_zonal_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_zonal_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_uint32(mask), l_ptr, l_off, l_mem,
-                                                C.c_uint32(n_zones), C.c_void_p(out_device_ptr), L.MEM_DEVICE, C.c_void_p(off.ctypes.data),
-                                                C.c_void_p(stats.ctypes.data), C.byref(ms)), "raster_zonal_batch")
-        return ms.value, stats
+        return self._region_call("zonal", q, lambda: self._extent(q, 0) * (len(names) * n_zones), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), l_ptr, l_off, l_mem, C.c_uint32(n_zones), out, mem, off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def zonal(self, ops, labels, start=0, stop=None, window=None, n_zones=None):
         """{statistic: ndarray [n_zones, stop - start] float64} per zone of `labels` -- uint16 [rows, cols] of the whole raster, or
         of `window` = (top, bottom, left, right); ZONE_NONE and labels >= n_zones are in no zone -- at every instant of [start,
         stop).  n_zones defaults to the largest label present, ZONE_NONE apart, plus 1 (at least 1).  Without instants: empty
         matrices."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
-        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
-        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
-            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         bits, names = self.reduce_ops(ops)
         lab = np.asarray(labels)
         if lab.dtype != np.uint16 or lab.shape != (bottom - top, right - left):
@@ -491,40 +426,17 @@ class EncodedRaster:
         the bulk kernel, by the fallback walk, from elided leaves."""
         e = self._edges(edges)
         bins = e.size - 1
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        ms = C.c_float()
-        stats = np.zeros(3, dtype=np.uint64)
+        q = self._cubes(cubes)
         m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "histogram")
-        if out_device_ptr is None:
-            vol = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64) * np.uint64(bins)
-            off = np.zeros(len(q), dtype=np.uint64)
-            if len(q) > 1:
-                off[1:] = np.cumsum(vol)[:-1]
-            out = np.zeros(max(1, int(vol.sum())), dtype=np.uint64)
-            L.check(L.lib().dcdf_raster_histogram_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(e.ctypes.data),
-                                                        C.c_uint32(bins), m_ptr, m_off, m_mem, C.c_void_p(out.ctypes.data), L.MEM_HOST,
-                                                        C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
-                    "raster_histogram_batch")
-            return out, off, ms.value, stats
-        off = np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_histogram_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(e.ctypes.data),
-                                                    C.c_uint32(bins), m_ptr, m_off, m_mem, C.c_void_p(out_device_ptr), L.MEM_DEVICE,
-                                                    C.c_void_p(off.ctypes.data), C.c_void_p(stats.ctypes.data), C.byref(ms)),
-                "raster_histogram_batch")
-        return ms.value, stats
+        return self._region_call("histogram", q, lambda: self._extent(q, 0) * bins, np.uint64,
+                                 lambda n, out, mem, off, stats: (n, C.c_void_p(e.ctypes.data), C.c_uint32(bins), m_ptr, m_off, m_mem, out, mem, off, stats),
+                                 zeroed=True, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def histogram(self, edges, start=0, stop=None, window=None, mask=None):
         """ndarray [stop - start, bins] uint64: per instant of [start, stop), how many cells of the whole raster, or of `window` =
         (top, bottom, left, right), fall into every bin of `edges` (histogram_flat's rule); mask: [rows, cols] of the window,
         non-zero = the cell is selected.  Without instants: shape (0, bins)."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
-        top, bottom, left, right = (0, R, 0, Cc) if window is None else (int(x) for x in window)
-        if not (0 <= top <= bottom <= R and 0 <= left <= right <= Cc):
-            raise ValueError("window (%d:%d, %d:%d) outside the raster's %d x %d cells" % (top, bottom, left, right, R, Cc))
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         e = self._edges(edges)
         bins = e.size - 1
         if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
