@@ -64,7 +64,7 @@ SYMBOLS = [
     "dcdf_raster_create_tiles", "dcdf_raster_get_batch", "dcdf_raster_fill_cell_batch", "dcdf_raster_decode_batch",
     "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
     "dcdf_raster_histogram_batch", "dcdf_histogram_bounds", "dcdf_raster_spells_batch",
-    "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs",
+    "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs", "dcdf_raster_quantile_time_batch", "dcdf_quantile_select_host",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -73,6 +73,9 @@ HIST_MAX_BINS = 256  # DCDF_HIST_MAX_BINS
 SPELL_OPS = {"count": 1, "longest": 2, "longest_start": 4, "first": 8, "last": 16}
 SPELL_NONE = 0xffffffff  # DCDF_SPELL_NONE
 ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
+# dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
+QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
+QUANTILE_MAX_PROBS = 16
 
 
 def lib():
@@ -118,6 +121,11 @@ def lib():
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.dcdf_raster_quantile_time_batch.restype = C.c_int
+        L.dcdf_raster_quantile_time_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_quantile_select_host.restype = C.c_int
+        L.dcdf_quantile_select_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
         L.dcdf_histogram_bounds.restype = C.c_int
         L.dcdf_histogram_bounds.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L
@@ -136,6 +144,20 @@ def space_fold_records(records):
     check(lib().dcdf_space_fold_records(hi.ctypes.data if n else None, lo.ctypes.data if n else None, sc.ctypes.data if n else None, n,
                                         C.byref(out)), "space_fold_records")
     return out.value
+
+
+def quantile_select_host(x, probs, method="linear"):
+    """dcdf_quantile_select_host (host only, no GPU): the quantiles `probs` over axis 0 of x [instants, ...] as the device selects
+    them.  Returns (float64 [n_probs, ...], uint32 [...] passes over each cell's series after the first)."""
+    import numpy as np
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).ravel())
+    cells = int(np.prod(x.shape[1:], dtype=np.int64))
+    out = np.empty((max(p.size, 1),) + x.shape[1:], dtype=np.float64)
+    passes = np.zeros(x.shape[1:], dtype=np.uint32)
+    check(lib().dcdf_quantile_select_host(x.ctypes.data, x.shape[0], cells, p.ctypes.data, p.size, QUANTILE_METHODS[method], out.ctypes.data,
+                                          passes.ctypes.data), "quantile_select_host")
+    return out[:p.size], passes
 
 
 def zonal_fold_limbs(limbs):

@@ -1,4 +1,4 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells, zonal: k2r_raster_region.hip)
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells, zonal, quantile_time: k2r_raster_region.hip)
 // turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
 // A cube is cut into pieces, one per leaf it meets (raster_pieces).  A piece is of one of three kinds: on an elided leaf (one
@@ -14,6 +14,7 @@
 #include "k2r_bulk.h"
 #include "k2r_hist.h"
 #include "k2r_items.h"
+#include "k2r_quantile.h"
 #include "k2r_reduce.h"
 #include "k2r_space.h"
 #include "k2r_spell.h"
@@ -628,6 +629,104 @@ inline int plan_spells(const PlanRaster& g, const dcdf_cube* cubes, const double
         if (bad) return DCDF_ERR_BAD_ARG;
     }
     return B.assemble(P, node_wise, [](SpellFold& f, uint32_t a) { f.dt += a; });  // a part cut in time: its own first instant
+}
+
+// ---- quantiles over time -----------------------------------------------------------------------------------------------------
+// Selection needs all of a cell's values at once, so the cubes are decoded, band by band, into a bounded slab of stored integers
+// that k_quantile_select then reads.  A column is the part of a cube inside one leaf's place of the grid, over all the cube's
+// instants -- so within a segment all its cells are widened alike (QuantileSeg) --, cut further on multiples of 64 raster rows and
+// columns while its slab would exceed cap_bytes.  A band takes columns while their slabs fit (a column beyond the cap alone: the
+// cap bounds batching, not correctness).  Each band is a batch of sub-cubes for plan_decode, their bases inside the slab and the
+// output type DCDF_I64: bulk units, the walk's items and elided fills all land there by the kernels decode uses.  The bands'
+// lists lie one after the other; the bands run one after the other over the same slab.  base[q]: cube q's first output plane.
+struct QuantileBand {
+    size_t col0, col1, unit0, unit1, item0, item1, const0, const1;
+    uint64_t max_cells;  // of its largest column
+};
+struct QuantilePlan {
+    std::vector<QuantileCol> cols;
+    std::vector<QuantileSeg> segs;
+    std::vector<BulkUnit> units;
+    std::vector<WinItem> items;
+    std::vector<ConstPiece> consts;
+    std::vector<QuantileBand> bands;
+    uint64_t slab_max = 0;  // elements of the largest band's slab
+    uint64_t stats[3] = {0, 0, 0};
+};
+inline int plan_quantile_time(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, uint64_t cap_bytes, bool node_wise,
+                              uint32_t wanted, QuantilePlan& P) {
+    const uint64_t cap = std::max<uint64_t>(1, cap_bytes / sizeof(int64_t));  // elements
+    std::vector<dcdf_cube> subs;  // the current band's columns as cubes of their own, and where each starts in the slab
+    std::vector<uint64_t> sbase;
+    uint64_t used = 0;
+    QuantileBand cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    auto flush = [&]() -> int {
+        if (subs.empty()) return DCDF_OK;
+        DecodePlan D;
+        const int rc = plan_decode(g, subs.data(), subs.size(), sbase.data(), node_wise, wanted, D);
+        if (rc != DCDF_OK) return rc;
+        P.units.insert(P.units.end(), D.units.begin(), D.units.end());
+        P.items.insert(P.items.end(), D.items.begin(), D.items.end());
+        P.consts.insert(P.consts.end(), D.consts.begin(), D.consts.end());
+        for (int k = 0; k < 3; k++) P.stats[k] += D.stats[k];
+        cur.col1 = P.cols.size();
+        cur.unit1 = P.units.size();
+        cur.item1 = P.items.size();
+        cur.const1 = P.consts.size();
+        P.bands.push_back(cur);
+        P.slab_max = std::max(P.slab_max, used);
+        cur = QuantileBand{cur.col1, 0, cur.unit1, 0, cur.item1, 0, cur.const1, 0, 0};
+        subs.clear();
+        sbase.clear();
+        used = 0;
+        return DCDF_OK;
+    };
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        const uint32_t nt = c.end - c.start;
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        for (uint32_t ti = c.top / g.tile; ti <= (c.bottom - 1) / g.tile; ti++)
+            for (uint32_t tj = c.left / g.tile; tj <= (c.right - 1) / g.tile; tj++) {
+                const uint32_t top = std::max(c.top, ti * g.tile), bottom = std::min(c.bottom, (ti + 1) * g.tile);
+                const uint32_t left = std::max(c.left, tj * g.tile), right = std::min(c.right, (tj + 1) * g.tile);
+                // the column's table: one entry per segment the cube meets
+                const uint32_t seg0 = (uint32_t)P.segs.size();
+                for (uint32_t seg = c.start / g.cs; seg <= (c.end - 1) / g.cs; seg++) {
+                    const PlanLeaf& L = g.leaves[((uint64_t)seg * g.nti + ti) * g.ntj + tj];
+                    P.segs.push_back(QuantileSeg{std::max(c.start, seg * g.cs) - c.start, L.enc, L.fbits});
+                }
+                const uint32_t nseg = (uint32_t)P.segs.size() - seg0;
+                // rows and columns of a part: whole while the slab fits, else multiples of 64 (at least 64)
+                const uint64_t fit = cap / nt;  // cells
+                uint32_t pr = bottom - top, pc = right - left;
+                if ((uint64_t)pr * pc > fit) {
+                    pr = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(pr, fit / pc) / 64 * 64);
+                    if ((uint64_t)pr * pc > fit) pc = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(pc, fit / pr) / 64 * 64);
+                }
+                for (uint32_t r0 = top; r0 < bottom;) {
+                    const uint32_t r1 = std::min(bottom, pr >= bottom - top ? bottom : r0 / 64 * 64 + pr);
+                    for (uint32_t c0 = left; c0 < right;) {
+                        const uint32_t c1 = std::min(right, pc >= right - left ? right : c0 / 64 * 64 + pc);
+                        const uint64_t cells = (uint64_t)(r1 - r0) * (c1 - c0), need = cells * nt;
+                        if (used && used + need > cap) {
+                            const int rc = flush();
+                            if (rc != DCDF_OK) return rc;
+                        }
+                        P.cols.push_back(QuantileCol{nt, r1 - r0, c1 - c0, (uint32_t)wc, seg0, nseg, used,
+                                                     base[q] + (uint64_t)(r0 - c.top) * wc + (c0 - c.left), wr * wc});
+                        subs.push_back(dcdf_cube{c.start, c.end, r0, r1, c0, c1});
+                        sbase.push_back(used);
+                        used += need;
+                        cur.max_cells = std::max(cur.max_cells, cells);
+                        c0 = c1;
+                    }
+                    r0 = r1;
+                }
+                if (P.cols.size() > 0x7ffffff0ull || P.segs.size() > 0x7ffffff0ull) return DCDF_ERR_CAPACITY;
+            }
+    }
+    return flush();
 }
 
 #undef K2R_PLAN_INLINE

@@ -1,5 +1,5 @@
 // k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, spell
-// statistics, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// statistics, quantiles over time, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,7 @@
 
 using namespace k2r;
 
-// ---- what the six calls share -----------------------------------------------------------------------------------------------
+// ---- what the seven calls share ---------------------------------------------------------------------------------------------
 // Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
 // error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
 enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
@@ -40,6 +40,7 @@ static uint64_t env_cap(const char* name, uint64_t dflt) {
 static uint64_t reduce_slab_cells() { return env_cap("K2R_REDUCE_SLAB_CELLS", (uint64_t)1 << 22); }  // cells of one fallback slab
 static uint64_t space_record_cap() { return env_cap("K2R_SPACE_RECORDS", (uint64_t)6 << 20); }      // records of a batch, 40 bytes each
 static uint64_t zonal_acc_cap() { return env_cap("K2R_ZONAL_ACC_BYTES", (uint64_t)128 << 20); }     // 72 bytes per (zone, instant)
+static uint64_t quantile_slab_bytes() { return env_cap("K2R_QUANTILE_SLAB_BYTES", (uint64_t)256 << 20); }  // stored integers of one band
 // A fold kernel over n pieces on the null stream: a column of gy workgroups per piece.
 template <auto Kernel, class Fold, class... Args>
 static int launch_fold(uint32_t gy, const Fold* d_ps, size_t n, Args... args) {
@@ -354,6 +355,50 @@ extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* c
         if (rc == DCDF_OK)
             rc = launch_bulk_spell(r->d_refs.as<ChunkRef>(), R.units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr.as<uint32_t>(), ops);
         if (rc == DCDF_OK) rc = R.walk.run<k_spell_fold>(r, P.walk, g, 16, d_dst, d_scr.as<uint32_t>(), ops);
+        if (rc != DCDF_OK) return rc;
+    }
+    return R.end(W, true, kernel_ms);
+}
+// ---- quantiles over time: per cell, order statistics of the values decode returns (k2r_quantile.h) ----------------------------
+// The plan is plan_quantile_time's (k2r_plan.h): the cubes in columns, the columns in bands of a bounded slab.  A band: its
+// sub-cubes decoded as stored integers (DCDF_I64: store_typed leaves n as it is) by the three launches of decode -- elided fills,
+// the bulk kernel's units, the window walk's items --, then k_quantile_select (k2r_quantile.hip) over its columns.  The bands
+// run one after the other on the null stream over one pooled slab.
+extern "C" int dcdf_raster_quantile_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* probs, uint32_t n_probs,
+                                               int32_t method, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                                               float* kernel_ms) {
+    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, quantile_args_ok(probs, n_probs, method), ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    const PlaneLayout L(cubes, nq, n_probs, 0);
+    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    QuantilePlan P;
+    rc = plan_quantile_time(r->plan(), cubes, nq, W.base.data(), quantile_slab_bytes(), r->all_node, bulk_wanted_units(), P);
+    if (rc != DCDF_OK) return rc;
+    DevBuf d_cols, d_segs, d_slab;
+    RegionRun R;  // (units: the bulk units, cfolds: the elided fills, walk.items: the walk's items)
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
+    double* const d_dst = (double*)W.dst();
+    K2R_HIP(d_slab.alloc_pooled(P.slab_max * sizeof(int64_t)));
+    K2R_HIP(upload(d_cols, P.cols));
+    K2R_HIP(upload(d_segs, P.segs));
+    rc = upload_some(R.units, P.units);
+    if (rc == DCDF_OK) rc = upload_some(R.cfolds, P.consts);
+    if (rc == DCDF_OK) rc = upload_some(R.walk.items, P.items);
+    if (rc == DCDF_OK) rc = R.start();
+    if (rc != DCDF_OK) return rc;
+    QuantileProbs pr{};
+    for (uint32_t i = 0; i < n_probs; i++) pr.p[i] = probs[i];
+    for (const QuantileBand& b : P.bands) {
+        rc = launch_raster_fill_const(r, R.cfolds.as<ConstPiece>() + b.const0, (uint32_t)(b.const1 - b.const0), d_slab.p, DCDF_I64);
+        if (rc == DCDF_OK)
+            rc = launch_bulk_decode(r->d_refs.as<ChunkRef>(), R.units.as<BulkUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), d_slab.p, DCDF_I64);
+        if (rc == DCDF_OK && b.item1 > b.item0)
+            rc = launch_window_items_dev(r->d_refs, R.walk.items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), d_slab.p, DCDF_I64, nullptr,
+                                         nullptr, r->all_node, r->all_narrow);
+        if (rc == DCDF_OK)
+            rc = launch_quantile_select(d_cols.as<QuantileCol>() + b.col0, (uint32_t)(b.col1 - b.col0), b.max_cells, d_segs.as<QuantileSeg>(),
+                                        d_slab.as<int64_t>(), pr, n_probs, method, d_dst);
         if (rc != DCDF_OK) return rc;
     }
     return R.end(W, true, kernel_ms);

@@ -403,6 +403,20 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return EncodedRaster._spells_none(EncodedRaster.spell_ops(ops)[1], bottom - top, right - left)
         return self.raster().spells(lower, upper, ops, start, stop, window=(top, bottom, left, right))
 
+    def quantile_time(self, probs, start=0, stop=None, top=0, bottom=None, left=0, right=None, method="linear"):
+        """Per-cell quantiles over the instants [start, stop) of the window [top, bottom) x [left, right): ndarray [n_probs, rows,
+        cols] float64 ([rows, cols] for a scalar `probs`) over the values window() returns widened to float64, NaN cells skipped
+        -- numpy.nanquantile(window, probs, axis=0) for method "linear"; "lower", "higher" and "nearest" pick a value of the series
+        itself.  Exact; NaN where a cell has no value.  Through raster().quantile_time: the cube is decoded band by band into a
+        bounded device buffer and only the planes are written (dcdf_raster_quantile_time_batch)."""
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            from .raster import EncodedRaster
+            p, _, scalar = EncodedRaster._probs(probs, method)
+            out = np.full((p.size, bottom - top, right - left), np.nan)
+            return out[0] if scalar else out
+        return self.raster().quantile_time(probs, start, stop, window=(top, bottom, left, right), method=method)
+
     def reduce_space(self, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
         """Per-instant statistics over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
         ([rows, cols] of the window, boolean or uint8) is non-zero when a mask is given: {name: ndarray [stop - start] float64} for

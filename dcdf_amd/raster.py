@@ -265,6 +265,54 @@ class EncodedRaster:
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
     @staticmethod
+    def _probs(probs, method):
+        """probs / method of quantile_time as (float64 array [n], method code, probs was a scalar): 1 .. 16 probabilities in [0, 1],
+        method one of "lower", "higher", "nearest", "linear" (or its DCDF_QUANTILE_* code)."""
+        p = np.asarray(probs, dtype=np.float64)
+        scalar = p.ndim == 0
+        p = np.ascontiguousarray(p.reshape(-1))
+        if not 1 <= p.size <= L.QUANTILE_MAX_PROBS:
+            raise ValueError("quantile_time: %d probabilities, not 1 .. %d" % (p.size, L.QUANTILE_MAX_PROBS))
+        if not ((p >= 0) & (p <= 1)).all():  # (a NaN fails both)
+            raise ValueError("quantile_time: probabilities must lie in [0, 1]")
+        if isinstance(method, str):
+            if method not in L.QUANTILE_METHODS:
+                raise ValueError("quantile_time: unknown method %r (one of %s)" % (method, ", ".join(L.QUANTILE_METHODS)))
+            method = L.QUANTILE_METHODS[method]
+        if int(method) not in L.QUANTILE_METHODS.values():
+            raise ValueError("quantile_time: unknown method %r" % (method,))
+        return p, int(method), scalar
+
+    def quantile_time_flat(self, cubes, probs, method="linear", out_device_ptr=None, out_offset=None):
+        """Per-cell quantiles over time of dataset-level cubes [n, 6] through dcdf_raster_quantile_time_batch: cube q yields one
+        [rows, cols] float64 plane per probability of `probs` (1 .. 16 values in [0, 1], shared by all cubes), in their order, over
+        the values decode_flat returns for it in the leaves' own dtype, NaN skipped: with v the n sorted values of a cell and
+        h = (n - 1) * p, "lower" is v[floor(h)], "higher" v[ceil(h)], "nearest" the nearer of the two (the even index at a tie) and
+        "linear" the interpolation numpy.nanquantile makes; NaN where n == 0.  The result is exact: the order statistics are selected
+        on the device.  Host form: returns (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's planes are
+        flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms,
+        stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided leaves."""
+        p, code, _ = self._probs(probs, method)
+        q = self._cubes(cubes)
+        return self._region_call("quantile_time", q, lambda: self._planes(q, p.size), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_void_p(p.ctypes.data), C.c_uint32(p.size), C.c_int32(code), out, mem, off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def quantile_time(self, probs, start=0, stop=None, window=None, method="linear"):
+        """ndarray [n_probs, rows, cols] float64 ([rows, cols] for a scalar `probs`): the quantiles of every cell's series over the
+        instants [start, stop) of the whole raster, or of `window` = (top, bottom, left, right) (quantile_time_flat's rule).  Without
+        instants or cells: NaN planes of that shape."""
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
+        p, code, scalar = self._probs(probs, method)
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            out = np.full((p.size, rows, cols), np.nan)
+        else:
+            flat, _, _, _ = self.quantile_time_flat([[start, stop, top, bottom, left, right]], p, code)
+            out = flat[:p.size * rows * cols].reshape(p.size, rows, cols)
+        return out[0] if scalar else out
+
+    @staticmethod
     def _device_arrays(q, arrays, what, noun):
         """One array per cube (masks, labels) already on the device, given as (device pointer, offsets uint64[n]): (pointer, offsets,
         memory kind, what must stay alive over the call); None when `arrays` is not of that form."""

@@ -51,4 +51,8 @@ blocks = (np.arange(256)[:, None] // 64 * 4 + np.arange(256)[None, :] // 64).ast
 zones = R.zonal(("mean", "count"), blocks, 8, 24)
 assert list(zones) == ["count", "mean"] and zones["mean"].shape == (16, 16) and (zones["count"] == 64 * 64).all()
 assert all(zones["mean"][z, t] == math.fsum(a[8 + t][blocks == z].tolist()) / 4096.0 for z in range(16) for t in range(16))
+q = R.quantile_time([0.5, 0.9], 8, 24)  # float64 [2, 256, 256]: the median and the 90th percentile of every cell's 16 values, exact
+srt, h = np.sort(a[8:24], axis=0).astype(np.float64), 15 * 0.9
+assert (q[0] == (srt[7] + srt[8]) / 2).all() and (q[1] == srt[int(h)] + (srt[int(h) + 1] - srt[int(h)]) * (h - int(h))).all()
+assert (R.quantile_time(0.9, 8, 24, method="higher") == np.quantile(a[8:24], 0.9, axis=0, method="higher")).all()
 print("readme example ok")

@@ -297,6 +297,34 @@ enum { DCDF_SPELL_COUNT = 1, DCDF_SPELL_LONGEST = 2, DCDF_SPELL_LONGEST_START = 
 #define DCDF_SPELL_NONE 0xffffffffu
 int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
                              uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Quantiles over time: per cell (row, col) of each cube, order statistics of its series -- the median, the 5th or 95th percentile
+ * -- exact, selected on the device from a bounded slab of decoded values; the cube never reaches the host.  The call takes plain
+ * and tiled rasters, elided leaves included.  Cubes, out_mem, out_offset, stats and kernel_ms are exactly
+ * dcdf_raster_reduce_time_batch's: reversed bounds of a cube are swapped, stats are the numbers dcdf_raster_decode_batch reports
+ * for the same cubes, a cube of zero volume writes nothing, nq == 0 is fine, stats and kernel_ms may be NULL.
+ *   probs    n_probs doubles in HOST memory, shared by all cubes; 1 <= n_probs <= 16, each in [0, 1].
+ *   x[t]     of a cell: reduce_time's x[t], the stored integer widened with the encoding and fractional bits of the leaf that holds
+ *            the cell at that instant.  v[0 .. n) = the non-NaN x[t] in ascending order, n their count; -0.0 sorts before +0.0.
+ *   n == 0   gives NaN.  Else h = (double)(n - 1) * p (one IEEE multiplication), j = floor(h), g = h - j, j1 = min(j + 1, n - 1):
+ *   DCDF_QUANTILE_LOWER    v[j]
+ *   DCDF_QUANTILE_HIGHER   v[j] when g == 0, else v[j1]
+ *   DCDF_QUANTILE_NEAREST  v[j] when g < 0.5, v[j1] when g > 0.5; at g == 0.5 whichever of j, j1 is even
+ *   DCDF_QUANTILE_LINEAR   v[j] when g == 0, else v[j] + (v[j1] - v[j]) * g: three separate IEEE double operations, no fused
+ *                          multiply-add
+ * p = 0 and p = 1 are DCDF_REDUCE_MIN and DCDF_REDUCE_MAX bit for bit, apart from the sign of a zero.  Cube q writes n_probs planes
+ * in the order of probs, each dense [rows][cols] float64, from out + out_offset[q] (elements), host or device memory; nothing
+ * outside a cube's planes is written.  The result is an order statistic of the cell's own values: it depends on no cut of the work.
+ * DCDF_ERR_BAD_ARG: n_probs of 0 or above 16; a NaN or a value outside [0, 1] among probs; an unknown method; NULL r, cubes, probs,
+ * out or out_offset; an unknown out_mem.  DCDF_ERR_BOUNDS: a cube outside the raster.  DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+enum { DCDF_QUANTILE_LOWER = 0, DCDF_QUANTILE_HIGHER = 1, DCDF_QUANTILE_NEAREST = 2, DCDF_QUANTILE_LINEAR = 3 };
+int dcdf_raster_quantile_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, const double* probs, uint32_t n_probs,
+                                    int32_t method, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* The selection dcdf_raster_quantile_time_batch runs per cell, as the device runs it, on the host: x is [instants][cells] doubles
+ * (NaN = no value), out [n_probs][cells]; passes (may be NULL) [cells]: how many times the cell's series was read after the first.
+ * Pure host function; no GPU, no HIP call (so it is testable on a CPU-only machine).  DCDF_ERR_BAD_ARG: a NULL pointer, the
+ * probs / method errors above. */
+int dcdf_quantile_select_host(const double* x, uint32_t instants, uint64_t cells, const double* probs, uint32_t n_probs, int32_t method,
+                              double* out, uint32_t* passes);
 /* Reduce over space: per instant of each cube, statistics over its SELECTED cells -- a series over an area.  The call takes
  * plain and tiled rasters.  Cube q is [start, end) x [top, bottom) x [left, right) (reversed bounds are swapped); its cell (r, c)
  * is selected when mask == NULL, or when the byte mask[mask_offset[q] + (r - top) * cols + (c - left)] is non-zero: a dense
