@@ -252,6 +252,20 @@ struct SegmentPlan : ReducePlan<Unit, Fold> {
     std::vector<SegRange> ranges;
     using ReducePlan<Unit, Fold>::ReducePlan;
 };
+// The heads of a piece's records (k2r_cell_fold.h): piece p of a cube of wr x wc cells whose first output / scratch plane starts
+// at base / sbase, and unit u of p.
+K2R_PLAN_INLINE CellFold cell_fold(const PlanRaster& g, const Piece& p, uint64_t wr, uint64_t wc, uint64_t base, uint64_t sbase) {
+    return CellFold{p.nt(), p.rows(), p.cols(), (uint32_t)wc, p.dt == 0 /* the piece holds the cube's first instant */, p.enc, p.fbits,
+                    p.kind == PIECE_CONST, (uint64_t)p.leaf * g.cs + p.l.start, base + p.in_win, sbase + p.in_win, wr * wc};
+}
+template <class Unit>
+K2R_PLAN_INLINE void cell_unit(Unit& u, const Piece& p, const CellFold& f) {
+    u.sr = f.sr;
+    u.init = f.init;
+    u.o_off = f.o_off + unit_in_piece(u, p, f.sr);
+    u.s_off = f.s_off + unit_in_piece(u, p, f.sr);
+    u.psz = f.psz;
+}
 template <class Unit, class Fold>
 struct SegmentBuckets {
     struct Segment {
@@ -342,16 +356,8 @@ inline int plan_reduce_time(const PlanRaster& g, const dcdf_cube* cubes, size_t 
         if (cube_cells(c) == 0) continue;
         P.means.push_back(MeanPiece{base[q], sbase[q], wr * wc});
         plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
-            const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
-            const FoldPiece f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
-                              (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc};
-            B.put(p, f, [&](ReduceUnit& u) {
-                u.sr = (uint32_t)wc;
-                u.init = init;
-                u.o_off = f.o_off + unit_in_piece(u, p, wc);
-                u.s_off = f.s_off + unit_in_piece(u, p, wc);
-                u.psz = wr * wc;
-            });
+            const FoldPiece f = cell_fold(g, p, wr, wc, base[q], sbase[q]);
+            B.put(p, f, [&](ReduceUnit& u) { cell_unit(u, p, f); });
         });
     }
     return B.assemble(P, node_wise, [](FoldPiece&, uint32_t) {});
@@ -609,21 +615,15 @@ inline int plan_spells(const PlanRaster& g, const dcdf_cube* cubes, const double
                 if (!value_bounds(p.enc, p.fbits, lower[q], upper[q], &cache[at].vr)) bad = true;
             }
             const ValueRange& vr = cache[at].vr;
-            const uint32_t init = p.dt == 0;  // the piece holds the cube's first instant
             const SpellRange64 r64 = spell_range64(vr);
-            const SpellFold f{p.nt(), p.rows(), p.cols(), (uint32_t)wc, init, p.enc, p.fbits, p.kind == PIECE_CONST,
-                              (uint64_t)p.leaf * g.cs + p.l.start, base[q] + p.in_win, sbase[q] + p.in_win, wr * wc, p.dt, r64.flags, r64.lo, r64.hi};
+            const SpellFold f{cell_fold(g, p, wr, wc, base[q], sbase[q]), p.dt, r64.flags, r64.lo, r64.hi};
             const SpellRange32 r32 = p.kind == PIECE_BULK ? spell_range32(vr) : SpellRange32{};  // the units' alone
             B.put(p, f, [&](SpellUnit& u) {
-                u.sr = (uint32_t)wc;
-                u.init = init;
+                cell_unit(u, p, f);
                 u.dt = p.dt;
                 u.lo = r32.lo;
                 u.hi = r32.hi;
                 u.flags = r32.flags;
-                u.o_off = f.o_off + unit_in_piece(u, p, wc);
-                u.s_off = f.s_off + unit_in_piece(u, p, wc);
-                u.psz = wr * wc;
             });
         });
         if (bad) return DCDF_ERR_BAD_ARG;

@@ -188,52 +188,116 @@ extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* c
     if (rc != DCDF_OK) return rc;
     return batch_epilogue(W, ev, P.items.empty(), kernel_ms);
 }
-// ---- reduce over time: per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h) --------------------
-// The plan, and what keeps the sum's order, are plan_reduce_time's (k2r_plan.h): the segments are launched one after the other in
-// ascending order on the null stream.  The state planes are the output planes themselves (cube q's requested planes in ascending
-// bit order); SUM / COUNT kept for MEAN alone live in scratch planes.
+// ---- per-cell folds over time: reduce_time and spells (k2r_cell_fold.h) -------------------------------------------------------
+// The plan, and what keeps a cell's instants in order, are plan_reduce_time's and plan_spells' (k2r_plan.h): the segments are
+// launched one after the other in ascending order on the null stream, and every piece continues the state its cells' planes
+// hold.  The state planes are the output planes themselves (cube q's requested planes in ascending bit order); states kept for
+// another's sake alone live in pooled scratch planes (state_plane).
 //
 // Pieces on chunks the bulk kernel does not take are decoded by the window walk as stored integers (DCDF_I64: store_typed
-// leaves n as it is) into a slab of a bounded number of cells, then folded by k_reduce_fold, which applies the leaf's own
-// encoding (reduce_widen: the conversions of store_typed, so the value is the typed fill_window's) -- one walk launch per slab
-// whatever mix of encodings its chunks have.  Elided pieces are folded by the same kernel straight from dcdf_raster::d_vals.
+// leaves n as it is) into a slab of a bounded number of cells -- one walk launch per slab whatever mix of encodings its chunks
+// have --, then folded by k_cell_fold: a thread per cell, its instants in order.  Elided pieces are folded by the same kernel
+// straight from dcdf_raster::d_vals (one value per instant).  Op -- a per-cell statistic -- has
+//   Piece, T                 the fold record, a CellFold (k2r_cell_fold.h) and what else the statistic needs; the planes' element
+//   Op(P, dst, scr, ops)     per piece: the plane pointers
+//   init() / load(at)        the cell's initial state / its state from the planes (only when the piece continues a cube)
+//   step(P, t, n)            the stored integer n of the piece's instant t into the state
+//   store(at)                the state into the planes
+template <class Op>
 __global__ void __launch_bounds__(256)
-k_reduce_fold(const FoldPiece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, double* dst,
-              double* scr, uint32_t ops) {
-    const uint32_t live = reduce_live(ops);
+k_cell_fold(const typename Op::Piece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
+            typename Op::T* dst, typename Op::T* scr, uint32_t ops) {
     for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-        const FoldPiece P = ps[p];
+        const typename Op::Piece P = ps[p];
         const uint64_t cells = (uint64_t)P.rows * P.cols;
-        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        Op op(P, dst, scr, ops);
         for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
             const uint64_t at = e / P.cols * P.sr + e % P.cols;
-            double s = 0.0, c = 0.0, lo = __builtin_nan(""), hi = __builtin_nan("");
-            if (!P.init) {
-                if (live & RA_MIN) lo = p_min[at];
-                if (live & RA_MAX) hi = p_max[at];
-                if (live & RA_SUM) s = p_sum[at];
-                if (live & RA_COUNT) c = p_cnt[at];
-            }
-            for (uint32_t t = 0; t < P.nt; t++) {
-                const double x = reduce_widen(P.enc, P.fbits, P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e]);
-                if (x == x) {
-                    s = s + x;
-                    c = c + 1.0;
-                    lo = fmin(lo, x);
-                    hi = fmax(hi, x);
-                }
-            }
-            if (live & RA_MIN) p_min[at] = lo;
-            if (live & RA_MAX) p_max[at] = hi;
-            if (live & RA_SUM) p_sum[at] = s;
-            if (live & RA_COUNT) p_cnt[at] = c;
+            op.init();
+            if (!P.init) op.load(at);
+            for (uint32_t t = 0; t < P.nt; t++) op.step(P, t, P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e]);
+            op.store(at);
         }
     }
 }
-// the finishing kernel: MEAN = SUM / COUNT, NaN where nothing was counted
+// reduce_time (k2r_reduce.h): the leaf's own encoding applied to the stored integer (reduce_widen: the conversions of
+// store_typed, so the value is the typed fill_window's), then the four accumulators as doubles
+struct ReduceCell {
+    typedef FoldPiece Piece;
+    typedef double T;
+    const uint32_t live;
+    double *const p_min, *const p_max, *const p_sum, *const p_cnt;
+    double s, c, lo, hi;
+    __device__ ReduceCell(const FoldPiece& P, double* dst, double* scr, uint32_t ops)
+        : live(reduce_live(ops)),
+          p_min(reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_max(reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_sum(reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_cnt(reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz)) {}
+    __device__ void init() {
+        s = c = 0.0;
+        lo = hi = __builtin_nan("");
+    }
+    __device__ void load(uint64_t at) {
+        if (live & RA_MIN) lo = p_min[at];
+        if (live & RA_MAX) hi = p_max[at];
+        if (live & RA_SUM) s = p_sum[at];
+        if (live & RA_COUNT) c = p_cnt[at];
+    }
+    __device__ void step(const FoldPiece& P, uint32_t, int64_t n) {
+        const double x = reduce_widen(P.enc, P.fbits, n);
+        if (x == x) {
+            s = s + x;
+            c = c + 1.0;
+            lo = fmin(lo, x);
+            hi = fmax(hi, x);
+        }
+    }
+    __device__ void store(uint64_t at) const {
+        if (live & RA_MIN) p_min[at] = lo;
+        if (live & RA_MAX) p_max[at] = hi;
+        if (live & RA_SUM) p_sum[at] = s;
+        if (live & RA_COUNT) p_cnt[at] = c;
+    }
+};
+// spells (k2r_spell.h): spell_step, the hit test on the stored integer itself
+struct SpellCell {
+    typedef SpellFold Piece;
+    typedef uint32_t T;
+    const uint32_t live;
+    uint32_t *const p_cnt, *const p_lng, *const p_lst, *const p_fst, *const p_las, *const p_cur;
+    SpellState s;
+    __device__ SpellCell(const SpellFold& P, uint32_t* dst, uint32_t* scr, uint32_t ops)
+        : live(spell_live(ops)),
+          p_cnt(spell_plane(SP_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_lng(spell_plane(SP_LONGEST, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_lst(spell_plane(SP_LSTART, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_fst(spell_plane(SP_FIRST, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_las(spell_plane(SP_LAST, dst, scr, ops, P.o_off, P.s_off, P.psz)),
+          p_cur(spell_plane(SP_CUR, dst, scr, ops, P.o_off, P.s_off, P.psz)) {}
+    __device__ void init() { s = spell_init(); }
+    __device__ void load(uint64_t at) {
+        if (live & SP_COUNT) s.count = p_cnt[at];
+        if (live & SP_LONGEST) s.longest = p_lng[at];
+        if (live & SP_LSTART) s.lstart = p_lst[at];
+        if (live & SP_FIRST) s.first = p_fst[at];
+        if (live & SP_LAST) s.last = p_las[at];
+        if (live & SP_CUR) s.cur = p_cur[at];
+    }
+    __device__ void step(const SpellFold& P, uint32_t t, int64_t v) {
+        if (P.enc == ENC_I32) v = (int64_t)(int32_t)v;  // (store_typed's conversion)
+        spell_step(s, P.dt + t, spell_hit64(v, P.lo, P.hi, P.flags));
+    }
+    __device__ void store(uint64_t at) const {
+        if (live & SP_COUNT) p_cnt[at] = s.count;
+        if (live & SP_LONGEST) p_lng[at] = s.longest;
+        if (live & SP_LSTART) p_lst[at] = s.lstart;
+        if (live & SP_FIRST) p_fst[at] = s.first;
+        if (live & SP_LAST) p_las[at] = s.last;
+        if (live & SP_CUR) p_cur[at] = s.cur;
+    }
+};
+// the finishing kernel of reduce_time: MEAN = SUM / COUNT, NaN where nothing was counted
 __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
     for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
         const MeanPiece P = ps[p];
@@ -246,118 +310,82 @@ __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict
         }
     }
 }
-extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
-                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
-    if (rc != DCDF_OK || nq == 0) return rc;
-    const uint32_t live = reduce_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
-    const PlaneLayout L(cubes, nq, n_out, n_scr);
-    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
-    TimePlan P(reduce_slab_cells());
-    rc = plan_reduce_time(r->plan(), cubes, nq, W.base.data(), L.sbase.data(), r->all_node, P);
-    if (rc != DCDF_OK) return rc;
-    DevBuf d_means, d_scr;
-    RegionRun R;
-    rc = R.begin(W, stats, P.stats);
-    if (rc != DCDF_OK || R.nothing) return rc;
-    double* const d_dst = (double*)W.dst();
-    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(double)));
-    rc = R.upload(P);
-    if (rc != DCDF_OK) return rc;
-    if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
-    rc = R.start();
-    if (rc != DCDF_OK) return rc;
-    for (const SegRange& g : P.ranges) {
-        rc = R.fold_consts<k_reduce_fold, FoldPiece>(r, g, 16, d_dst, d_scr.as<double>(), ops);
-        if (rc == DCDF_OK)
-            rc = launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), R.units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                    d_dst, d_scr.as<double>(), ops);
-        if (rc == DCDF_OK) rc = R.walk.run<k_reduce_fold>(r, P.walk, g, 16, d_dst, d_scr.as<double>(), ops);
-        if (rc != DCDF_OK) return rc;
-    }
-    if (ops & ROP_MEAN) {
-        uint64_t big = 0;
-        for (const MeanPiece& m : P.means) big = std::max(big, m.psz);
-        hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
-                           dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr.as<double>(), ops);
-        K2R_HIP(hipGetLastError());
-    }
-    return R.end(W, true, kernel_ms);
-}
-// ---- spell statistics: per cell, the hits of a value range over time and their runs (k2r_spell.h) -----------------------------
-// reduce_time's shape: plan_spells (k2r_plan.h) gives the segments in ascending order, launched one after the other on the null
-// stream; every piece continues the run state its cells' planes hold.  The state planes are the output planes themselves (cube
-// q's requested planes in ascending bit order); cur, and LONGEST kept for LONGEST_START alone, live in pooled scratch planes.
-//
-// A thread per cell of a fallback piece (the window walk's slab of stored integers) or of an elided piece (one value per instant
-// from dcdf_raster::d_vals): its instants in order through spell_step, the hit test on the stored integer itself.
-__global__ void __launch_bounds__(256)
-k_spell_fold(const SpellFold* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals, uint32_t* dst,
-             uint32_t* scr, uint32_t ops) {
-    const uint32_t live = spell_live(ops);
-    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-        const SpellFold P = ps[p];
-        const uint64_t cells = (uint64_t)P.rows * P.cols;
-        uint32_t* const p_cnt = spell_plane(SP_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        uint32_t* const p_lng = spell_plane(SP_LONGEST, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        uint32_t* const p_lst = spell_plane(SP_LSTART, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        uint32_t* const p_fst = spell_plane(SP_FIRST, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        uint32_t* const p_las = spell_plane(SP_LAST, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        uint32_t* const p_cur = spell_plane(SP_CUR, dst, scr, ops, P.o_off, P.s_off, P.psz);
-        for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
-            const uint64_t at = e / P.cols * P.sr + e % P.cols;
-            SpellState s = spell_init();
-            if (!P.init) {
-                if (live & SP_COUNT) s.count = p_cnt[at];
-                if (live & SP_LONGEST) s.longest = p_lng[at];
-                if (live & SP_LSTART) s.lstart = p_lst[at];
-                if (live & SP_FIRST) s.first = p_fst[at];
-                if (live & SP_LAST) s.last = p_las[at];
-                if (live & SP_CUR) s.cur = p_cur[at];
-            }
-            for (uint32_t t = 0; t < P.nt; t++) {
-                int64_t v = P.elided ? vals[P.src + t] : slab[P.src + (uint64_t)t * cells + e];
-                if (P.enc == ENC_I32) v = (int64_t)(int32_t)v;  // (store_typed's conversion)
-                spell_step(s, P.dt + t, spell_hit64(v, P.lo, P.hi, P.flags));
-            }
-            if (live & SP_COUNT) p_cnt[at] = s.count;
-            if (live & SP_LONGEST) p_lng[at] = s.longest;
-            if (live & SP_LSTART) p_lst[at] = s.lstart;
-            if (live & SP_FIRST) p_fst[at] = s.first;
-            if (live & SP_LAST) p_las[at] = s.last;
-            if (live & SP_CUR) p_cur[at] = s.cur;
-        }
-    }
-}
-extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
-                                        uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    bool own = ops != 0 && ops <= SP_ALL && (nq == 0 || (lower && upper));
-    for (size_t q = 0; own && q < nq && q <= 0x7fffffffu; q++) own = lower[q] == lower[q] && upper[q] == upper[q];  // a NaN bound
-    int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
-    if (rc != DCDF_OK || nq == 0) return rc;
-    const uint32_t live = spell_live(ops), n_out = popc32(ops), n_scr = popc32(live & ~ops);
-    const PlaneLayout L(cubes, nq, n_out, n_scr);
-    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(uint32_t), out_mem == DCDF_MEM_DEVICE);
-    SpellPlan P(reduce_slab_cells());
-    rc = plan_spells(r->plan(), cubes, lower, upper, nq, W.base.data(), L.sbase.data(), r->all_node, P);
+// What follows region_begin in both calls.  live: the states the call carries, `ops` and those kept for another's sake.
+// make_plan(P, base, sbase) fills the Plan (a SegmentPlan); staged(P) uploads what else the call's launches read, before the
+// events; bulk(units, g, d_dst, d_scr) launches the bulk kernel over range g's units; finish(P, d_dst, d_scr) launches what
+// follows the last segment.  Per segment: the elided folds, the bulk units, the walk's slabs -- a segment's pieces share no cell.
+template <class Op, class Plan, class MakePlan, class Bulk, class Staged, class Finish>
+static int cell_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t live, typename Op::T* out, int out_mem,
+                           const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms, MakePlan&& make_plan, Bulk&& bulk, Staged&& staged,
+                           Finish&& finish) {
+    typedef typename Op::T T;
+    const PlaneLayout L(cubes, nq, popc32(ops), popc32(live & ~ops));
+    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(T), out_mem == DCDF_MEM_DEVICE);
+    Plan P(reduce_slab_cells());
+    int rc = make_plan(P, W.base.data(), L.sbase.data());
     if (rc != DCDF_OK) return rc;
     DevBuf d_scr;
     RegionRun R;
     rc = R.begin(W, stats, P.stats);
     if (rc != DCDF_OK || R.nothing) return rc;
-    uint32_t* const d_dst = (uint32_t*)W.dst();
-    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(uint32_t)));
+    T* const d_dst = (T*)W.dst();
+    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(T)));
     rc = R.upload(P);
+    if (rc == DCDF_OK) rc = staged(P);
     if (rc == DCDF_OK) rc = R.start();
     if (rc != DCDF_OK) return rc;
     for (const SegRange& g : P.ranges) {
-        rc = R.fold_consts<k_spell_fold, SpellFold>(r, g, 16, d_dst, d_scr.as<uint32_t>(), ops);
-        if (rc == DCDF_OK)
-            rc = launch_bulk_spell(r->d_refs.as<ChunkRef>(), R.units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr.as<uint32_t>(), ops);
-        if (rc == DCDF_OK) rc = R.walk.run<k_spell_fold>(r, P.walk, g, 16, d_dst, d_scr.as<uint32_t>(), ops);
+        rc = R.fold_consts<k_cell_fold<Op>, typename Op::Piece>(r, g, 16, d_dst, d_scr.as<T>(), ops);
+        if (rc == DCDF_OK) rc = bulk(R.units, g, d_dst, d_scr.as<T>());
+        if (rc == DCDF_OK) rc = R.walk.run<k_cell_fold<Op>>(r, P.walk, g, 16, d_dst, d_scr.as<T>(), ops);
         if (rc != DCDF_OK) return rc;
     }
-    return R.end(W, true, kernel_ms);
+    rc = finish(P, d_dst, d_scr.as<T>());
+    return rc == DCDF_OK ? R.end(W, true, kernel_ms) : rc;
+}
+// per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h); SUM / COUNT kept for MEAN alone are the
+// scratch planes
+extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
+                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    DevBuf d_means;
+    return cell_fold_batch<ReduceCell, TimePlan>(
+        r, cubes, nq, ops, reduce_live(ops), out, out_mem, out_offset, stats, kernel_ms,
+        [&](TimePlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_reduce_time(r->plan(), cubes, nq, base, sbase, r->all_node, P); },
+        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
+            return launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                      d_dst, d_scr, ops);
+        },
+        [&](const TimePlan& P) {
+            if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
+            return (int)DCDF_OK;
+        },
+        [&](const TimePlan& P, double* d_dst, double* d_scr) {
+            if (!(ops & ROP_MEAN)) return (int)DCDF_OK;
+            uint64_t big = 0;
+            for (const MeanPiece& m : P.means) big = std::max(big, m.psz);
+            hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
+                               dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr, ops);
+            K2R_HIP(hipGetLastError());
+            return (int)DCDF_OK;
+        });
+}
+// per cell, the hits of a value range over time and their runs (k2r_spell.h); cur, and LONGEST kept for LONGEST_START alone, are
+// the scratch planes
+extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
+                                        uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    bool own = ops != 0 && ops <= SP_ALL && (nq == 0 || (lower && upper));
+    for (size_t q = 0; own && q < nq && q <= 0x7fffffffu; q++) own = lower[q] == lower[q] && upper[q] == upper[q];  // a NaN bound
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return cell_fold_batch<SpellCell, SpellPlan>(
+        r, cubes, nq, ops, spell_live(ops), out, out_mem, out_offset, stats, kernel_ms,
+        [&](SpellPlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_spells(r->plan(), cubes, lower, upper, nq, base, sbase, r->all_node, P); },
+        [&](const DevBuf& units, const SegRange& g, uint32_t* d_dst, uint32_t* d_scr) {
+            return launch_bulk_spell(r->d_refs.as<ChunkRef>(), units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr, ops);
+        },
+        [](const SpellPlan&) { return (int)DCDF_OK; }, [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; });
 }
 // ---- quantiles over time: per cell, order statistics of the values decode returns (k2r_quantile.h) ----------------------------
 // The plan is plan_quantile_time's (k2r_plan.h): the cubes in columns, the columns in bands of a bounded slab.  A band: its

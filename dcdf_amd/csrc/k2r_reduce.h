@@ -6,7 +6,7 @@
 // s = 0.0, s = s + x[t] in instant order; COUNT = the non-NaN x[t]; MEAN = SUM / COUNT.  The chain's order is what every piece
 // of the plan keeps: a cell's instants are only ever added one after the other to the one running sum of its state plane.
 #pragma once
-#include "k2r_decode.h"
+#include "k2r_cell_fold.h"
 
 namespace k2r {
 
@@ -14,12 +14,9 @@ namespace k2r {
 constexpr uint32_t RA_MIN = 1u, RA_MAX = 2u, RA_SUM = 4u, RA_COUNT = 8u, RA_ALL = 15u, ROP_MEAN = 16u;
 K2R_HD uint32_t reduce_live(uint32_t ops) { return (ops & RA_ALL) | ((ops & ROP_MEAN) ? (RA_SUM | RA_COUNT) : 0u); }
 
-// Where accumulator A of a cube lives: in its own output plane when the caller asked for it (planes in ascending bit order),
-// else -- SUM or COUNT kept for MEAN alone -- in a scratch plane.  o_off / s_off: element of a cell in the cube's first output
-// / scratch plane; psz: cells of a plane.
+// Where accumulator A of a cube lives (state_plane, k2r_cell_fold.h): SUM or COUNT kept for MEAN alone are the scratch planes.
 K2R_HD double* reduce_plane(uint32_t A, double* dst, double* scr, uint32_t ops, uint64_t o_off, uint64_t s_off, uint64_t psz) {
-    if (ops & A) return dst + o_off + (uint64_t)popc32(ops & (A - 1u)) * psz;
-    return scr + s_off + (uint64_t)popc32(reduce_live(ops) & ~ops & (A - 1u)) * psz;
+    return state_plane(A, reduce_live(ops), dst, scr, ops, o_off, s_off, psz);
 }
 
 // x[t]: store_typed (k2r_decode.h) of the stored integer n with the leaf's encoding, widened to double
@@ -32,26 +29,16 @@ K2R_HD double reduce_widen(int32_t enc, uint32_t fbits, int64_t n) {
     }
 }
 
-// One workgroup's work in k_bulk_reduce: BulkUnit (k2r_bulk.h) with the place of its cells in the state planes instead of the
-// output strides.  init: the piece starts at its cube's first instant -- the planes are initialised, not loaded.
-struct ReduceUnit {
-    uint32_t chunk;  // index into the ChunkRef table
-    uint32_t t0, t1;
-    uint16_t rr, rc;
-    uint16_t top, bottom, left, right;
-    uint32_t sr;     // row stride of the planes in elements (the cube's columns)
-    uint32_t init;
+// One workgroup's work in k_bulk_reduce: CellUnit (k2r_cell_fold.h), then the place of its cells in the state planes.
+struct ReduceUnit : CellUnit {
     uint64_t o_off, s_off, psz;  // of cell (top, left): reduce_plane
 };
-// A fallback or elided piece folded by k_reduce_fold, a thread per cell looping over the instants in order.  src: element of
-// (first instant, first row, first column) in the slab of stored integers, dense [nt][rows][cols]; for an elided piece the
-// index of its first instant in dcdf_raster::d_vals (one value per instant).
-struct FoldPiece {
-    uint32_t nt, rows, cols, sr, init;
-    int32_t enc;
-    uint32_t fbits, elided;
-    uint64_t src, o_off, s_off, psz;
-};
+// A fallback or elided piece: the shared head is all reduce_time needs.
+using FoldPiece = CellFold;
+K2R_PIN_BEGIN
+static_assert(sizeof(ReduceUnit) == 56, "ReduceUnit");
+K2R_PIN(ReduceUnit, init, 28) K2R_PIN(ReduceUnit, o_off, 32) K2R_PIN(ReduceUnit, s_off, 40) K2R_PIN(ReduceUnit, psz, 48)
+K2R_PIN_END
 // MEAN of one cube
 struct MeanPiece {
     uint64_t o_off, s_off, psz;

@@ -9,7 +9,7 @@
 // sequential fold with a state of six integers (spell_step); a piece of the plan loads the state its predecessor stored, so the
 // result depends on no cut of a cell's instants.
 #pragma once
-#include "k2r_decode.h"
+#include "k2r_cell_fold.h"
 
 namespace k2r {
 
@@ -29,12 +29,10 @@ K2R_HD uint32_t spell_groups(uint32_t ops) {
     return ((ops & SP_COUNT) ? SG_COUNT : 0u) | ((ops & (SP_LONGEST | SP_LSTART)) ? SG_RUNS : 0u) | ((ops & (SP_FIRST | SP_LAST)) ? SG_ENDS : 0u);
 }
 
-// Where state A of a cube lives (reduce_plane's rule, k2r_reduce.h): in its own output plane when the caller asked for it (planes
-// in ascending bit order), else -- cur, and LONGEST kept for LONGEST_START alone -- in a scratch plane.  o_off / s_off: element
-// of a cell in the cube's first output / scratch plane; psz: cells of a plane.
+// Where state A of a cube lives (state_plane, k2r_cell_fold.h): cur, and LONGEST kept for LONGEST_START alone, are the scratch
+// planes.
 K2R_HD uint32_t* spell_plane(uint32_t A, uint32_t* dst, uint32_t* scr, uint32_t ops, uint64_t o_off, uint64_t s_off, uint64_t psz) {
-    if (ops & A) return dst + o_off + (uint64_t)popc32(ops & (A - 1u)) * psz;
-    return scr + s_off + (uint64_t)popc32(spell_live(ops) & ~ops & (A - 1u)) * psz;
+    return state_plane(A, spell_live(ops), dst, scr, ops, o_off, s_off, psz);
 }
 
 // ---- the fold ----------------------------------------------------------------------------------------------------------------
@@ -85,30 +83,25 @@ K2R_HD bool spell_hit64(int64_t n, int64_t lo, int64_t hi, uint32_t flags) {
 }
 
 // ---- the plan's records ------------------------------------------------------------------------------------------------------
-// One workgroup's work in k_bulk_spell: BulkUnit's first 24 bytes (k2r_bulk.h), then the place of its cells in the state planes.
-// init: the piece starts at its cube's first instant -- the state is initialised, not loaded.  dt: the index of t0 counted from
-// the cube's first instant.
-struct SpellUnit {
-    uint32_t chunk;  // index into the ChunkRef table
-    uint32_t t0, t1;
-    uint16_t rr, rc;
-    uint16_t top, bottom, left, right;
-    uint32_t sr;  // row stride of the planes in elements (the cube's columns)
-    uint32_t init;
+// One workgroup's work in k_bulk_spell: CellUnit (k2r_cell_fold.h), the leaf's range, then the place of its cells in the state
+// planes.  dt: the index of t0 counted from the cube's first instant.
+struct SpellUnit : CellUnit {
     uint32_t dt;
     int32_t lo, hi;  // spell_range32 of the leaf
     uint32_t flags;
     uint64_t o_off, s_off, psz;  // of cell (top, left): spell_plane
 };
-// A fallback or elided piece folded by k_spell_fold: FoldPiece (k2r_reduce.h) with dt and the leaf's range as stored integers.
-struct SpellFold {
-    uint32_t nt, rows, cols, sr, init;
-    int32_t enc;
-    uint32_t fbits, elided;
-    uint64_t src, o_off, s_off, psz;
+// A fallback or elided piece: CellFold with dt and the leaf's range as stored integers.
+struct SpellFold : CellFold {
     uint32_t dt, flags;
     int64_t lo, hi;
 };
+K2R_PIN_BEGIN
+static_assert(sizeof(SpellUnit) == 72 && sizeof(SpellFold) == 88, "SpellUnit, SpellFold");
+K2R_PIN(SpellUnit, init, 28) K2R_PIN(SpellUnit, dt, 32) K2R_PIN(SpellUnit, lo, 36) K2R_PIN(SpellUnit, hi, 40) K2R_PIN(SpellUnit, flags, 44)
+K2R_PIN(SpellUnit, o_off, 48) K2R_PIN(SpellUnit, s_off, 56) K2R_PIN(SpellUnit, psz, 64)
+K2R_PIN(SpellFold, psz, 56) K2R_PIN(SpellFold, dt, 64) K2R_PIN(SpellFold, flags, 68) K2R_PIN(SpellFold, lo, 72) K2R_PIN(SpellFold, hi, 80)
+K2R_PIN_END
 
 #if defined(__HIPCC__)
 struct ChunkRef;

@@ -100,6 +100,43 @@ def test_every_dtype_segments_and_blocks(rasters, kind):
     assert_same(d["count"], want["count"])
 
 
+# 2 x 2 tiles -- 64 x 64, two strips of 6 and the 6 x 6 corner chunk (fallback walk) -- and three segments, the last one short.  The
+# second cube is unaligned in every edge and its planes have an odd size (63 x 63), so a row's four cells are clipped, meet their
+# plane at a misaligned address, and every piece after the first continues the state its cells' planes hold.
+FOLD_SHAPE, FOLD_TILE, FOLD_CS = (20, 70, 70), 64, 8
+FOLD_CUBES = [[0, 20, 0, 70, 0, 70], [3, 19, 3, 66, 5, 68]]
+
+
+def fold_source(kind):
+    a = BD.source(kind, FOLD_SHAPE)
+    if a.dtype.kind == "f":
+        a[:, 17, 23] = np.nan        # at every instant
+        a[:6, 40, 5] = np.nan        # at every instant but one
+        a[7:, 40, 5] = np.nan
+        a[2:11, 10:30, 30:50] = np.nan  # a patch across the first segment boundary
+        a[5:, 66, 67] = np.nan       # (in the corner chunk)
+    return a
+
+
+@pytest.mark.parametrize("kind", ["i32", "f32"])
+def test_every_instantiation_of_the_shared_fold(dc, kind):
+    """Every `ops` in 1 .. 31: k_bulk_reduce<LIVE> for LIVE 1 .. 15, with and without MEAN, and the per-cell fold kernel."""
+    a = fold_source(kind)
+    R = BD.build_raster(dc, a, FOLD_TILE, FOLD_CS)
+    want = [M.reduce_time(a[t0:t1, r0:r1, c0:c1]) for t0, t1, r0, r1, c0, c1 in FOLD_CUBES]
+    if kind == "f32":
+        assert (want[0]["count"] == 0).any() and (want[0]["count"] == 1).any() and (want[1]["count"] < 16).any()
+    for ops in range(1, 32):
+        flat, off, _, stats = R.reduce_time_flat(FOLD_CUBES, ops)
+        assert int(stats[0]) > 0 and int(stats[1]) > 0 and int(stats.sum()) == BD.volume(FOLD_CUBES)
+        for q, (t0, t1, r0, r1, c0, c1) in enumerate(FOLD_CUBES):
+            got = M.planes(flat, off, q, ops, r1 - r0, c1 - c0)
+            assert list(got) == M.names_of(ops)
+            for n in got:
+                assert_same(got[n], want[q][n])
+    R.close()
+
+
 def order_raster(dc, dtype):
     """[24, 64, 64], tile 64, chunk_size 8: three segments built apart with 0, 25 and 12 fractional bits, values m / 2^bits with
     |m| < 2^28 -- stored integers 2 m + 1 inside +-2^30, so every chunk takes the bulk kernel -- whose sum depends on the order."""

@@ -100,6 +100,28 @@ def test_every_dtype_segments_and_blocks(rasters, kind):
 
 
 @pytest.mark.parametrize("kind", ["i32", "f32"])
+def test_every_instantiation_of_the_shared_fold(dc, kind):
+    """Every `ops` in 1 .. 31: k_bulk_spell<GROUPS> for GROUPS 1 .. 7 with every choice of scratch planes, and the per-cell fold kernel,
+    on the small raster of the reduce_time test: a whole cube and one unaligned in every edge with planes of an odd size."""
+    a = RT.fold_source(kind)
+    R = BD.build_raster(dc, a, RT.FOLD_TILE, RT.FOLD_CS)
+    cubes = RT.FOLD_CUBES
+    lower, upper = bound_pairs(a)  # (one pair per cube)
+    want = [M.spells(M.hits(a[t0:t1, r0:r1, c0:c1], lower[q], upper[q])) for q, (t0, t1, r0, r1, c0, c1) in enumerate(cubes)]
+    for w, c in zip(want, cubes):
+        assert 0 < w["count"].sum() < BD.volume([c]) and (w["longest"] > 1).any() and (w["longest"] < w["count"]).any()
+    for ops in range(1, 32):
+        flat, off, _, stats = R.spells_flat(cubes, lower, upper, ops)
+        assert int(stats[0]) > 0 and int(stats[1]) > 0 and int(stats.sum()) == BD.volume(cubes)
+        for q, (t0, t1, r0, r1, c0, c1) in enumerate(cubes):
+            got = M.planes(flat, off, q, ops, r1 - r0, c1 - c0)
+            assert list(got) == M.names_of(ops)
+            for n in got:
+                same(got[n], want[q][n])
+    R.close()
+
+
+@pytest.mark.parametrize("kind", ["i32", "f32"])
 def test_cross_checks_with_search_values_and_reduce_time(rasters, kind):
     a, R = rasters(kind)
     T, Rr, Cc = SHAPE
@@ -296,7 +318,7 @@ print("STATS", int(stats[0]), int(stats[1]), int(stats[2]))
 
 @pytest.mark.parametrize("slab", [None, "150000"], ids=["default_slab", "pieces_cut_in_time"])
 def test_fallback_without_top_table_in_a_child_process(slab):
-    """No side-16 tables: every piece takes the window walk and k_spell_fold.  With a slab of 150 000 cells the 8 x 256 x 200 pieces
+    """No side-16 tables: every piece takes the window walk and k_cell_fold.  With a slab of 150 000 cells the 8 x 256 x 200 pieces
     of the first cube are cut in time, two instants a slab: runs cross slab cuts inside a segment."""
     env = dict(os.environ, K2R_NO_TOP_TABLE="1")
     if slab:
