@@ -65,6 +65,7 @@ SYMBOLS = [
     "dcdf_raster_reduce_time_batch", "dcdf_raster_reduce_space_batch", "dcdf_space_fold_records",
     "dcdf_raster_histogram_batch", "dcdf_histogram_bounds", "dcdf_raster_spells_batch",
     "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs", "dcdf_raster_quantile_time_batch", "dcdf_quantile_select_host",
+    "dcdf_raster_reduce_time_groups_batch",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -73,6 +74,7 @@ HIST_MAX_BINS = 256  # DCDF_HIST_MAX_BINS
 SPELL_OPS = {"count": 1, "longest": 2, "longest_start": 4, "first": 8, "last": 16}
 SPELL_NONE = 0xffffffff  # DCDF_SPELL_NONE
 ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
+GROUP_NONE = 0xffff  # DCDF_GROUP_NONE: the label of an instant of no group (dcdf_raster_reduce_time_groups_batch)
 # dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
 QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
 QUANTILE_MAX_PROBS = 16
@@ -119,6 +121,9 @@ def lib():
         L.dcdf_raster_zonal_batch.restype = C.c_int
         L.dcdf_raster_zonal_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_reduce_time_groups_batch.restype = C.c_int
+        L.dcdf_raster_reduce_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.dcdf_raster_quantile_time_batch.restype = C.c_int

@@ -1,11 +1,12 @@
-// k2r_bulk.hip -- the six bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
-// (k2r_reduce.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h), spell statistics (k2r_spell.h), zonal
-// statistics (k2r_zonal.h).  All six
+// k2r_bulk.hip -- the seven bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
+// (k2r_reduce.h), grouped reduction over time (k2r_group.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h),
+// spell statistics (k2r_spell.h), zonal statistics (k2r_zonal.h).  All seven
 // walk a unit the same way; that walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8,
 // bulk_select16).  A thread gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
 #include <hip/hip_runtime.h>
 
 #include "k2r_bulk_walk.h"
+#include "k2r_group.h"
 #include "k2r_hist.h"
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
@@ -314,6 +315,163 @@ int launch_bulk_reduce(const ChunkRef* d_refs, const uint8_t* d_enc, const Reduc
         default: return DCDF_ERR_BAD_ARG;
     }
 #undef K2R_REDUCE_CASE
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- grouped reduction over time (k2r_group.h): k_bulk_reduce's accumulators, one run of equal labels at a time ---------------
+// The thread's accumulators of one run into the planes of the run's group (p_*: already moved to that group): k_bulk_reduce's
+// end-of-unit code with the planes always loaded -- they were filled with the identities before the first segment.  SUM is
+// stored (the run began with the plane's value), COUNT added -- for an integer leaf the run's length --, MIN / MAX by fmin / fmax.
+template <uint32_t LIVE>
+__device__ __forceinline__ void group_merge16(const GroupUnit& U, uint32_t tid, int kind, int32_t enc, uint32_t fbits, int32_t sg, uint32_t run,
+                                              double* p_min, double* p_max, double* p_sum, double* p_cnt, const double (&sum)[4][4],
+                                              const uint32_t (&cnt)[4][4], const int32_t (&lo)[4][4], const int32_t (&hi)[4][4]) {
+    const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+    // The cells' places are worked out again at every merge: hoisted out of the instants' loop they would stay in registers over
+    // the walk, which costs a wave per SIMD.
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (uint32_t a = 0; a < 4u; a++) {
+        const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+        if (r < top || r >= bottom || c0 + 4u <= left || c0 >= right) continue;
+        const int64_t at = (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left);
+        if constexpr ((LIVE & RA_SUM) != 0) plane_store4(p_sum + at, sum[a], c0, left, right);
+        if constexpr ((LIVE & RA_COUNT) != 0) {
+            double x[4], old[4] = {0.0, 0.0, 0.0, 0.0};
+            plane_load4(p_cnt + at, old, c0, left, right);
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) x[e] = old[e] + (double)(kind != 0 ? cnt[a][e] : run);
+            plane_store4(p_cnt + at, x, c0, left, right);
+        }
+        if constexpr ((LIVE & RA_MIN) != 0) {
+            double x[4], old[4];
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) {
+                x[e] = leaf_extreme(lo[a][e], INT32_MAX, enc, fbits, sg);
+                old[e] = __builtin_nan("");
+            }
+            plane_load4(p_min + at, old, c0, left, right);
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) x[e] = fmin(old[e], x[e]);
+            plane_store4(p_min + at, x, c0, left, right);
+        }
+        if constexpr ((LIVE & RA_MAX) != 0) {
+            double x[4], old[4];
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) {
+                x[e] = leaf_extreme(hi[a][e], INT32_MIN, enc, fbits, sg);
+                old[e] = __builtin_nan("");
+            }
+            plane_load4(p_max + at, old, c0, left, right);
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) x[e] = fmax(old[e], x[e]);
+            plane_store4(p_max + at, x, c0, left, right);
+        }
+    }
+}
+// k_bulk_reduce with a label per instant (labels[U.lab + (t - U.t0)], uniform over the workgroup, read once per instant): the
+// register accumulators hold one run of equal labels.  On a change of group -- and, through the same code, behind the last
+// instant -- the run is merged into its group's planes (group_merge16); a new run starts from the identities and its group's
+// running SUM.  A thread always meets the same cells, so what it stored for a group it loads back itself when the group returns.
+// Instants of no group are neither decoded nor merged: every instant is decoded from its block's Snapshot and its own Log alone
+// (bulk_instant keeps track of the Snapshot in the pyramid).
+template <uint32_t LIVE>
+__global__ void __launch_bounds__(256)
+k_bulk_group(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const GroupUnit* __restrict__ units, uint32_t n_units,
+             const uint16_t* __restrict__ labels, uint32_t n_groups, double* dst, double* scr, uint32_t ops) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    const uint32_t tid = threadIdx.x;
+    constexpr uint32_t END = 0xffffffffu;  // the "label" behind the unit's last instant: it differs from every group
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const GroupUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int32_t enc = (int32_t)encs[U.chunk];
+        const int kind = leaf_kind(enc);
+        const int64_t div = (int64_t)1 << (C.fbits + 1u);  // from_fixed's divisor
+        const double inv = 1.0 / (double)div;
+        const float invf = 1.0f / (float)div;
+        const int32_t sg = leaf_mirror(kind, C.fbits);
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        // group 0's planes; group g's are g * U.gsz on
+        double* const p_min = reduce_plane(RA_MIN, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_max = reduce_plane(RA_MAX, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_sum = reduce_plane(RA_SUM, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_cnt = reduce_plane(RA_COUNT, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double sum[4][4];
+        uint32_t cnt[4][4];
+        int32_t lo[4][4], hi[4][4];
+        uint32_t cur = GROUP_NONE, run = 0;  // the open run's group and length
+        uint32_t cur_snap = 0xffffffffu;
+        for (uint32_t t = U.t0;; t++) {
+            const uint32_t lab = t < U.t1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)labels[U.lab + (t - U.t0)]) : END;
+            if (lab != END && lab >= n_groups) continue;
+            if (lab != cur) {
+                if (cur != GROUP_NONE) {
+                    const uint64_t go = (uint64_t)cur * U.gsz;
+                    group_merge16<LIVE>(U, tid, kind, enc, C.fbits, sg, run, p_min + go, p_max + go, p_sum + go, p_cnt + go, sum, cnt, lo, hi);
+                }
+                if (lab == END) break;
+                cur = lab;
+                run = 0;
+                uint32_t tl = tid;  // (as in group_merge16: the places of the cells are not kept over the walk)
+                asm volatile("" : "+v"(tl));
+#pragma unroll
+                for (uint32_t a = 0; a < 4u; a++) {
+#pragma unroll
+                    for (uint32_t e = 0; e < 4u; e++) {
+                        sum[a][e] = 0.0;
+                        cnt[a][e] = 0u;
+                        lo[a][e] = INT32_MAX;
+                        hi[a][e] = INT32_MIN;
+                    }
+                    if constexpr ((LIVE & RA_SUM) != 0) {
+                        const uint32_t g = tl + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+                        if (r >= top && r < bottom && c0 + 4u > left && c0 < right)
+                            plane_load4(p_sum + (uint64_t)cur * U.gsz + ((int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left)), sum[a], c0, left, right);
+                    }
+                }
+            }
+            run++;
+            const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+#pragma unroll
+            for (uint32_t k = 0; k < 2u; k++) {
+                const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
+                if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
+                V v[2][4];
+                bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
+#pragma unroll
+                for (uint32_t i = 0; i < 2u; i++) {
+                    const uint32_t r = r0 + i, a = 2u * k + i;
+                    if (r < top || r >= bottom) continue;
+                    if (kind == 0) reduce_fold4<LIVE, 0>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                    else if (kind == 1) reduce_fold4<LIVE, 1>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                    else reduce_fold4<LIVE, 2>(v[i], sum[a], cnt[a], lo[a], hi[a], inv, invf, sg);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+int launch_bulk_group(const ChunkRef* d_refs, const uint8_t* d_enc, const GroupUnit* d_units, uint32_t n, const uint16_t* d_labels,
+                      uint32_t n_groups, double* d_dst, double* d_scr, uint32_t ops) {
+    if (n == 0) return DCDF_OK;
+    const dim3 grid = bulk_grid(n), block(256);
+#define K2R_GROUP_CASE(L) \
+    case L: hipLaunchKernelGGL((k_bulk_group<L>), grid, block, 0, 0, d_refs, d_enc, d_units, n, d_labels, n_groups, d_dst, d_scr, ops); break;
+    switch (reduce_live(ops)) {
+        K2R_GROUP_CASE(1) K2R_GROUP_CASE(2) K2R_GROUP_CASE(3) K2R_GROUP_CASE(4) K2R_GROUP_CASE(5)
+        K2R_GROUP_CASE(6) K2R_GROUP_CASE(7) K2R_GROUP_CASE(8) K2R_GROUP_CASE(9) K2R_GROUP_CASE(10)
+        K2R_GROUP_CASE(11) K2R_GROUP_CASE(12) K2R_GROUP_CASE(13) K2R_GROUP_CASE(14) K2R_GROUP_CASE(15)
+        default: return DCDF_ERR_BAD_ARG;
+    }
+#undef K2R_GROUP_CASE
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

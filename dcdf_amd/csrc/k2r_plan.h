@@ -1,4 +1,5 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_space, histogram, spells, zonal, quantile_time: k2r_raster_region.hip)
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_time_groups, reduce_space, histogram, spells, zonal, quantile_time:
+// k2r_raster_region.hip)
 // turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
 // A cube is cut into pieces, one per leaf it meets (raster_pieces).  A piece is of one of three kinds: on an elided leaf (one
@@ -12,6 +13,7 @@
 #include <utility>
 
 #include "k2r_bulk.h"
+#include "k2r_group.h"
 #include "k2r_hist.h"
 #include "k2r_items.h"
 #include "k2r_quantile.h"
@@ -361,6 +363,37 @@ inline int plan_reduce_time(const PlanRaster& g, const dcdf_cube* cubes, size_t 
         });
     }
     return B.assemble(P, node_wise, [](FoldPiece&, uint32_t) {});
+}
+
+// ---- grouped reduce over time ------------------------------------------------------------------------------------------------
+// plan_reduce_time's plan with the accumulators' "planes" n_groups times as large (k2r_group.h): base[q] / sbase[q] are cube q's
+// first output / scratch array [n_groups][rows][cols], loff[q] the place of its first label in the call's device label array.  No
+// record initialises: k_group_fill sets the arrays `means` lists to the identities before the first segment.  A unit's instants are never
+// split over workgroups (as in plan_spells): two workgroups on the same cells would have to merge a group's running sum.
+struct GroupPlan : SegmentPlan<GroupUnit, GroupFold> {
+    std::vector<MeanPiece> means;  // every cube's arrays: what the fill and MEAN run over
+    using SegmentPlan::SegmentPlan;
+};
+inline int plan_reduce_time_groups(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* loff, uint32_t n_groups,
+                                   const uint64_t* base, const uint64_t* sbase, bool node_wise, GroupPlan& P) {
+    SegmentBuckets<GroupUnit, GroupFold> B(g);
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        const uint64_t wr = c.bottom - c.top, wc = c.right - c.left;
+        if (cube_cells(c) == 0) continue;
+        P.means.push_back(MeanPiece{base[q], sbase[q], n_groups * wr * wc});
+        plan_pieces(g, c, P.stats, [&](const Piece& p) K2R_PLAN_LAMBDA {
+            GroupFold f{cell_fold(g, p, wr, wc, base[q], sbase[q]), loff[q] + p.dt, wr * wc};
+            f.init = 0;
+            f.psz = n_groups * wr * wc;
+            B.put(p, f, [&](GroupUnit& u) {
+                cell_unit(u, p, f);
+                u.lab = f.lab;
+                u.gsz = f.gsz;
+            });
+        });
+    }
+    return B.assemble(P, node_wise, [](GroupFold& f, uint32_t a) { f.lab += a; });  // a part cut in time: its own first label
 }
 
 // ---- reduce over space -------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time, spell
+// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time (plain and grouped), spell
 // statistics, quantiles over time, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
@@ -9,7 +9,7 @@
 
 using namespace k2r;
 
-// ---- what the seven calls share ---------------------------------------------------------------------------------------------
+// ---- what the eight calls share ---------------------------------------------------------------------------------------------
 // Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
 // error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
 enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
@@ -188,7 +188,7 @@ extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* c
     if (rc != DCDF_OK) return rc;
     return batch_epilogue(W, ev, P.items.empty(), kernel_ms);
 }
-// ---- per-cell folds over time: reduce_time and spells (k2r_cell_fold.h) -------------------------------------------------------
+// ---- per-cell folds over time: reduce_time, reduce_time_groups and spells (k2r_cell_fold.h) -----------------------------------
 // The plan, and what keeps a cell's instants in order, are plan_reduce_time's and plan_spells' (k2r_plan.h): the segments are
 // launched one after the other in ascending order on the null stream, and every piece continues the state its cells' planes
 // hold.  The state planes are the output planes themselves (cube q's requested planes in ascending bit order); states kept for
@@ -199,18 +199,18 @@ extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* c
 // have --, then folded by k_cell_fold: a thread per cell, its instants in order.  Elided pieces are folded by the same kernel
 // straight from dcdf_raster::d_vals (one value per instant).  Op -- a per-cell statistic -- has
 //   Piece, T                 the fold record, a CellFold (k2r_cell_fold.h) and what else the statistic needs; the planes' element
-//   Op(P, dst, scr, ops)     per piece: the plane pointers
+//   Op(P, dst, scr, ops, x...)  per piece: the plane pointers; x: what else the statistic's kernel is given (X)
 //   init() / load(at)        the cell's initial state / its state from the planes (only when the piece continues a cube)
 //   step(P, t, n)            the stored integer n of the piece's instant t into the state
 //   store(at)                the state into the planes
-template <class Op>
+template <class Op, class... X>
 __global__ void __launch_bounds__(256)
 k_cell_fold(const typename Op::Piece* __restrict__ ps, uint32_t n, const int64_t* __restrict__ slab, const int64_t* __restrict__ vals,
-            typename Op::T* dst, typename Op::T* scr, uint32_t ops) {
+            typename Op::T* dst, typename Op::T* scr, uint32_t ops, X... x) {
     for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
         const typename Op::Piece P = ps[p];
         const uint64_t cells = (uint64_t)P.rows * P.cols;
-        Op op(P, dst, scr, ops);
+        Op op(P, dst, scr, ops, x...);
         for (uint64_t e = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; e < cells; e += (uint64_t)gridDim.y * blockDim.x) {
             const uint64_t at = e / P.cols * P.sr + e % P.cols;
             op.init();
@@ -297,6 +297,50 @@ struct SpellCell {
         if (live & SP_CUR) p_cur[at] = s.cur;
     }
 };
+// reduce_time_groups (k2r_group.h): ReduceCell's accumulators for one run of equal labels at a time (group_step), merged into
+// the run's group at a change of group and at the piece's end.  A GroupFold never initialises -- the planes are filled first --,
+// so load() always runs: it is where the cell's planes are taken.
+struct GroupCell {
+    typedef GroupFold Piece;
+    typedef double T;
+    const uint16_t* const labels;
+    const uint32_t n_groups;
+    GroupPlanes base, at;  // of the piece's first cell, of the thread's cell
+    GroupState st;
+    __device__ GroupCell(const GroupFold& P, double* dst, double* scr, uint32_t ops, const uint16_t* labels_, uint32_t n_groups_)
+        : labels(labels_ + P.lab), n_groups(n_groups_) {
+        const uint32_t live = reduce_live(ops);
+        base.p_min = live & RA_MIN ? reduce_plane(RA_MIN, dst, scr, ops, P.o_off, P.s_off, P.psz) : nullptr;
+        base.p_max = live & RA_MAX ? reduce_plane(RA_MAX, dst, scr, ops, P.o_off, P.s_off, P.psz) : nullptr;
+        base.p_sum = live & RA_SUM ? reduce_plane(RA_SUM, dst, scr, ops, P.o_off, P.s_off, P.psz) : nullptr;
+        base.p_cnt = live & RA_COUNT ? reduce_plane(RA_COUNT, dst, scr, ops, P.o_off, P.s_off, P.psz) : nullptr;
+        base.gsz = P.gsz;
+        at = base;
+    }
+    __device__ void init() { st = group_init(); }
+    __device__ void load(uint64_t e) {
+        at.p_min = base.p_min ? base.p_min + e : nullptr;
+        at.p_max = base.p_max ? base.p_max + e : nullptr;
+        at.p_sum = base.p_sum ? base.p_sum + e : nullptr;
+        at.p_cnt = base.p_cnt ? base.p_cnt + e : nullptr;
+    }
+    __device__ void step(const GroupFold& P, uint32_t t, int64_t n) { group_step(st, at, labels[t], n_groups, reduce_widen(P.enc, P.fbits, n)); }
+    __device__ void store(uint64_t) const { group_merge(st, at); }
+};
+// the identities of every live accumulator of reduce_time_groups into the cubes' arrays, before the first segment: SUM 0.0,
+// COUNT 0, MIN / MAX NaN.  A group no instant belongs to keeps them (and MEAN's 0 / 0 case makes its NaN).
+__global__ void __launch_bounds__(256) k_group_fill(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
+    const uint32_t live = reduce_live(ops);
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const MeanPiece P = ps[p];
+        for (uint32_t A = RA_MIN; A <= RA_COUNT; A <<= 1) {
+            if (!(live & A)) continue;
+            double* const q = reduce_plane(A, dst, scr, ops, P.o_off, P.s_off, P.psz);
+            const double v = A & (RA_MIN | RA_MAX) ? __builtin_nan("") : 0.0;
+            for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) q[e] = v;
+        }
+    }
+}
 // the finishing kernel of reduce_time: MEAN = SUM / COUNT, NaN where nothing was counted
 __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
     for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
@@ -310,16 +354,18 @@ __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict
         }
     }
 }
-// What follows region_begin in both calls.  live: the states the call carries, `ops` and those kept for another's sake.
+// What follows region_begin in the three calls.  live: the states the call carries, `ops` and those kept for another's sake.
 // make_plan(P, base, sbase) fills the Plan (a SegmentPlan); staged(P) uploads what else the call's launches read, before the
 // events; bulk(units, g, d_dst, d_scr) launches the bulk kernel over range g's units; finish(P, d_dst, d_scr) launches what
 // follows the last segment.  Per segment: the elided folds, the bulk units, the walk's slabs -- a segment's pieces share no cell.
-template <class Op, class Plan, class MakePlan, class Bulk, class Staged, class Finish>
-static int cell_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t live, typename Op::T* out, int out_mem,
-                           const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms, MakePlan&& make_plan, Bulk&& bulk, Staged&& staged,
-                           Finish&& finish) {
+// depth: the [rows][cols] planes of one state (reduce_time_groups: its groups); first(P, d_dst, d_scr) launches what precedes the
+// first segment; x: what k_cell_fold hands to Op besides the planes.
+template <class Op, class Plan, class MakePlan, class Bulk, class Staged, class First, class Finish, class... X>
+static int cell_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t live, uint32_t depth, typename Op::T* out,
+                           int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms, MakePlan&& make_plan, Bulk&& bulk,
+                           Staged&& staged, First&& first, Finish&& finish, X... x) {
     typedef typename Op::T T;
-    const PlaneLayout L(cubes, nq, popc32(ops), popc32(live & ~ops));
+    const PlaneLayout L(cubes, nq, popc32(ops) * depth, popc32(live & ~ops) * depth);
     WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(T), out_mem == DCDF_MEM_DEVICE);
     Plan P(reduce_slab_cells());
     int rc = make_plan(P, W.base.data(), L.sbase.data());
@@ -333,15 +379,26 @@ static int cell_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t 
     rc = R.upload(P);
     if (rc == DCDF_OK) rc = staged(P);
     if (rc == DCDF_OK) rc = R.start();
+    if (rc == DCDF_OK) rc = first(P, d_dst, d_scr.as<T>());
     if (rc != DCDF_OK) return rc;
     for (const SegRange& g : P.ranges) {
-        rc = R.fold_consts<k_cell_fold<Op>, typename Op::Piece>(r, g, 16, d_dst, d_scr.as<T>(), ops);
+        rc = R.fold_consts<k_cell_fold<Op, X...>, typename Op::Piece>(r, g, 16, d_dst, d_scr.as<T>(), ops, x...);
         if (rc == DCDF_OK) rc = bulk(R.units, g, d_dst, d_scr.as<T>());
-        if (rc == DCDF_OK) rc = R.walk.run<k_cell_fold<Op>>(r, P.walk, g, 16, d_dst, d_scr.as<T>(), ops);
+        if (rc == DCDF_OK) rc = R.walk.run<k_cell_fold<Op, X...>>(r, P.walk, g, 16, d_dst, d_scr.as<T>(), ops, x...);
         if (rc != DCDF_OK) return rc;
     }
     rc = finish(P, d_dst, d_scr.as<T>());
     return rc == DCDF_OK ? R.end(W, true, kernel_ms) : rc;
+}
+// k_reduce_mean over the cubes of a plan (reduce_time, reduce_time_groups)
+static int launch_reduce_mean(const DevBuf& d_means, const std::vector<MeanPiece>& means, double* d_dst, double* d_scr, uint32_t ops) {
+    if (!(ops & ROP_MEAN)) return DCDF_OK;
+    uint64_t big = 0;
+    for (const MeanPiece& m : means) big = std::max(big, m.psz);
+    hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)), dim3(256),
+                       0, 0, d_means.as<MeanPiece>(), (uint32_t)means.size(), d_dst, d_scr, ops);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
 }
 // per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h); SUM / COUNT kept for MEAN alone are the
 // scratch planes
@@ -351,7 +408,7 @@ extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cu
     if (rc != DCDF_OK || nq == 0) return rc;
     DevBuf d_means;
     return cell_fold_batch<ReduceCell, TimePlan>(
-        r, cubes, nq, ops, reduce_live(ops), out, out_mem, out_offset, stats, kernel_ms,
+        r, cubes, nq, ops, reduce_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms,
         [&](TimePlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_reduce_time(r->plan(), cubes, nq, base, sbase, r->all_node, P); },
         [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
             return launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
@@ -361,15 +418,53 @@ extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cu
             if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
             return (int)DCDF_OK;
         },
-        [&](const TimePlan& P, double* d_dst, double* d_scr) {
-            if (!(ops & ROP_MEAN)) return (int)DCDF_OK;
+        [](const TimePlan&, double*, double*) { return (int)DCDF_OK; },
+        [&](const TimePlan& P, double* d_dst, double* d_scr) { return launch_reduce_mean(d_means, P.means, d_dst, d_scr, ops); });
+}
+// reduce_time's statistics per cell and group of a per-instant label array (k2r_group.h).  The labels of all cubes that write
+// something go to the device once, one cube after the other; the arrays [n_groups][rows][cols] are filled with the identities
+// before the first segment (k_group_fill), so every piece continues what the planes hold.
+extern "C" int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
+                                                    const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                                                    const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const bool own = ops != 0 && ops <= (RA_ALL | ROP_MEAN) && n_groups >= 1 && n_groups <= 65535 && (nq == 0 || (labels && label_offset));
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    // the device label array: the instants of every cube that has cells, in batch order
+    std::vector<uint64_t> loff(nq, 0);
+    std::vector<uint16_t> lab;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        loff[q] = lab.size();
+        lab.insert(lab.end(), labels + label_offset[q], labels + label_offset[q] + (c.end - c.start));
+    }
+    DevBuf d_means, d_labels;
+    if (!lab.empty()) K2R_HIP(d_labels.alloc_pooled(lab.size() * sizeof(uint16_t)));  // (its address is a launch argument below)
+    return cell_fold_batch<GroupCell, GroupPlan>(
+        r, cubes, nq, ops, reduce_live(ops), n_groups, out, out_mem, out_offset, stats, kernel_ms,
+        [&](GroupPlan& P, const uint64_t* base, const uint64_t* sbase) {
+            return plan_reduce_time_groups(r->plan(), cubes, nq, loff.data(), n_groups, base, sbase, r->all_node, P);
+        },
+        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
+            return launch_bulk_group(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<GroupUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                     d_labels.as<uint16_t>(), n_groups, d_dst, d_scr, ops);
+        },
+        [&](const GroupPlan& P) {
+            K2R_HIP(hipMemcpy(d_labels.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            K2R_HIP(upload(d_means, P.means));  // (the fill runs over them whatever `ops`)
+            return (int)DCDF_OK;
+        },
+        [&](const GroupPlan& P, double* d_dst, double* d_scr) {
             uint64_t big = 0;
             for (const MeanPiece& m : P.means) big = std::max(big, m.psz);
-            hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
+            hipLaunchKernelGGL(k_group_fill, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
                                dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr, ops);
             K2R_HIP(hipGetLastError());
             return (int)DCDF_OK;
-        });
+        },
+        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_reduce_mean(d_means, P.means, d_dst, d_scr, ops); },
+        (const uint16_t*)d_labels.as<uint16_t>(), n_groups);
 }
 // per cell, the hits of a value range over time and their runs (k2r_spell.h); cur, and LONGEST kept for LONGEST_START alone, are
 // the scratch planes
@@ -380,12 +475,13 @@ extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* c
     const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
     if (rc != DCDF_OK || nq == 0) return rc;
     return cell_fold_batch<SpellCell, SpellPlan>(
-        r, cubes, nq, ops, spell_live(ops), out, out_mem, out_offset, stats, kernel_ms,
+        r, cubes, nq, ops, spell_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms,
         [&](SpellPlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_spells(r->plan(), cubes, lower, upper, nq, base, sbase, r->all_node, P); },
         [&](const DevBuf& units, const SegRange& g, uint32_t* d_dst, uint32_t* d_scr) {
             return launch_bulk_spell(r->d_refs.as<ChunkRef>(), units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr, ops);
         },
-        [](const SpellPlan&) { return (int)DCDF_OK; }, [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; });
+        [](const SpellPlan&) { return (int)DCDF_OK; }, [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; },
+        [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; });
 }
 // ---- quantiles over time: per cell, order statistics of the values decode returns (k2r_quantile.h) ----------------------------
 // The plan is plan_quantile_time's (k2r_plan.h): the cubes in columns, the columns in bands of a bounded slab.  A band: its

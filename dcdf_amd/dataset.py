@@ -389,6 +389,30 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             return {n: np.full((bottom - top, right - left), 0.0 if n in ("sum", "count") else np.nan) for n in names}
         return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
 
+    def reduce_time_groups(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """reduce_time per group of instants -- monthly means from daily data (labels = np.arange(T) // 30), a climatology (labels =
+        np.arange(T) % 12): `labels` is any integer array [stop - start] of group ids, negative = no group.  Returns (ids, {name:
+        ndarray [len(ids), rows, cols] float64}): ids are the distinct non-negative ids ascending (np.unique), plane i of every
+        array is reduce_time over the instants labelled ids[i] (the sum sequential in instant order; a cell without a value in the
+        group gets NaN, NaN, +0.0, 0, NaN).  More than 65535 distinct ids: ValueError.  Through raster().reduce_time_groups: the
+        encoded bytes are read once on the GPU whatever the number of groups (dcdf_raster_reduce_time_groups_batch)."""
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
+        from . import _lib
+        from .raster import EncodedRaster
+        names = EncodedRaster.reduce_ops(ops)[1]
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.shape != (stop - start,):
+            raise ValueError("reduce_time_groups: the labels are %s %r, the instants integers %r" % (lab.dtype, lab.shape, (stop - start,)))
+        inside = lab >= 0
+        ids, inv = np.unique(lab[inside], return_inverse=True)
+        if ids.size > 65535:
+            raise ValueError("reduce_time_groups: %d distinct group ids, at most 65535" % ids.size)
+        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
+            return ids, EncodedRaster._groups_none(names, ids.size, bottom - top, right - left)
+        dense = np.full(lab.shape, _lib.GROUP_NONE, dtype=np.uint16)
+        dense[inside] = inv.astype(np.uint16)
+        return ids, self.raster().reduce_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size)
+
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
         [rows, cols] uint32} for the names of `ops` ("count", "longest", "longest_start", "first", "last", or a DCDF_SPELL_*

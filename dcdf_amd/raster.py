@@ -217,6 +217,68 @@ class EncodedRaster:
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
     @staticmethod
+    def _n_groups(n_groups):
+        n_groups = int(n_groups)
+        if not 1 <= n_groups <= 65535:
+            raise ValueError("reduce_time_groups: n_groups %d outside 1 .. 65535" % n_groups)
+        return n_groups
+
+    @staticmethod
+    def _groups_none(names, n_groups, rows, cols):
+        return {n: np.full((n_groups, rows, cols), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+
+    def reduce_time_groups_flat(self, cubes, ops, labels, n_groups, out_device_ptr=None, out_offset=None):
+        """reduce_time_flat's statistics per cell and group of instants, of dataset-level cubes [n, 6] through
+        dcdf_raster_reduce_time_groups_batch: one walk of the encoded bytes whatever the number of groups.  labels: one uint16 array
+        [instants] per (normalised) cube -- instant i, counted from the cube's first, belongs to group labels[i] when that is <
+        n_groups; GROUP_NONE (0xffff) and every other value >= n_groups belong to no group.  Cube q yields one [n_groups, rows, cols]
+        float64 array per statistic of `ops` (reduce_ops), in the order min, max, sum, count, mean: group g is reduce_time of the
+        instants labelled g, the sum sequential in instant order; a group without a non-NaN value gets NaN, NaN, +0.0, 0, NaN.  Host
+        form: returns (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's part is flat[offsets[q]:] shaped
+        (statistics, n_groups, r, c).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats =
+        uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided leaves."""
+        mask, names = self.reduce_ops(ops)
+        n_groups = self._n_groups(n_groups)
+        q = self._cubes(cubes)
+        labels = list(labels)
+        if len(labels) != len(q):
+            raise ValueError("reduce_time_groups: %d label arrays for %d cubes" % (len(labels), len(q)))
+        nt = self._extent(q, 0)
+        parts = []
+        for i, m in enumerate(labels):
+            m = np.asarray(m)
+            if m.dtype != np.uint16:
+                raise ValueError("reduce_time_groups: labels %d are %s, not uint16" % (i, m.dtype))
+            if m.shape != (int(nt[i]),):
+                raise ValueError("reduce_time_groups: labels %d have shape %r, their cube %d instants" % (i, m.shape, int(nt[i])))
+            parts.append(m)
+        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
+        return self._region_call("reduce_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), l_ptr, l_off, C.c_uint32(n_groups), out, mem, off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def reduce_time_groups(self, ops, labels, start=0, stop=None, window=None, n_groups=None):
+        """{statistic: ndarray [n_groups, rows, cols] float64}: reduce_time over the instants [start, stop) of the whole raster, or
+        of `window` = (top, bottom, left, right), separately for every group of `labels` -- uint16 [stop - start], GROUP_NONE and
+        labels >= n_groups are in no group.  n_groups defaults to the largest label present, GROUP_NONE apart, plus 1 (at least
+        1).  Without instants or cells: NaN planes, count 0 and sum 0, of that shape."""
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
+        mask, names = self.reduce_ops(ops)
+        lab = np.asarray(labels)
+        if lab.dtype != np.uint16 or lab.shape != (stop - start,):
+            raise ValueError("reduce_time_groups: the labels are %s %r, the instants uint16 %r" % (lab.dtype, lab.shape, (stop - start,)))
+        if n_groups is None:
+            named = lab[lab != L.GROUP_NONE]
+            n_groups = int(named.max()) + 1 if named.size else 1
+        n_groups = self._n_groups(n_groups)
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            return self._groups_none(names, n_groups, rows, cols)
+        out, _, _, _ = self.reduce_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups)
+        n = n_groups * rows * cols
+        return {name: out[i * n:(i + 1) * n].reshape(n_groups, rows, cols) for i, name in enumerate(names)}
+
+    @staticmethod
     def spell_ops(ops):
         """ops of spells / spells_flat as (bitmask, names in plane order): a DCDF_SPELL_* bitmask, one name or an iterable of
         "count" / "longest" / "longest_start" / "first" / "last"."""

@@ -28,6 +28,10 @@ assert list(maps) == ["max", "count", "mean"] and (maps["max"] == a[8:24].max(0)
 assert (maps["mean"] == a[8:24].sum(0) / 16.0).all()
 flat, offsets, _, stats = R.reduce_time_flat([(0, 32, 10, 200, 0, 256)], ("min", "sum"))
 assert (flat.reshape(2, 190, 256) == np.stack([a[:, 10:200].min(0), a[:, 10:200].sum(0)])).all()
+monthly = R.reduce_time_groups(("mean",), (np.arange(32) // 30).astype(np.uint16))
+assert monthly["mean"].shape == (2, 256, 256) and (monthly["mean"][0] == a[:30].sum(0) / 30.0).all() and (monthly["mean"][1] == a[30:].sum(0) / 2.0).all()
+clim = R.reduce_time_groups(("mean", "max"), (np.arange(32) % 12).astype(np.uint16))
+assert list(clim) == ["max", "mean"] and all((clim["max"][g] == a[g::12].max(0)).all() and (clim["mean"][g] == a[g::12].sum(0) / len(a[g::12])).all() for g in range(12))
 spell = R.spells(500, np.inf, ("count", "longest", "first"), 8, 24)  # instants counted from 8; 0xffffffff where nothing hit
 hit = a[8:24] >= 500
 cur = np.zeros((256, 256), dtype=np.int64)

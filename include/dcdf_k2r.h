@@ -270,6 +270,27 @@ int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_
 enum { DCDF_REDUCE_MIN = 1, DCDF_REDUCE_MAX = 2, DCDF_REDUCE_SUM = 4, DCDF_REDUCE_COUNT = 8, DCDF_REDUCE_MEAN = 16 };
 int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
                                   const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Grouped reduce over time: dcdf_raster_reduce_time_batch's statistics, per cell, separately for every group of a per-instant
+ * label array -- monthly means from daily data, a month-of-year climatology -- from ONE walk of each unit's instants.  Cubes, ops
+ * (DCDF_REDUCE_*), out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds are
+ * swapped, nq == 0 is fine, stats and kernel_ms may be NULL, stats are the numbers dcdf_raster_decode_batch reports for the same
+ * cubes (the labels do not change them).
+ *   labels   in HOST memory: instant i of cube q, counted from the cube's first instant after normalisation, has label
+ *            labels[label_offset[q] + i] and belongs to group g when that equals g < n_groups; DCDF_GROUP_NONE and every other
+ *            value >= n_groups belong to no group: such an instant contributes nowhere.  1 <= n_groups <= 65535, for all cubes.
+ * With x[t] as above, per cell and group g over the instants of the group in ascending order: MIN / MAX = fmin / fmax over the
+ * non-NaN x; SUM = the sequential chain s = 0.0, s = s + x[t]; COUNT = the number of non-NaN x; MEAN = SUM / COUNT (one
+ * division).  A group without an instant, or whose x are all NaN, gets NaN, NaN, +0.0, 0, NaN.  Cube q writes popcount(ops) arrays
+ * in ascending bit order from out + out_offset[q] (elements), each dense [n_groups][rows][cols] float64; every element of them is
+ * written whatever the memory held, nothing outside them is; a cube without instants, rows or columns writes nothing.  The result
+ * depends on no cut of the work: with n_groups == 1 and all labels 0 it is dcdf_raster_reduce_time_batch bit for bit, and for any
+ * labels group g equals reduce_time of the sub-series of the instants labelled g.
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 16, n_groups 0 or above 65535, NULL labels / label_offset / cubes / out / out_offset
+ * with nq > 0, an unknown out_mem; DCDF_ERR_BOUNDS: a cube outside the raster; DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+#define DCDF_GROUP_NONE 0xffffu
+int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
+                                         const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                                         const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
 /* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
  * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
  * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
