@@ -66,6 +66,7 @@ SYMBOLS = [
     "dcdf_raster_histogram_batch", "dcdf_histogram_bounds", "dcdf_raster_spells_batch",
     "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs", "dcdf_raster_quantile_time_batch", "dcdf_quantile_select_host",
     "dcdf_raster_reduce_time_groups_batch",
+    "dcdf_raster_moments_time_batch", "dcdf_raster_moments_time_groups_batch", "dcdf_moments_host",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -75,6 +76,8 @@ SPELL_OPS = {"count": 1, "longest": 2, "longest_start": 4, "first": 8, "last": 1
 SPELL_NONE = 0xffffffff  # DCDF_SPELL_NONE
 ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
 GROUP_NONE = 0xffff  # DCDF_GROUP_NONE: the label of an instant of no group (dcdf_raster_reduce_time_groups_batch)
+# dcdf_raster_moments_time_batch / dcdf_raster_moments_time_groups_batch: the statistics (DCDF_MOMENT_*), in plane order
+MOMENT_OPS = {"count": 1, "mean": 2, "var": 4, "std": 8}
 # dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
 QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
 QUANTILE_MAX_PROBS = 16
@@ -124,6 +127,14 @@ def lib():
         L.dcdf_raster_reduce_time_groups_batch.restype = C.c_int
         L.dcdf_raster_reduce_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_moments_time_batch.restype = C.c_int
+        L.dcdf_raster_moments_time_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_moments_time_groups_batch.restype = C.c_int
+        L.dcdf_raster_moments_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                            C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_moments_host.restype = C.c_int
+        L.dcdf_moments_host.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.dcdf_raster_quantile_time_batch.restype = C.c_int
@@ -163,6 +174,21 @@ def quantile_select_host(x, probs, method="linear"):
     check(lib().dcdf_quantile_select_host(x.ctypes.data, x.shape[0], cells, p.ctypes.data, p.size, QUANTILE_METHODS[method], out.ctypes.data,
                                           passes.ctypes.data), "quantile_select_host")
     return out[:p.size], passes
+
+
+def moments_host(x, ddof=0, state=None, finish=True):
+    """dcdf_moments_host (host only, no GPU): continues the state (c, K, s1, s2) of the moments over time -- None: the initial one
+    -- over the float64 series x, NaN skipped, with the step the kernels run.  Returns (state float64[4], (count, mean, var, std)
+    float64[4] or None without `finish`)."""
+    import numpy as np
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+    st = np.array([0.0, np.nan, 0.0, 0.0]) if state is None else np.array(state, dtype=np.float64)
+    if st.shape != (4,):
+        raise ValueError("moments_host: the state is (c, K, s1, s2)")
+    out = np.empty(4, dtype=np.float64) if finish else None
+    check(lib().dcdf_moments_host(x.ctypes.data if x.size else None, x.size, ddof, st.ctypes.data, None if out is None else out.ctypes.data),
+          "moments_host")
+    return st, out
 
 
 def zonal_fold_limbs(limbs):

@@ -1,6 +1,6 @@
-// k2r_bulk.hip -- the seven bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
-// (k2r_reduce.h), grouped reduction over time (k2r_group.h), reduction over space (k2r_space.h), value histograms (k2r_hist.h),
-// spell statistics (k2r_spell.h), zonal statistics (k2r_zonal.h).  All seven
+// k2r_bulk.hip -- the eight bulk kernels over whole regions of a stored raster: decode (k2r_bulk.h), reduction over time
+// (k2r_reduce.h), grouped reduction over time (k2r_group.h), moments over time (k2r_moment.h), reduction over space (k2r_space.h),
+// value histograms (k2r_hist.h), spell statistics (k2r_spell.h), zonal statistics (k2r_zonal.h).  All eight
 // walk a unit the same way; that walk, and why it yields fill_window's values, is in k2r_bulk_walk.h (bulk_instant, bulk_cells8,
 // bulk_select16).  A thread gets the same 16 cells of the region at every instant; what is here is what each kernel does with them.
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include "k2r_bulk_walk.h"
 #include "k2r_group.h"
 #include "k2r_hist.h"
+#include "k2r_moment.h"
 #include "k2r_reduce.h"
 #include "k2r_runtime.h"
 #include "k2r_space.h"
@@ -472,6 +473,150 @@ int launch_bulk_group(const ChunkRef* d_refs, const uint8_t* d_enc, const GroupU
         default: return DCDF_ERR_BAD_ARG;
     }
 #undef K2R_GROUP_CASE
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+
+// ---- moments over time (k2r_moment.h): the state (c, K, s1, s2) of one run of equal labels at a time ---------------------------
+// The thread's 16 states from (STORE false) or into (STORE true) the planes of one group (p_*: already moved to that group),
+// whole: there is no merge rule.  The count is kept as an integer -- it never exceeds the instants of a cube -- and converts to
+// the double the planes hold.  As in group_merge16, the cells' places are worked out again at every call.
+template <bool STORE>
+__device__ __forceinline__ void moment_state16(const GroupUnit& U, uint32_t tid, double* p_c, double* p_k, double* p_s1, double* p_s2,
+                                               uint32_t (&cnt)[4][4], double (&K)[4][4], double (&s1)[4][4], double (&s2)[4][4]) {
+    const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (uint32_t a = 0; a < 4u; a++) {
+        double x[4];
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; e++) {
+            x[e] = STORE ? (double)cnt[a][e] : 0.0;
+            if constexpr (!STORE) {  // (the identities: cells outside the unit's rectangle are neither folded nor stored)
+                K[a][e] = __builtin_nan("");
+                s1[a][e] = 0.0;
+                s2[a][e] = 0.0;
+            }
+        }
+        const uint32_t g = tid + 256u * (a >> 1), r = (uint32_t)U.rr + 2u * (g >> 4) + (a & 1u), c0 = (uint32_t)U.rc + 4u * (g & 15u);
+        if (r >= top && r < bottom && c0 + 4u > left && c0 < right) {
+            const int64_t at = (int64_t)(r - top) * U.sr + ((int64_t)c0 - (int64_t)left);
+            if constexpr (STORE) {
+                plane_store4(p_c + at, x, c0, left, right);
+                plane_store4(p_k + at, K[a], c0, left, right);
+                plane_store4(p_s1 + at, s1[a], c0, left, right);
+                plane_store4(p_s2 + at, s2[a], c0, left, right);
+            } else {
+                plane_load4(p_c + at, x, c0, left, right);
+                plane_load4(p_k + at, K[a], c0, left, right);
+                plane_load4(p_s1 + at, s1[a], c0, left, right);
+                plane_load4(p_s2 + at, s2[a], c0, left, right);
+            }
+        }
+        if constexpr (!STORE) {
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; e++) cnt[a][e] = (uint32_t)x[e];
+        }
+    }
+}
+// One instant of four cells into their states: reduce_fold4's value conversions by kind (x has from_fixed's bits; a float leaf's
+// stored 0 is NaN), then the contract's step.  Only x depends on the kind -- a uniform branch --; the states are updated by one
+// piece of code for all three.  With a state update per kind the registers of the 16 states were copied at every join: 350
+// VGPRs + AGPRs, one wave per SIMD, against 212 this way.
+__device__ __forceinline__ void moment_fold4(int kind, const int32_t (&v)[4], uint32_t (&cnt)[4], double (&K)[4], double (&s1)[4], double (&s2)[4], double inv,
+                                             float invf) {
+#pragma clang fp contract(off)
+    double x[4];
+    if (kind == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) x[e] = (double)v[e];
+    } else if (kind == 1) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) x[e] = v[e] != 0 ? (double)((float)(v[e] - 1) * invf) : __builtin_nan("");
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++) x[e] = v[e] != 0 ? (double)(v[e] - 1) * inv : __builtin_nan("");
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) moment_step(cnt[e], K[e], s1[e], s2[e], x[e]);
+}
+// k_bulk_group's walk with the moments' state: labels[U.lab + (t - U.t0)] per instant, or group 0 throughout without a label
+// array.  The instants are taken a run of equal labels at a time: the run's group's state is loaded whole, the run's instants
+// are folded in an inner loop, the state is stored whole -- the planes were filled with the identities before the first
+// segment, so a group's first touch is a load like any other, and a thread always meets the same cells.  Instants of no group
+// are not decoded and end no run.  (Loading and storing inside one loop over the instants, as k_bulk_group merges, kept two
+// copies of the states in registers.)  One instantiation: `ops` only decides which planes are output and which scratch
+// (moment_plane).
+__global__ void __launch_bounds__(256)
+k_bulk_moment(const ChunkRef* __restrict__ chunks, const uint8_t* __restrict__ encs, const GroupUnit* __restrict__ units, uint32_t n_units,
+              const uint16_t* __restrict__ labels, uint32_t n_groups, double* dst, double* scr, uint32_t ops) {
+    typedef int32_t V;
+    __shared__ V pyr[BP_SIZE];
+    __shared__ uint32_t nst[BN_SIZE];
+    __shared__ V nd[BN_SIZE];
+    const uint32_t tid = threadIdx.x;
+    constexpr uint32_t END = 0xffffffffu;  // the "label" behind the unit's last instant: it differs from every group
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const GroupUnit U = units[u];
+        const ChunkRef C = chunks[U.chunk];
+        const int kind = leaf_kind((int32_t)encs[U.chunk]);
+        const int64_t div = (int64_t)1 << (C.fbits + 1u);  // from_fixed's divisor
+        const double inv = 1.0 / (double)div;
+        const float invf = 1.0f / (float)div;
+        const gbytes gb = (gbytes)C.bytes;
+        const uint32_t top = U.top, bottom = U.bottom, left = U.left, right = U.right;
+        // group 0's planes; group g's are g * U.gsz on
+        double* const p_c = moment_plane(MS_COUNT, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_k = moment_plane(MS_K, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_s1 = moment_plane(MS_S1, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        double* const p_s2 = moment_plane(MS_S2, dst, scr, ops, U.o_off, U.s_off, U.psz);
+        uint32_t cnt[4][4];
+        double K[4][4], s1[4][4], s2[4][4];
+        uint32_t cur_snap = 0xffffffffu;
+        uint32_t t = U.t0;
+        for (;;) {
+            uint32_t lab = END;
+            for (; t < U.t1; t++) {
+                lab = labels ? (uint32_t)__builtin_amdgcn_readfirstlane((int)labels[U.lab + (t - U.t0)]) : 0u;
+                if (lab < n_groups) break;
+            }
+            if (t >= U.t1) break;
+            const uint64_t go = (uint64_t)lab * U.gsz;
+            moment_state16<false>(U, tid, p_c + go, p_k + go, p_s1 + go, p_s2 + go, cnt, K, s1, s2);
+            for (;;) {
+                const BulkInstant I = bulk_instant(C, U, t, cur_snap, pyr, nst, nd, tid);
+#pragma unroll
+                for (uint32_t k = 0; k < 2u; k++) {
+                    const uint32_t e = tid + 256u * k, rp = e >> 4, cg = e & 15u;
+                    const uint32_t r0 = (uint32_t)U.rr + 2u * rp, c0 = (uint32_t)U.rc + 4u * cg;  // chunk coordinates
+                    if (r0 + 2u <= top || r0 >= bottom || c0 + 4u <= left || c0 >= right) continue;
+                    V v[2][4];
+                    bulk_cells8(gb, I, pyr, nst, nd, rp, cg, v);
+#pragma unroll
+                    for (uint32_t i = 0; i < 2u; i++) {
+                        const uint32_t r = r0 + i, a = 2u * k + i;
+                        if (r < top || r >= bottom) continue;
+                        moment_fold4(kind, v[i], cnt[a], K[a], s1[a], s2[a], inv, invf);
+                    }
+                }
+                uint32_t next = END;
+                for (t++; t < U.t1; t++) {
+                    next = labels ? (uint32_t)__builtin_amdgcn_readfirstlane((int)labels[U.lab + (t - U.t0)]) : 0u;
+                    if (next < n_groups) break;
+                }
+                if (t >= U.t1 || next != lab) break;
+            }
+            moment_state16<true>(U, tid, p_c + go, p_k + go, p_s1 + go, p_s2 + go, cnt, K, s1, s2);
+        }
+        __syncthreads();
+    }
+}
+
+int launch_bulk_moment(const ChunkRef* d_refs, const uint8_t* d_enc, const GroupUnit* d_units, uint32_t n, const uint16_t* d_labels,
+                       uint32_t n_groups, double* d_dst, double* d_scr, uint32_t ops) {
+    if (n == 0) return DCDF_OK;
+    if (ops == 0 || ops > MO_ALL) return DCDF_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k_bulk_moment, bulk_grid(n), dim3(256), 0, 0, d_refs, d_enc, d_units, n, d_labels, n_groups, d_dst, d_scr, ops);
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }

@@ -1,4 +1,4 @@
-// k2r_cell_fold.h -- per-cell folds over time (reduce_time: k2r_reduce.h, reduce_time_groups: k2r_group.h, spells: k2r_spell.h): what every such statistic shares
+// k2r_cell_fold.h -- per-cell folds over time (reduce_time: k2r_reduce.h, reduce_time_groups: k2r_group.h, moments_time: k2r_moment.h, spells: k2r_spell.h): what every such statistic shares
 // in the planner (k2r_plan.h), the bulk kernels (k2r_bulk.hip) and the fold kernel (k2r_raster_region.hip).  Compiles for the host
 // alone as well (g++).
 //
@@ -6,7 +6,7 @@
 // piece holds its cube's first instant), steps through its instants in order and stores the state back; the pieces of a cell
 // run one after the other (SegmentPlan), so the result depends on no cut of the cell's instants.  A statistic is a state with
 // init, load, step and store (k_cell_fold's Op, k2r_raster_region.hip), two records that begin with the heads below, and a bulk
-// kernel of its own on the shared walk (k_bulk_reduce, k_bulk_group, k_bulk_spell: k2r_bulk.hip).
+// kernel of its own on the shared walk (k_bulk_reduce, k_bulk_group, k_bulk_moment, k_bulk_spell: k2r_bulk.hip).
 #pragma once
 #include <cstddef>
 

@@ -1,15 +1,16 @@
-// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time (plain and grouped), spell
-// statistics, quantiles over time, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time (plain and grouped), moments
+// over time (plain and grouped), spell statistics, quantiles over time, reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
+#include "k2r_moment.h"
 #include "k2r_raster_host.h"
 
 using namespace k2r;
 
-// ---- what the eight calls share ---------------------------------------------------------------------------------------------
+// ---- what the ten calls share -----------------------------------------------------------------------------------------------
 // Arguments (own_args_ok: the call's own), support, the zero state of the two reports, the cubes' bounds -- in the order of the
 // error codes.  EXACT_FLOATS: the call's arithmetic takes no float chunk with fractional bits value_bounds refuses.
 enum RegionFloats { ANY_FLOATS, EXACT_FLOATS };
@@ -188,7 +189,7 @@ extern "C" int dcdf_raster_decode_batch(const dcdf_raster* r, const dcdf_cube* c
     if (rc != DCDF_OK) return rc;
     return batch_epilogue(W, ev, P.items.empty(), kernel_ms);
 }
-// ---- per-cell folds over time: reduce_time, reduce_time_groups and spells (k2r_cell_fold.h) -----------------------------------
+// ---- per-cell folds over time: reduce_time, reduce_time_groups, moments_time and spells (k2r_cell_fold.h) ---------------------
 // The plan, and what keeps a cell's instants in order, are plan_reduce_time's and plan_spells' (k2r_plan.h): the segments are
 // launched one after the other in ascending order on the null stream, and every piece continues the state its cells' planes
 // hold.  The state planes are the output planes themselves (cube q's requested planes in ascending bit order); states kept for
@@ -341,6 +342,57 @@ __global__ void __launch_bounds__(256) k_group_fill(const MeanPiece* __restrict_
         }
     }
 }
+// moments_time / moments_time_groups (k2r_moment.h): the state (c, K, s1, s2) of one run of equal labels at a time
+// (moment_group_step), stored whole at a change of group and at the piece's end.  As GroupCell: the planes are filled first, no
+// piece initialises, load() is where the cell's planes are taken.  Without a label array every instant is group 0.
+struct MomentCell {
+    typedef GroupFold Piece;
+    typedef double T;
+    const uint16_t* const labels;
+    const uint32_t n_groups;
+    MomentPlanes base, at;  // of the piece's first cell, of the thread's cell
+    MomentRun st;
+    __device__ MomentCell(const GroupFold& P, double* dst, double* scr, uint32_t ops, const uint16_t* labels_, uint32_t n_groups_)
+        : labels(labels_ ? labels_ + P.lab : nullptr), n_groups(n_groups_), base(moment_planes(dst, scr, ops, P.o_off, P.s_off, P.psz, P.gsz)), at(base) {}
+    __device__ void init() { st = moment_run_init(); }
+    __device__ void load(uint64_t e) { at = MomentPlanes{base.p_c + e, base.p_k + e, base.p_s1 + e, base.p_s2 + e, base.gsz}; }
+    __device__ void step(const GroupFold& P, uint32_t t, int64_t n) {
+        moment_group_step(st, at, moment_label(labels, t), n_groups, reduce_widen(P.enc, P.fbits, n));
+    }
+    __device__ void store(uint64_t) const { moment_store(st, at); }
+};
+// the initial state (0, NaN, +0.0, +0.0) into the four state arrays of every cube, before the first segment
+__global__ void __launch_bounds__(256) k_moment_fill(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
+    const MomentState s0 = moment_init();
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const MeanPiece P = ps[p];
+        const MomentPlanes Q = moment_planes(dst, scr, ops, P.o_off, P.s_off, P.psz, 0);
+        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) {
+            Q.p_c[e] = s0.c;
+            Q.p_k[e] = s0.K;
+            Q.p_s1[e] = s0.s1;
+            Q.p_s2[e] = s0.s2;
+        }
+    }
+}
+// the finishing kernel of the moments: every cell's (and group's) state into the requested planes of MEAN, VAR and STD
+// (moment_finish); COUNT's plane is its state
+__global__ void __launch_bounds__(256) k_moment_finish(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops, uint32_t ddof) {
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const MeanPiece P = ps[p];
+        const MomentPlanes Q = moment_planes(dst, scr, ops, P.o_off, P.s_off, P.psz, 0);
+        double* const p_mean = moment_plane(MO_MEAN, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_var = moment_plane(MO_VAR, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        double* const p_std = moment_plane(MO_STD, dst, scr, ops, P.o_off, P.s_off, P.psz);
+        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < P.psz; e += (uint64_t)gridDim.x * blockDim.x) {
+            double o[4];
+            moment_finish(MomentState{Q.p_c[e], Q.p_k[e], Q.p_s1[e], Q.p_s2[e]}, ddof, o);
+            if (ops & MO_MEAN) p_mean[e] = o[1];
+            if (ops & MO_VAR) p_var[e] = o[2];
+            if (ops & MO_STD) p_std[e] = o[3];
+        }
+    }
+}
 // the finishing kernel of reduce_time: MEAN = SUM / COUNT, NaN where nothing was counted
 __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict__ ps, uint32_t n, double* dst, double* scr, uint32_t ops) {
     for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
@@ -354,7 +406,7 @@ __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict
         }
     }
 }
-// What follows region_begin in the three calls.  live: the states the call carries, `ops` and those kept for another's sake.
+// What follows region_begin in the five calls.  live: the states the call carries, `ops` and those kept for another's sake.
 // make_plan(P, base, sbase) fills the Plan (a SegmentPlan); staged(P) uploads what else the call's launches read, before the
 // events; bulk(units, g, d_dst, d_scr) launches the bulk kernel over range g's units; finish(P, d_dst, d_scr) launches what
 // follows the last segment.  Per segment: the elided folds, the bulk units, the walk's slabs -- a segment's pieces share no cell.
@@ -465,6 +517,85 @@ extern "C" int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const 
         },
         [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_reduce_mean(d_means, P.means, d_dst, d_scr, ops); },
         (const uint16_t*)d_labels.as<uint16_t>(), n_groups);
+}
+// A kernel over the cubes' arrays of a plan (P.means), a row of workgroups per cube: the fills and the finishing kernels.
+template <auto Kernel, class... Args>
+static int launch_over_means(const DevBuf& d_means, const std::vector<MeanPiece>& means, Args... args) {
+    if (means.empty()) return DCDF_OK;
+    uint64_t big = 0;
+    for (const MeanPiece& m : means) big = std::max(big, m.psz);
+    hipLaunchKernelGGL(Kernel, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)), dim3(256), 0, 0,
+                       d_means.as<MeanPiece>(), (uint32_t)means.size(), args...);
+    K2R_HIP(hipGetLastError());
+    return DCDF_OK;
+}
+// Per-cell count, mean, variance and standard deviation over time (k2r_moment.h), per group of a per-instant label array or --
+// labels == nullptr: the ungrouped call -- as one group every instant belongs to.  One path: the grouped reduce's plan
+// (plan_reduce_time_groups) and records, the four state arrays filled before the first segment (k_moment_fill), MEAN / VAR / STD
+// made by k_moment_finish behind the last; ddof goes there only.
+static int moments_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof, const uint16_t* labels,
+                         const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                         float* kernel_ms) {
+    // the device label array: the instants of every cube that has cells, in batch order
+    std::vector<uint64_t> loff(nq, 0);
+    std::vector<uint16_t> lab;
+    for (size_t q = 0; labels && q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        loff[q] = lab.size();
+        lab.insert(lab.end(), labels + label_offset[q], labels + label_offset[q] + (c.end - c.start));
+    }
+    DevBuf d_means, d_labels;
+    if (!lab.empty()) K2R_HIP(d_labels.alloc_pooled(lab.size() * sizeof(uint16_t)));  // (its address is a launch argument below)
+    const uint16_t* const d_lab = lab.empty() ? nullptr : d_labels.as<uint16_t>();
+    // (labels given, yet no cube has cells: nothing is planned and d_lab is never read)
+    return cell_fold_batch<MomentCell, GroupPlan>(
+        r, cubes, nq, ops, MS_ALL, n_groups, out, out_mem, out_offset, stats, kernel_ms,
+        [&](GroupPlan& P, const uint64_t* base, const uint64_t* sbase) {
+            return plan_reduce_time_groups(r->plan(), cubes, nq, loff.data(), n_groups, base, sbase, r->all_node, P);
+        },
+        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
+            return launch_bulk_moment(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<GroupUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
+                                      d_lab, n_groups, d_dst, d_scr, ops);
+        },
+        [&](const GroupPlan& P) {
+            if (!lab.empty()) K2R_HIP(hipMemcpy(d_labels.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            return upload_some(d_means, P.means);
+        },
+        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_over_means<k_moment_fill>(d_means, P.means, d_dst, d_scr, ops); },
+        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_over_means<k_moment_finish>(d_means, P.means, d_dst, d_scr, ops, ddof); },
+        d_lab, n_groups);
+}
+extern "C" int dcdf_raster_moments_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof, double* out, int out_mem,
+                                              const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const bool own = ops != 0 && ops <= MO_ALL && ddof <= 1;
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return moments_batch(r, cubes, nq, ops, ddof, nullptr, nullptr, 1, out, out_mem, out_offset, stats, kernel_ms);
+}
+extern "C" int dcdf_raster_moments_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof,
+                                                     const uint16_t* labels, const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                                                     const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const bool own = ops != 0 && ops <= MO_ALL && ddof <= 1 && n_groups >= 1 && n_groups <= 65535 && (nq == 0 || (labels && label_offset));
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return moments_batch(r, cubes, nq, ops, ddof, labels, label_offset, n_groups, out, out_mem, out_offset, stats, kernel_ms);
+}
+// the moments' step and finish on the host (no HIP call): continues state = (c, K, s1, s2) over x and finishes into out
+extern "C" int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, double state[4], double out[4]) {
+    if (!state || (!x && n > 0) || ddof > 1) return DCDF_ERR_BAD_ARG;
+    MomentState s{state[0], state[1], state[2], state[3]};
+    for (size_t i = 0; i < n; i++) moment_step(s, x[i]);
+    state[0] = s.c;
+    state[1] = s.K;
+    state[2] = s.s1;
+    state[3] = s.s2;
+    if (out) {
+        double o[4];
+        moment_finish(s, ddof, o);
+        for (int i = 0; i < 4; i++) out[i] = o[i];
+    }
+    return DCDF_OK;
 }
 // per cell, the hits of a value range over time and their runs (k2r_spell.h); cur, and LONGEST kept for LONGEST_START alone, are
 // the scratch planes

@@ -413,6 +413,48 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         dense[inside] = inv.astype(np.uint16)
         return ids, self.raster().reduce_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size)
 
+    def moments_time(self, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
+        """Per-cell count, mean, variance and standard deviation over the instants [start, stop) of the window [top, bottom) x
+        [left, right): {name: ndarray [rows, cols] float64} for the names of `ops` ("count", "mean", "var", "std", or a
+        DCDF_MOMENT_* bitmask), over the values window() returns widened to float64, NaN cells skipped; the divisor of var is
+        count - ddof, ddof 0 or 1.  What (x - mean) / std over a baseline period needs, from one walk: the sums are taken of
+        x - K, K the cell's first value, sequentially in instant order, so the result depends on no cut of the work, a constant
+        cell has var exactly 0 and mean exactly its value; a cell without a value gets 0, NaN, NaN, NaN.  Through
+        raster().moments_time: the encoded bytes are read once on the GPU and only the planes are written
+        (dcdf_raster_moments_time_batch)."""
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
+        from .raster import EncodedRaster
+        names = EncodedRaster.moment_ops(ops)[1]
+        ddof = EncodedRaster._ddof(ddof)
+        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
+            return EncodedRaster._moments_none(names, (bottom - top, right - left))
+        return self.raster().moments_time(ops, start, stop, window=(top, bottom, left, right), ddof=ddof)
+
+    def moments_time_groups(self, labels, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
+        """moments_time per group of instants -- mean and std per month of the year for standardised anomalies (labels =
+        month_of(instants)): `labels` is any integer array [stop - start] of group ids, negative = no group.  Returns (ids, {name:
+        ndarray [len(ids), rows, cols] float64}) as reduce_time_groups does: ids are the distinct non-negative ids ascending,
+        plane i of every array is moments_time over the instants labelled ids[i], in order (a cell without a value in the group
+        gets 0, NaN, NaN, NaN).  More than 65535 distinct ids: ValueError.  Through raster().moments_time_groups: the encoded
+        bytes are read once on the GPU whatever the number of groups (dcdf_raster_moments_time_groups_batch)."""
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
+        from . import _lib
+        from .raster import EncodedRaster
+        names = EncodedRaster.moment_ops(ops)[1]
+        ddof = EncodedRaster._ddof(ddof)
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.shape != (stop - start,):
+            raise ValueError("moments_time_groups: the labels are %s %r, the instants integers %r" % (lab.dtype, lab.shape, (stop - start,)))
+        inside = lab >= 0
+        ids, inv = np.unique(lab[inside], return_inverse=True)
+        if ids.size > 65535:
+            raise ValueError("moments_time_groups: %d distinct group ids, at most 65535" % ids.size)
+        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
+            return ids, EncodedRaster._moments_none(names, (ids.size, bottom - top, right - left))
+        dense = np.full(lab.shape, _lib.GROUP_NONE, dtype=np.uint16)
+        dense[inside] = inv.astype(np.uint16)
+        return ids, self.raster().moments_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size, ddof=ddof)
+
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
         [rows, cols] uint32} for the names of `ops` ("count", "longest", "longest_start", "first", "last", or a DCDF_SPELL_*

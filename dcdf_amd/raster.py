@@ -217,10 +217,10 @@ class EncodedRaster:
         return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
 
     @staticmethod
-    def _n_groups(n_groups):
+    def _n_groups(n_groups, what="reduce_time_groups"):
         n_groups = int(n_groups)
         if not 1 <= n_groups <= 65535:
-            raise ValueError("reduce_time_groups: n_groups %d outside 1 .. 65535" % n_groups)
+            raise ValueError("%s: n_groups %d outside 1 .. 65535" % (what, n_groups))
         return n_groups
 
     @staticmethod
@@ -275,6 +275,105 @@ class EncodedRaster:
         if start == stop or rows * cols == 0:
             return self._groups_none(names, n_groups, rows, cols)
         out, _, _, _ = self.reduce_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups)
+        n = n_groups * rows * cols
+        return {name: out[i * n:(i + 1) * n].reshape(n_groups, rows, cols) for i, name in enumerate(names)}
+
+    @staticmethod
+    def moment_ops(ops):
+        """ops of moments_time / moments_time_groups as (bitmask, names in plane order): a DCDF_MOMENT_* bitmask, one name or an
+        iterable of "count" / "mean" / "var" / "std"."""
+        mask, names = EncodedRaster._ops(ops, L.MOMENT_OPS, "moments_time")
+        if mask >= 16:
+            raise ValueError("moments_time: ops %r is not a set of %s" % (ops, ", ".join(L.MOMENT_OPS)))
+        return mask, names
+
+    @staticmethod
+    def _ddof(ddof):
+        if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or ddof not in (0, 1):
+            raise ValueError("moments_time: ddof %r is neither 0 nor 1" % (ddof,))
+        return int(ddof)
+
+    @staticmethod
+    def _moments_none(names, shape):
+        return {n: np.full(shape, 0.0 if n == "count" else np.nan) for n in names}
+
+    def moments_time_flat(self, cubes, ops, ddof=0, out_device_ptr=None, out_offset=None):
+        """Per-cell count, mean, variance and standard deviation over time of dataset-level cubes [n, 6] through
+        dcdf_raster_moments_time_batch: cube q yields one [rows, cols] float64 plane per statistic of `ops` (moment_ops), in the
+        order count, mean, var, std, over the values decode_flat returns for it in the leaves' own dtype, NaN skipped.  The sums
+        are taken of x - K, K the cell's first value, sequentially in instant order (include/dcdf_k2r.h): mean = K + s1 / count,
+        var = (s2 - s1 * s1 / count) / (count - ddof), std = sqrt(var) correctly rounded; ddof is 0 or 1.  A cell without a value
+        gets 0, NaN, NaN, NaN; a constant cell has var exactly 0.  Host form: returns (flat float64 array, offsets uint64[n],
+        kernel ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset
+        in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from
+        elided leaves."""
+        mask, names = self.moment_ops(ops)
+        ddof = self._ddof(ddof)
+        q = self._cubes(cubes)
+        return self._region_call("moments_time", q, lambda: self._planes(q, len(names)), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), C.c_uint32(ddof), out, mem, off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def moments_time(self, ops=("mean", "std"), start=0, stop=None, window=None, ddof=0):
+        """{statistic: ndarray [rows, cols] float64} of moments_time_flat over the instants [start, stop) of the whole raster, or
+        of `window` = (top, bottom, left, right).  Without instants or cells: count 0, NaN elsewhere."""
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
+        mask, names = self.moment_ops(ops)
+        ddof = self._ddof(ddof)
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            return self._moments_none(names, (rows, cols))
+        out, _, _, _ = self.moments_time_flat([[start, stop, top, bottom, left, right]], mask, ddof)
+        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+
+    def moments_time_groups_flat(self, cubes, ops, labels, n_groups, ddof=0, out_device_ptr=None, out_offset=None):
+        """moments_time_flat's statistics per cell and group of instants through dcdf_raster_moments_time_groups_batch: one walk of
+        the encoded bytes whatever the number of groups.  labels and n_groups are reduce_time_groups_flat's: one uint16 array
+        [instants] per (normalised) cube, GROUP_NONE (0xffff) and every other value >= n_groups in no group.  Cube q yields one
+        [n_groups, rows, cols] float64 array per statistic of `ops`, in the order count, mean, var, std: group g is moments_time of
+        the instants labelled g, in order (its K is the group's first value); a group without a value gets 0, NaN, NaN, NaN.
+        Returns what moments_time_flat returns, cube q's part shaped (statistics, n_groups, r, c)."""
+        mask, names = self.moment_ops(ops)
+        ddof = self._ddof(ddof)
+        n_groups = self._n_groups(n_groups, "moments_time_groups")
+        q = self._cubes(cubes)
+        labels = list(labels)
+        if len(labels) != len(q):
+            raise ValueError("moments_time_groups: %d label arrays for %d cubes" % (len(labels), len(q)))
+        nt = self._extent(q, 0)
+        parts = []
+        for i, m in enumerate(labels):
+            m = np.asarray(m)
+            if m.dtype != np.uint16:
+                raise ValueError("moments_time_groups: labels %d are %s, not uint16" % (i, m.dtype))
+            if m.shape != (int(nt[i]),):
+                raise ValueError("moments_time_groups: labels %d have shape %r, their cube %d instants" % (i, m.shape, int(nt[i])))
+            parts.append(m)
+        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
+        return self._region_call("moments_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
+                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), C.c_uint32(ddof), l_ptr, l_off, C.c_uint32(n_groups), out, mem,
+                                                                  off, stats),
+                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def moments_time_groups(self, ops, labels, start=0, stop=None, window=None, n_groups=None, ddof=0):
+        """{statistic: ndarray [n_groups, rows, cols] float64}: moments_time over the instants [start, stop) of the whole raster, or
+        of `window`, separately for every group of `labels` -- uint16 [stop - start], GROUP_NONE and labels >= n_groups are in no
+        group.  n_groups defaults to the largest label present, GROUP_NONE apart, plus 1 (at least 1).  With one group and all
+        labels 0 it is moments_time bit for bit.  Without instants or cells: count 0, NaN elsewhere, of that shape."""
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
+        mask, names = self.moment_ops(ops)
+        ddof = self._ddof(ddof)
+        lab = np.asarray(labels)
+        if lab.dtype != np.uint16 or lab.shape != (stop - start,):
+            raise ValueError("moments_time_groups: the labels are %s %r, the instants uint16 %r" % (lab.dtype, lab.shape, (stop - start,)))
+        if n_groups is None:
+            named = lab[lab != L.GROUP_NONE]
+            n_groups = int(named.max()) + 1 if named.size else 1
+        n_groups = self._n_groups(n_groups, "moments_time_groups")
+        rows, cols = bottom - top, right - left
+        if start == stop or rows * cols == 0:
+            return self._moments_none(names, (n_groups, rows, cols))
+        out, _, _, _ = self.moments_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups, ddof)
         n = n_groups * rows * cols
         return {name: out[i * n:(i + 1) * n].reshape(n_groups, rows, cols) for i, name in enumerate(names)}
 

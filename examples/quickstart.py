@@ -32,6 +32,11 @@ monthly = R.reduce_time_groups(("mean",), (np.arange(32) // 30).astype(np.uint16
 assert monthly["mean"].shape == (2, 256, 256) and (monthly["mean"][0] == a[:30].sum(0) / 30.0).all() and (monthly["mean"][1] == a[30:].sum(0) / 2.0).all()
 clim = R.reduce_time_groups(("mean", "max"), (np.arange(32) % 12).astype(np.uint16))
 assert list(clim) == ["max", "mean"] and all((clim["max"][g] == a[g::12].max(0)).all() and (clim["mean"][g] == a[g::12].sum(0) / len(a[g::12])).all() for g in range(12))
+mom = R.moments_time(("mean", "var", "std"), ddof=1)  # the shifted sums of one walk: var is exactly 0 where a cell never changes
+assert np.allclose(mom["std"], a.std(0, ddof=1)) and ((mom["var"] == 0) == (a == a[0]).all(0)).all()
+assert (R.moments_time("var", 5, 6)["var"] == 0).all() and (R.moments_time("mean", 5, 6)["mean"] == a[5]).all()  # (one instant: constant cells)
+one = R.moments_time_groups(("mean", "var", "std"), np.zeros(32, dtype=np.uint16), ddof=1)  # per group of instants; one group is the plain call
+assert all((one[n][0].view(np.uint64) == mom[n].view(np.uint64)).all() for n in mom)
 spell = R.spells(500, np.inf, ("count", "longest", "first"), 8, 24)  # instants counted from 8; 0xffffffff where nothing hit
 hit = a[8:24] >= 500
 cur = np.zeros((256, 256), dtype=np.int64)

@@ -291,6 +291,42 @@ int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, 
 int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
                                          const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
                                          const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* Moments over time: per cell (row, col) of each cube, how many values it has, their mean, variance and standard deviation --
+ * what a standardised anomaly (x - mean) / std or a variability map needs, mean and std from ONE walk.  Cubes, out_mem,
+ * out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's; labels, label_offset, n_groups and
+ * DCDF_GROUP_NONE exactly dcdf_raster_reduce_time_groups_batch's.  ops is a non-empty set of DCDF_MOMENT_*, ddof (the divisor of
+ * VAR is COUNT - ddof) 0 or 1.
+ * With x[t] as above, the state of a cell -- per group, in the grouped call -- is four doubles (c, K, s1, s2), at first
+ * (0, NaN, +0.0, +0.0).  For t ascending every non-NaN x[t] does
+ *     if (c == 0) K = x;   d = x - K;   s1 = s1 + d;   s2 = s2 + d * d;   c = c + 1;
+ * each one IEEE double operation (the product rounded, then the sum: nothing is contracted into an fma), sequentially in
+ * instant order as DCDF_REDUCE_SUM's chain is, so the result depends on no cut of the work.  Then, per cell (and group):
+ *     COUNT = c;   m = s1 / c;   MEAN = K + m;   q = s2 - s1 * m, +0.0 where that is negative;
+ *     VAR = q / (c - ddof) when c > ddof, else NaN;   STD = sqrt(VAR), correctly rounded.
+ * K, the shift, is the series' first value, a sample of the series: (mean - K)^2 / VAR <= n, which bounds the relative error of
+ * VAR by the order of (n + 2)^2 * 2^-53.  Consequences: a constant series has VAR exactly +0.0 and MEAN
+ * exactly its value; one value with ddof = 1 gives VAR = STD = NaN; MEAN is K + s1 / c, not SUM / COUNT -- it may differ from
+ * DCDF_REDUCE_MEAN in the last bits and is offered so that mean and std come from one walk --; for integer leaves with
+ * |x| < 2^53 a constant added to every value leaves VAR and STD unchanged bit for bit, because every d is exact.
+ * Cube q writes popcount(ops) planes in the order COUNT, MEAN, VAR, STD from out + out_offset[q] (elements), each dense
+ * [rows][cols] float64 -- in the grouped call [n_groups][rows][cols], group g the moments of the instants labelled g in order (its
+ * K is the group's first value).  A cell or group without a value gets 0, NaN, NaN, NaN.  Every element of the planes is written,
+ * nothing outside them is; a cube without instants, rows or columns writes nothing.  The grouped call with n_groups == 1 and all
+ * labels 0 is the plain call bit for bit.
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 8, ddof > 1, (grouped) n_groups 0 or above 65535 and NULL labels / label_offset with
+ * nq > 0, NULL r / cubes / out / out_offset, an unknown out_mem (nq == 0 is fine, stats and kernel_ms may be NULL);
+ * DCDF_ERR_BOUNDS: a cube outside the raster; DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+enum { DCDF_MOMENT_COUNT = 1, DCDF_MOMENT_MEAN = 2, DCDF_MOMENT_VAR = 4, DCDF_MOMENT_STD = 8 };
+int dcdf_raster_moments_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof, double* out, int out_mem,
+                                   const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+int dcdf_raster_moments_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof,
+                                          const uint16_t* labels, const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                                          const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms);
+/* The step and the finish above on the host -- no GPU call, the functions the kernels run.  Continues state = (c, K, s1, s2)
+ * over x[0 .. n) in order, NaN skipped, and leaves the new state there; when out is not NULL, finishes that state into out =
+ * (COUNT, MEAN, VAR, STD) with ddof.  A series starts from (0, NaN, 0, 0).  DCDF_ERR_BAD_ARG: NULL state, NULL x with n > 0,
+ * ddof > 1. */
+int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, double state[4], double out[4]);
 /* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
  * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
  * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
