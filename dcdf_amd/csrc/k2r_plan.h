@@ -395,6 +395,20 @@ inline int plan_reduce_time_groups(const PlanRaster& g, const dcdf_cube* cubes, 
     }
     return B.assemble(P, node_wise, [](GroupFold& f, uint32_t a) { f.lab += a; });  // a part cut in time: its own first label
 }
+// The call's device label array, as it is on the host: the labels of every cube that has cells -- its c.end - c.start instants,
+// from labels[label_offset[q]] --, one cube after the other in batch order; loff[q]: the place of cube q's first (0 for a cube
+// without cells).  labels == nullptr -- the ungrouped moments -- yields no label.
+inline void gather_time_labels(const dcdf_cube* cubes, size_t nq, const uint16_t* labels, const uint64_t* label_offset, std::vector<uint64_t>& loff,
+                               std::vector<uint16_t>& lab) {
+    loff.assign(nq, 0);
+    lab.clear();
+    for (size_t q = 0; labels && q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        loff[q] = lab.size();
+        lab.insert(lab.end(), labels + label_offset[q], labels + label_offset[q] + (c.end - c.start));
+    }
+}
 
 // ---- reduce over space -------------------------------------------------------------------------------------------------------
 // Every piece leaves one SpacePartial per instant in a scratch array; the pieces of one (cube, segment) share their instants, so

@@ -406,118 +406,6 @@ __global__ void __launch_bounds__(256) k_reduce_mean(const MeanPiece* __restrict
         }
     }
 }
-// What follows region_begin in the five calls.  live: the states the call carries, `ops` and those kept for another's sake.
-// make_plan(P, base, sbase) fills the Plan (a SegmentPlan); staged(P) uploads what else the call's launches read, before the
-// events; bulk(units, g, d_dst, d_scr) launches the bulk kernel over range g's units; finish(P, d_dst, d_scr) launches what
-// follows the last segment.  Per segment: the elided folds, the bulk units, the walk's slabs -- a segment's pieces share no cell.
-// depth: the [rows][cols] planes of one state (reduce_time_groups: its groups); first(P, d_dst, d_scr) launches what precedes the
-// first segment; x: what k_cell_fold hands to Op besides the planes.
-template <class Op, class Plan, class MakePlan, class Bulk, class Staged, class First, class Finish, class... X>
-static int cell_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t live, uint32_t depth, typename Op::T* out,
-                           int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms, MakePlan&& make_plan, Bulk&& bulk,
-                           Staged&& staged, First&& first, Finish&& finish, X... x) {
-    typedef typename Op::T T;
-    const PlaneLayout L(cubes, nq, popc32(ops) * depth, popc32(live & ~ops) * depth);
-    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(T), out_mem == DCDF_MEM_DEVICE);
-    Plan P(reduce_slab_cells());
-    int rc = make_plan(P, W.base.data(), L.sbase.data());
-    if (rc != DCDF_OK) return rc;
-    DevBuf d_scr;
-    RegionRun R;
-    rc = R.begin(W, stats, P.stats);
-    if (rc != DCDF_OK || R.nothing) return rc;
-    T* const d_dst = (T*)W.dst();
-    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(T)));
-    rc = R.upload(P);
-    if (rc == DCDF_OK) rc = staged(P);
-    if (rc == DCDF_OK) rc = R.start();
-    if (rc == DCDF_OK) rc = first(P, d_dst, d_scr.as<T>());
-    if (rc != DCDF_OK) return rc;
-    for (const SegRange& g : P.ranges) {
-        rc = R.fold_consts<k_cell_fold<Op, X...>, typename Op::Piece>(r, g, 16, d_dst, d_scr.as<T>(), ops, x...);
-        if (rc == DCDF_OK) rc = bulk(R.units, g, d_dst, d_scr.as<T>());
-        if (rc == DCDF_OK) rc = R.walk.run<k_cell_fold<Op, X...>>(r, P.walk, g, 16, d_dst, d_scr.as<T>(), ops, x...);
-        if (rc != DCDF_OK) return rc;
-    }
-    rc = finish(P, d_dst, d_scr.as<T>());
-    return rc == DCDF_OK ? R.end(W, true, kernel_ms) : rc;
-}
-// k_reduce_mean over the cubes of a plan (reduce_time, reduce_time_groups)
-static int launch_reduce_mean(const DevBuf& d_means, const std::vector<MeanPiece>& means, double* d_dst, double* d_scr, uint32_t ops) {
-    if (!(ops & ROP_MEAN)) return DCDF_OK;
-    uint64_t big = 0;
-    for (const MeanPiece& m : means) big = std::max(big, m.psz);
-    hipLaunchKernelGGL(k_reduce_mean, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(means.size(), 65535)), dim3(256),
-                       0, 0, d_means.as<MeanPiece>(), (uint32_t)means.size(), d_dst, d_scr, ops);
-    K2R_HIP(hipGetLastError());
-    return DCDF_OK;
-}
-// per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h); SUM / COUNT kept for MEAN alone are the
-// scratch planes
-extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
-                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
-    if (rc != DCDF_OK || nq == 0) return rc;
-    DevBuf d_means;
-    return cell_fold_batch<ReduceCell, TimePlan>(
-        r, cubes, nq, ops, reduce_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms,
-        [&](TimePlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_reduce_time(r->plan(), cubes, nq, base, sbase, r->all_node, P); },
-        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
-            return launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                      d_dst, d_scr, ops);
-        },
-        [&](const TimePlan& P) {
-            if (ops & ROP_MEAN) K2R_HIP(upload(d_means, P.means));
-            return (int)DCDF_OK;
-        },
-        [](const TimePlan&, double*, double*) { return (int)DCDF_OK; },
-        [&](const TimePlan& P, double* d_dst, double* d_scr) { return launch_reduce_mean(d_means, P.means, d_dst, d_scr, ops); });
-}
-// reduce_time's statistics per cell and group of a per-instant label array (k2r_group.h).  The labels of all cubes that write
-// something go to the device once, one cube after the other; the arrays [n_groups][rows][cols] are filled with the identities
-// before the first segment (k_group_fill), so every piece continues what the planes hold.
-extern "C" int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
-                                                    const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
-                                                    const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
-    const bool own = ops != 0 && ops <= (RA_ALL | ROP_MEAN) && n_groups >= 1 && n_groups <= 65535 && (nq == 0 || (labels && label_offset));
-    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
-    if (rc != DCDF_OK || nq == 0) return rc;
-    // the device label array: the instants of every cube that has cells, in batch order
-    std::vector<uint64_t> loff(nq, 0);
-    std::vector<uint16_t> lab;
-    for (size_t q = 0; q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (cube_cells(c) == 0) continue;
-        loff[q] = lab.size();
-        lab.insert(lab.end(), labels + label_offset[q], labels + label_offset[q] + (c.end - c.start));
-    }
-    DevBuf d_means, d_labels;
-    if (!lab.empty()) K2R_HIP(d_labels.alloc_pooled(lab.size() * sizeof(uint16_t)));  // (its address is a launch argument below)
-    return cell_fold_batch<GroupCell, GroupPlan>(
-        r, cubes, nq, ops, reduce_live(ops), n_groups, out, out_mem, out_offset, stats, kernel_ms,
-        [&](GroupPlan& P, const uint64_t* base, const uint64_t* sbase) {
-            return plan_reduce_time_groups(r->plan(), cubes, nq, loff.data(), n_groups, base, sbase, r->all_node, P);
-        },
-        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
-            return launch_bulk_group(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<GroupUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                     d_labels.as<uint16_t>(), n_groups, d_dst, d_scr, ops);
-        },
-        [&](const GroupPlan& P) {
-            K2R_HIP(hipMemcpy(d_labels.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            K2R_HIP(upload(d_means, P.means));  // (the fill runs over them whatever `ops`)
-            return (int)DCDF_OK;
-        },
-        [&](const GroupPlan& P, double* d_dst, double* d_scr) {
-            uint64_t big = 0;
-            for (const MeanPiece& m : P.means) big = std::max(big, m.psz);
-            hipLaunchKernelGGL(k_group_fill, dim3((uint32_t)std::min<uint64_t>((big + 255) / 256, 2048), (uint32_t)std::min<size_t>(P.means.size(), 65535)),
-                               dim3(256), 0, 0, d_means.as<MeanPiece>(), (uint32_t)P.means.size(), d_dst, d_scr, ops);
-            K2R_HIP(hipGetLastError());
-            return (int)DCDF_OK;
-        },
-        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_reduce_mean(d_means, P.means, d_dst, d_scr, ops); },
-        (const uint16_t*)d_labels.as<uint16_t>(), n_groups);
-}
 // A kernel over the cubes' arrays of a plan (P.means), a row of workgroups per cube: the fills and the finishing kernels.
 template <auto Kernel, class... Args>
 static int launch_over_means(const DevBuf& d_means, const std::vector<MeanPiece>& means, Args... args) {
@@ -529,42 +417,151 @@ static int launch_over_means(const DevBuf& d_means, const std::vector<MeanPiece>
     K2R_HIP(hipGetLastError());
     return DCDF_OK;
 }
+// What a call hands to cell_fold_batch: the raster, the cubes, `ops`, and its own steps -- make_plan(P, base, sbase) fills the Plan
+// (a SegmentPlan), bulk(units, g, d_dst, d_scr) launches the bulk kernel over range g's units -- and, where it needs them, its own
+//   staged(P)                     uploads what else the call's launches read, before the events
+//   first(P, d_dst, d_scr)        launches what precedes the first segment
+//   finish(P, d_dst, d_scr)       launches what follows the last segment
+template <class Plan_, class T>
+struct CellFoldCall {
+    typedef Plan_ Plan;
+    const dcdf_raster* r;
+    const dcdf_cube* cubes;
+    size_t nq;
+    uint32_t ops;
+    int staged(const Plan&) { return DCDF_OK; }
+    int first(const Plan&, T*, T*) { return DCDF_OK; }
+    int finish(const Plan&, T*, T*) { return DCDF_OK; }
+};
+// What follows region_begin in the five calls.  live: the states the call carries, `ops` and those kept for another's sake.
+// depth: the [rows][cols] planes of one state (the grouped calls: their groups); x: what k_cell_fold hands to Op besides the
+// planes.  Per segment: the elided folds, the bulk units, the walk's slabs -- a segment's pieces share no cell.
+template <class Op, class Call, class... X>
+static int cell_fold_batch(Call& call, uint32_t live, uint32_t depth, typename Op::T* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                           float* kernel_ms, X... x) {
+    typedef typename Op::T T;
+    const uint32_t ops = call.ops;
+    const PlaneLayout L(call.cubes, call.nq, popc32(ops) * depth, popc32(live & ~ops) * depth);
+    WindowOut W(L.planes.data(), call.nq, out, out_offset, sizeof(T), out_mem == DCDF_MEM_DEVICE);
+    typename Call::Plan P(reduce_slab_cells());
+    int rc = call.make_plan(P, W.base.data(), L.sbase.data());
+    if (rc != DCDF_OK) return rc;
+    DevBuf d_scr;
+    RegionRun R;
+    rc = R.begin(W, stats, P.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
+    T* const d_dst = (T*)W.dst();
+    if (L.scr_total) K2R_HIP(d_scr.alloc_pooled(L.scr_total * sizeof(T)));
+    rc = R.upload(P);
+    if (rc == DCDF_OK) rc = call.staged(P);
+    if (rc == DCDF_OK) rc = R.start();
+    if (rc == DCDF_OK) rc = call.first(P, d_dst, d_scr.as<T>());
+    if (rc != DCDF_OK) return rc;
+    for (const SegRange& g : P.ranges) {
+        rc = R.fold_consts<k_cell_fold<Op, X...>, typename Op::Piece>(call.r, g, 16, d_dst, d_scr.as<T>(), ops, x...);
+        if (rc == DCDF_OK) rc = call.bulk(R.units, g, d_dst, d_scr.as<T>());
+        if (rc == DCDF_OK) rc = R.walk.run<k_cell_fold<Op, X...>>(call.r, P.walk, g, 16, d_dst, d_scr.as<T>(), ops, x...);
+        if (rc != DCDF_OK) return rc;
+    }
+    rc = call.finish(P, d_dst, d_scr.as<T>());
+    return rc == DCDF_OK ? R.end(W, true, kernel_ms) : rc;
+}
+// per-cell min / max / sum / count / mean of the values decode returns (k2r_reduce.h); SUM / COUNT kept for MEAN alone: scratch planes
+struct ReduceTimeCall : CellFoldCall<TimePlan, double> {
+    DevBuf d_means;
+    int make_plan(TimePlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_reduce_time(r->plan(), cubes, nq, base, sbase, r->all_node, P); }
+    int bulk(const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
+        return launch_bulk_reduce(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<ReduceUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst,
+                                  d_scr, ops);
+    }
+    int staged(const TimePlan& P) { return ops & ROP_MEAN ? upload_some(d_means, P.means) : (int)DCDF_OK; }
+    int finish(const TimePlan& P, double* d_dst, double* d_scr) {
+        return ops & ROP_MEAN ? launch_over_means<k_reduce_mean>(d_means, P.means, d_dst, d_scr, ops) : (int)DCDF_OK;
+    }
+};
+extern "C" int dcdf_raster_reduce_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, double* out, int out_mem,
+                                             const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, ops != 0 && ops <= (RA_ALL | ROP_MEAN), ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    ReduceTimeCall call{{r, cubes, nq, ops}};
+    return cell_fold_batch<ReduceCell>(call, reduce_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms);
+}
+// ---- the grouped folds: reduce_time_groups, moments_time and moments_time_groups ----------------------------------------------
+// One path: the grouped reduce's plan (plan_reduce_time_groups) and records; the arrays [n_groups][rows][cols] of every state
+// filled before the first segment, so every piece continues what the planes hold; a finishing kernel behind the last.
+// The device label array (gather_time_labels, k2r_plan.h): allocated before the plan -- its address is a launch argument --,
+// copied in one piece in the staged step.  Labels given, yet no cube has cells: nothing is planned and dev() is never read.
+struct TimeLabels {
+    std::vector<uint64_t> loff;
+    std::vector<uint16_t> lab;
+    DevBuf d_copy;
+    int alloc(const dcdf_cube* cubes, size_t nq, const uint16_t* labels, const uint64_t* label_offset) {
+        gather_time_labels(cubes, nq, labels, label_offset, loff, lab);
+        if (!lab.empty()) K2R_HIP(d_copy.alloc_pooled(lab.size() * sizeof(uint16_t)));
+        return DCDF_OK;
+    }
+    const uint16_t* dev() const { return lab.empty() ? nullptr : d_copy.as<uint16_t>(); }
+    int copy() const {
+        if (!lab.empty()) K2R_HIP(hipMemcpy(d_copy.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        return DCDF_OK;
+    }
+};
+// Bulk: the statistic's bulk launcher; Fill: the kernel of its states' identities, over P.means whatever `ops`; finishing(d_means,
+// means, d_dst, d_scr): what makes the planes that are no state.
+template <auto Bulk, auto Fill, class Finish>
+struct GroupedCall : CellFoldCall<GroupPlan, double> {
+    uint32_t n_groups;
+    Finish finishing;
+    TimeLabels labels;
+    DevBuf d_means;
+    int make_plan(GroupPlan& P, const uint64_t* base, const uint64_t* sbase) {
+        return plan_reduce_time_groups(r->plan(), cubes, nq, labels.loff.data(), n_groups, base, sbase, r->all_node, P);
+    }
+    int bulk(const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
+        return Bulk(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<GroupUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), labels.dev(), n_groups,
+                    d_dst, d_scr, ops);
+    }
+    int staged(const GroupPlan& P) {
+        const int rc = labels.copy();
+        return rc == DCDF_OK ? upload_some(d_means, P.means) : rc;
+    }
+    int first(const GroupPlan& P, double* d_dst, double* d_scr) { return launch_over_means<Fill>(d_means, P.means, d_dst, d_scr, ops); }
+    int finish(const GroupPlan& P, double* d_dst, double* d_scr) { return finishing(d_means, P.means, d_dst, d_scr); }
+};
+template <class Op, auto Bulk, auto Fill, class Finish>
+static int grouped_fold_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t live, const uint16_t* labels,
+                              const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                              float* kernel_ms, Finish finishing) {
+    GroupedCall<Bulk, Fill, Finish> call{{r, cubes, nq, ops}, n_groups, finishing};
+    const int rc = call.labels.alloc(cubes, nq, labels, label_offset);
+    if (rc != DCDF_OK) return rc;
+    return cell_fold_batch<Op>(call, live, n_groups, out, out_mem, out_offset, stats, kernel_ms, call.labels.dev(), n_groups);
+}
+// reduce_time's statistics per cell and group of a per-instant label array (k2r_group.h): the identities by k_group_fill, MEAN
+// by k_reduce_mean
+extern "C" int dcdf_raster_reduce_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const uint16_t* labels,
+                                                    const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                                                    const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const bool own = ops != 0 && ops <= (RA_ALL | ROP_MEAN) && n_groups >= 1 && n_groups <= 65535 && (nq == 0 || (labels && label_offset));
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return grouped_fold_batch<GroupCell, launch_bulk_group, k_group_fill>(
+        r, cubes, nq, ops, reduce_live(ops), labels, label_offset, n_groups, out, out_mem, out_offset, stats, kernel_ms,
+        [ops](const DevBuf& d_means, const std::vector<MeanPiece>& means, double* d_dst, double* d_scr) {
+            return ops & ROP_MEAN ? launch_over_means<k_reduce_mean>(d_means, means, d_dst, d_scr, ops) : (int)DCDF_OK;
+        });
+}
 // Per-cell count, mean, variance and standard deviation over time (k2r_moment.h), per group of a per-instant label array or --
-// labels == nullptr: the ungrouped call -- as one group every instant belongs to.  One path: the grouped reduce's plan
-// (plan_reduce_time_groups) and records, the four state arrays filled before the first segment (k_moment_fill), MEAN / VAR / STD
-// made by k_moment_finish behind the last; ddof goes there only.
+// labels == nullptr: the ungrouped call -- as one group every instant belongs to.  The four state arrays by k_moment_fill, MEAN /
+// VAR / STD by k_moment_finish; ddof goes there only.
 static int moments_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof, const uint16_t* labels,
                          const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
                          float* kernel_ms) {
-    // the device label array: the instants of every cube that has cells, in batch order
-    std::vector<uint64_t> loff(nq, 0);
-    std::vector<uint16_t> lab;
-    for (size_t q = 0; labels && q < nq; q++) {
-        const dcdf_cube c = norm_cube(cubes[q]);
-        if (cube_cells(c) == 0) continue;
-        loff[q] = lab.size();
-        lab.insert(lab.end(), labels + label_offset[q], labels + label_offset[q] + (c.end - c.start));
-    }
-    DevBuf d_means, d_labels;
-    if (!lab.empty()) K2R_HIP(d_labels.alloc_pooled(lab.size() * sizeof(uint16_t)));  // (its address is a launch argument below)
-    const uint16_t* const d_lab = lab.empty() ? nullptr : d_labels.as<uint16_t>();
-    // (labels given, yet no cube has cells: nothing is planned and d_lab is never read)
-    return cell_fold_batch<MomentCell, GroupPlan>(
-        r, cubes, nq, ops, MS_ALL, n_groups, out, out_mem, out_offset, stats, kernel_ms,
-        [&](GroupPlan& P, const uint64_t* base, const uint64_t* sbase) {
-            return plan_reduce_time_groups(r->plan(), cubes, nq, loff.data(), n_groups, base, sbase, r->all_node, P);
-        },
-        [&](const DevBuf& units, const SegRange& g, double* d_dst, double* d_scr) {
-            return launch_bulk_moment(r->d_refs.as<ChunkRef>(), r->d_enc.as<uint8_t>(), units.as<GroupUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0),
-                                      d_lab, n_groups, d_dst, d_scr, ops);
-        },
-        [&](const GroupPlan& P) {
-            if (!lab.empty()) K2R_HIP(hipMemcpy(d_labels.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            return upload_some(d_means, P.means);
-        },
-        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_over_means<k_moment_fill>(d_means, P.means, d_dst, d_scr, ops); },
-        [&](const GroupPlan& P, double* d_dst, double* d_scr) { return launch_over_means<k_moment_finish>(d_means, P.means, d_dst, d_scr, ops, ddof); },
-        d_lab, n_groups);
+    return grouped_fold_batch<MomentCell, launch_bulk_moment, k_moment_fill>(
+        r, cubes, nq, ops, MS_ALL, labels, label_offset, n_groups, out, out_mem, out_offset, stats, kernel_ms,
+        [ops, ddof](const DevBuf& d_means, const std::vector<MeanPiece>& means, double* d_dst, double* d_scr) {
+            return launch_over_means<k_moment_finish>(d_means, means, d_dst, d_scr, ops, ddof);
+        });
 }
 extern "C" int dcdf_raster_moments_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t ddof, double* out, int out_mem,
                                               const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
@@ -599,20 +596,21 @@ extern "C" int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, doubl
 }
 // per cell, the hits of a value range over time and their runs (k2r_spell.h); cur, and LONGEST kept for LONGEST_START alone, are
 // the scratch planes
+struct SpellsCall : CellFoldCall<SpellPlan, uint32_t> {
+    const double *lower, *upper;
+    int make_plan(SpellPlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_spells(r->plan(), cubes, lower, upper, nq, base, sbase, r->all_node, P); }
+    int bulk(const DevBuf& units, const SegRange& g, uint32_t* d_dst, uint32_t* d_scr) {
+        return launch_bulk_spell(r->d_refs.as<ChunkRef>(), units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr, ops);
+    }
+};
 extern "C" int dcdf_raster_spells_batch(const dcdf_raster* r, const dcdf_cube* cubes, const double* lower, const double* upper, size_t nq,
                                         uint32_t ops, uint32_t* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
     bool own = ops != 0 && ops <= SP_ALL && (nq == 0 || (lower && upper));
     for (size_t q = 0; own && q < nq && q <= 0x7fffffffu; q++) own = lower[q] == lower[q] && upper[q] == upper[q];  // a NaN bound
     const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, EXACT_FLOATS, stats, kernel_ms);
     if (rc != DCDF_OK || nq == 0) return rc;
-    return cell_fold_batch<SpellCell, SpellPlan>(
-        r, cubes, nq, ops, spell_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms,
-        [&](SpellPlan& P, const uint64_t* base, const uint64_t* sbase) { return plan_spells(r->plan(), cubes, lower, upper, nq, base, sbase, r->all_node, P); },
-        [&](const DevBuf& units, const SegRange& g, uint32_t* d_dst, uint32_t* d_scr) {
-            return launch_bulk_spell(r->d_refs.as<ChunkRef>(), units.as<SpellUnit>() + g.unit0, (uint32_t)(g.unit1 - g.unit0), d_dst, d_scr, ops);
-        },
-        [](const SpellPlan&) { return (int)DCDF_OK; }, [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; },
-        [](const SpellPlan&, uint32_t*, uint32_t*) { return (int)DCDF_OK; });
+    SpellsCall call{{r, cubes, nq, ops}, lower, upper};
+    return cell_fold_batch<SpellCell>(call, spell_live(ops), 1, out, out_mem, out_offset, stats, kernel_ms);
 }
 // ---- quantiles over time: per cell, order statistics of the values decode returns (k2r_quantile.h) ----------------------------
 // The plan is plan_quantile_time's (k2r_plan.h): the cubes in columns, the columns in bands of a bounded slab.  A band: its

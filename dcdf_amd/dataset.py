@@ -385,9 +385,24 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
             from .raster import EncodedRaster
-            names = EncodedRaster.reduce_ops(ops)[1]
-            return {n: np.full((bottom - top, right - left), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+            return EncodedRaster._nothing("reduce_time", EncodedRaster.reduce_ops(ops)[1], (bottom - top, right - left))
         return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
+
+    @staticmethod
+    def _dense_labels(labels, shape, what, noun, extent, none):
+        """Any integer ids of `shape`, negative = none, as (ids, dense): ids the distinct non-negative ones ascending, dense the uint16
+        labels of the raster's calls -- the place of every id in ids, `none` for a negative one.  what: the call's name; noun: "group"
+        or "zone"; extent: "instants" or "window"."""
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.shape != shape:
+            raise ValueError("%s: the labels are %s %r, the %s integers %r" % (what, lab.dtype, lab.shape, extent, shape))
+        inside = lab >= 0
+        ids, inv = np.unique(lab[inside], return_inverse=True)
+        if ids.size > 65535:
+            raise ValueError("%s: %d distinct %s ids, at most 65535" % (what, ids.size, noun))
+        dense = np.full(lab.shape, none, dtype=np.uint16)
+        dense[inside] = inv.astype(np.uint16)
+        return ids, dense
 
     def reduce_time_groups(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """reduce_time per group of instants -- monthly means from daily data (labels = np.arange(T) // 30), a climatology (labels =
@@ -400,17 +415,9 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         from . import _lib
         from .raster import EncodedRaster
         names = EncodedRaster.reduce_ops(ops)[1]
-        lab = np.asarray(labels)
-        if lab.dtype.kind not in "iu" or lab.shape != (stop - start,):
-            raise ValueError("reduce_time_groups: the labels are %s %r, the instants integers %r" % (lab.dtype, lab.shape, (stop - start,)))
-        inside = lab >= 0
-        ids, inv = np.unique(lab[inside], return_inverse=True)
-        if ids.size > 65535:
-            raise ValueError("reduce_time_groups: %d distinct group ids, at most 65535" % ids.size)
+        ids, dense = Variable._dense_labels(labels, (stop - start,), "reduce_time_groups", "group", "instants", _lib.GROUP_NONE)
         if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
-            return ids, EncodedRaster._groups_none(names, ids.size, bottom - top, right - left)
-        dense = np.full(lab.shape, _lib.GROUP_NONE, dtype=np.uint16)
-        dense[inside] = inv.astype(np.uint16)
+            return ids, EncodedRaster._nothing("reduce_time", names, (ids.size, bottom - top, right - left))
         return ids, self.raster().reduce_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size)
 
     def moments_time(self, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
@@ -427,7 +434,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         names = EncodedRaster.moment_ops(ops)[1]
         ddof = EncodedRaster._ddof(ddof)
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            return EncodedRaster._moments_none(names, (bottom - top, right - left))
+            return EncodedRaster._nothing("moments_time", names, (bottom - top, right - left))
         return self.raster().moments_time(ops, start, stop, window=(top, bottom, left, right), ddof=ddof)
 
     def moments_time_groups(self, labels, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
@@ -442,17 +449,9 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         from .raster import EncodedRaster
         names = EncodedRaster.moment_ops(ops)[1]
         ddof = EncodedRaster._ddof(ddof)
-        lab = np.asarray(labels)
-        if lab.dtype.kind not in "iu" or lab.shape != (stop - start,):
-            raise ValueError("moments_time_groups: the labels are %s %r, the instants integers %r" % (lab.dtype, lab.shape, (stop - start,)))
-        inside = lab >= 0
-        ids, inv = np.unique(lab[inside], return_inverse=True)
-        if ids.size > 65535:
-            raise ValueError("moments_time_groups: %d distinct group ids, at most 65535" % ids.size)
+        ids, dense = Variable._dense_labels(labels, (stop - start,), "moments_time_groups", "group", "instants", _lib.GROUP_NONE)
         if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
-            return ids, EncodedRaster._moments_none(names, (ids.size, bottom - top, right - left))
-        dense = np.full(lab.shape, _lib.GROUP_NONE, dtype=np.uint16)
-        dense[inside] = inv.astype(np.uint16)
+            return ids, EncodedRaster._nothing("moments_time", names, (ids.size, bottom - top, right - left))
         return ids, self.raster().moments_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size, ddof=ddof)
 
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
@@ -466,7 +465,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         from .raster import EncodedRaster
         if start == stop:  # (no instants, possibly none stored yet: nothing to open)
             EncodedRaster._spell_bounds(lower, upper, 1)
-            return EncodedRaster._spells_none(EncodedRaster.spell_ops(ops)[1], bottom - top, right - left)
+            return EncodedRaster._nothing("spells", EncodedRaster.spell_ops(ops)[1], (bottom - top, right - left))
         return self.raster().spells(lower, upper, ops, start, stop, window=(top, bottom, left, right))
 
     def quantile_time(self, probs, start=0, stop=None, top=0, bottom=None, left=0, right=None, method="linear"):
@@ -506,20 +505,9 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         from . import _lib
         from .raster import EncodedRaster
         names = EncodedRaster.reduce_ops(ops)[1]
-        lab = np.asarray(labels)
-        if lab.dtype.kind not in "iu" or lab.shape != (bottom - top, right - left):
-            raise ValueError("zonal: the labels are %s %r, the window integers %r" % (lab.dtype, lab.shape, (bottom - top, right - left)))
-        inside = lab >= 0
-        ids, inv = np.unique(lab[inside], return_inverse=True)
-        if ids.size > 65535:
-            raise ValueError("zonal: %d distinct zone ids, at most 65535" % ids.size)
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            return ids, {n: np.empty((ids.size, 0), dtype=np.float64) for n in names}
-        if ids.size == 0:
-            nan = {"sum": 0.0, "count": 0.0}
-            return ids, {n: np.full((0, stop - start), nan.get(n, np.nan)) for n in names}
-        dense = np.full(lab.shape, _lib.ZONE_NONE, dtype=np.uint16)
-        dense[inside] = inv.astype(np.uint16)
+        ids, dense = Variable._dense_labels(labels, (bottom - top, right - left), "zonal", "zone", "window", _lib.ZONE_NONE)
+        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no zone)
+            return ids, EncodedRaster._nothing("reduce_time", names, (ids.size, stop - start))
         return ids, self.raster().zonal(ops, dense, start, stop, window=(top, bottom, left, right), n_zones=ids.size)
 
     def histogram(self, edges, start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):

@@ -210,22 +210,67 @@ class EncodedRaster:
         (top, bottom, left, right).  Without instants: NaN planes, count 0 and sum 0."""
         start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.reduce_ops(ops)
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            return {n: np.full((rows, cols), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+        shape = (bottom - top, right - left)
+        if start == stop or shape[0] * shape[1] == 0:
+            return self._nothing("reduce_time", names, shape)
         out, _, _, _ = self.reduce_time_flat([[start, stop, top, bottom, left, right]], mask)
-        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+        return self._cut(out, names, shape)
+
+    # what a statistic holds where nothing was read -- no instant, no cell, no group or zone --, typed as its arrays are
+    _NOTHING = {
+        "reduce_time": dict(min=np.float64("nan"), max=np.float64("nan"), sum=np.float64(0), count=np.float64(0), mean=np.float64("nan")),
+        "moments_time": dict(count=np.float64(0), mean=np.float64("nan"), var=np.float64("nan"), std=np.float64("nan")),
+        "spells": dict(count=np.uint32(0), longest=np.uint32(0), longest_start=np.uint32(L.SPELL_NONE), first=np.uint32(L.SPELL_NONE),
+                       last=np.uint32(L.SPELL_NONE)),
+    }
 
     @staticmethod
-    def _n_groups(n_groups, what="reduce_time_groups"):
-        n_groups = int(n_groups)
-        if not 1 <= n_groups <= 65535:
-            raise ValueError("%s: n_groups %d outside 1 .. 65535" % (what, n_groups))
-        return n_groups
+    def _nothing(what, names, shape):
+        """{name: array of `shape`} of the statistics `names` of reduce_time / moments_time / spells over nothing"""
+        fill = EncodedRaster._NOTHING[what]
+        return {n: np.full(shape, fill[n], dtype=fill[n].dtype) for n in names}
 
     @staticmethod
-    def _groups_none(names, n_groups, rows, cols):
-        return {n: np.full((n_groups, rows, cols), 0.0 if n in ("sum", "count") else np.nan) for n in names}
+    def _cut(out, names, shape):
+        """one cube's flat result as {name: array of `shape`}, the arrays one after the other in the order of `names`"""
+        n = int(np.prod(shape, dtype=np.int64))
+        return {name: out[i * n:(i + 1) * n].reshape(shape) for i, name in enumerate(names)}
+
+    @staticmethod
+    def _n_groups(n, what="reduce_time_groups", noun="n_groups", lab=None, none=L.GROUP_NONE):
+        """n_groups / n_zones, 1 .. 65535; None: the largest label of `lab`, `none` apart, plus 1 (at least 1)"""
+        if n is None:
+            named = lab[lab != none]
+            n = int(named.max()) + 1 if named.size else 1
+        n = int(n)
+        if not 1 <= n <= 65535:
+            raise ValueError("%s: %s %d outside 1 .. 65535" % (what, noun, n))
+        return n
+
+    def _group_labels(self, labels, nt, n_groups, what):
+        """(labels, n_groups) of a whole-raster grouped method over nt instants: uint16 [nt]; n_groups by _n_groups"""
+        lab = np.asarray(labels)
+        if lab.dtype != np.uint16 or lab.shape != (nt,):
+            raise ValueError("%s: the labels are %s %r, the instants uint16 %r" % (what, lab.dtype, lab.shape, (nt,)))
+        return lab, self._n_groups(n_groups, what, lab=lab)
+
+    def _time_labels(self, q, labels, what):
+        """The label arguments of the grouped calls over time for the cubes q -- one uint16 array [instants] per cube, on the host --:
+        (pointer, offsets, what must stay alive over the call)."""
+        labels = list(labels)
+        if len(labels) != len(q):
+            raise ValueError("%s: %d label arrays for %d cubes" % (what, len(labels), len(q)))
+        nt = self._extent(q, 0)
+        parts = []
+        for i, m in enumerate(labels):
+            m = np.asarray(m)
+            if m.dtype != np.uint16:
+                raise ValueError("%s: labels %d are %s, not uint16" % (what, i, m.dtype))
+            if m.shape != (int(nt[i]),):
+                raise ValueError("%s: labels %d have shape %r, their cube %d instants" % (what, i, m.shape, int(nt[i])))
+            parts.append(m)
+        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
+        return l_ptr, l_off, keep
 
     def reduce_time_groups_flat(self, cubes, ops, labels, n_groups, out_device_ptr=None, out_offset=None):
         """reduce_time_flat's statistics per cell and group of instants, of dataset-level cubes [n, 6] through
@@ -240,19 +285,7 @@ class EncodedRaster:
         mask, names = self.reduce_ops(ops)
         n_groups = self._n_groups(n_groups)
         q = self._cubes(cubes)
-        labels = list(labels)
-        if len(labels) != len(q):
-            raise ValueError("reduce_time_groups: %d label arrays for %d cubes" % (len(labels), len(q)))
-        nt = self._extent(q, 0)
-        parts = []
-        for i, m in enumerate(labels):
-            m = np.asarray(m)
-            if m.dtype != np.uint16:
-                raise ValueError("reduce_time_groups: labels %d are %s, not uint16" % (i, m.dtype))
-            if m.shape != (int(nt[i]),):
-                raise ValueError("reduce_time_groups: labels %d have shape %r, their cube %d instants" % (i, m.shape, int(nt[i])))
-            parts.append(m)
-        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
+        l_ptr, l_off, keep = self._time_labels(q, labels, "reduce_time_groups")
         return self._region_call("reduce_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
                                  lambda n, out, mem, off, stats: (n, C.c_uint32(mask), l_ptr, l_off, C.c_uint32(n_groups), out, mem, off, stats),
                                  out_device_ptr=out_device_ptr, out_offset=out_offset)
@@ -264,19 +297,12 @@ class EncodedRaster:
         1).  Without instants or cells: NaN planes, count 0 and sum 0, of that shape."""
         start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.reduce_ops(ops)
-        lab = np.asarray(labels)
-        if lab.dtype != np.uint16 or lab.shape != (stop - start,):
-            raise ValueError("reduce_time_groups: the labels are %s %r, the instants uint16 %r" % (lab.dtype, lab.shape, (stop - start,)))
-        if n_groups is None:
-            named = lab[lab != L.GROUP_NONE]
-            n_groups = int(named.max()) + 1 if named.size else 1
-        n_groups = self._n_groups(n_groups)
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            return self._groups_none(names, n_groups, rows, cols)
+        lab, n_groups = self._group_labels(labels, stop - start, n_groups, "reduce_time_groups")
+        shape = (n_groups, bottom - top, right - left)
+        if start == stop or shape[1] * shape[2] == 0:
+            return self._nothing("reduce_time", names, shape)
         out, _, _, _ = self.reduce_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups)
-        n = n_groups * rows * cols
-        return {name: out[i * n:(i + 1) * n].reshape(n_groups, rows, cols) for i, name in enumerate(names)}
+        return self._cut(out, names, shape)
 
     @staticmethod
     def moment_ops(ops):
@@ -292,10 +318,6 @@ class EncodedRaster:
         if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or ddof not in (0, 1):
             raise ValueError("moments_time: ddof %r is neither 0 nor 1" % (ddof,))
         return int(ddof)
-
-    @staticmethod
-    def _moments_none(names, shape):
-        return {n: np.full(shape, 0.0 if n == "count" else np.nan) for n in names}
 
     def moments_time_flat(self, cubes, ops, ddof=0, out_device_ptr=None, out_offset=None):
         """Per-cell count, mean, variance and standard deviation over time of dataset-level cubes [n, 6] through
@@ -320,11 +342,11 @@ class EncodedRaster:
         start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.moment_ops(ops)
         ddof = self._ddof(ddof)
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            return self._moments_none(names, (rows, cols))
+        shape = (bottom - top, right - left)
+        if start == stop or shape[0] * shape[1] == 0:
+            return self._nothing("moments_time", names, shape)
         out, _, _, _ = self.moments_time_flat([[start, stop, top, bottom, left, right]], mask, ddof)
-        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+        return self._cut(out, names, shape)
 
     def moments_time_groups_flat(self, cubes, ops, labels, n_groups, ddof=0, out_device_ptr=None, out_offset=None):
         """moments_time_flat's statistics per cell and group of instants through dcdf_raster_moments_time_groups_batch: one walk of
@@ -337,19 +359,7 @@ class EncodedRaster:
         ddof = self._ddof(ddof)
         n_groups = self._n_groups(n_groups, "moments_time_groups")
         q = self._cubes(cubes)
-        labels = list(labels)
-        if len(labels) != len(q):
-            raise ValueError("moments_time_groups: %d label arrays for %d cubes" % (len(labels), len(q)))
-        nt = self._extent(q, 0)
-        parts = []
-        for i, m in enumerate(labels):
-            m = np.asarray(m)
-            if m.dtype != np.uint16:
-                raise ValueError("moments_time_groups: labels %d are %s, not uint16" % (i, m.dtype))
-            if m.shape != (int(nt[i]),):
-                raise ValueError("moments_time_groups: labels %d have shape %r, their cube %d instants" % (i, m.shape, int(nt[i])))
-            parts.append(m)
-        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
+        l_ptr, l_off, keep = self._time_labels(q, labels, "moments_time_groups")
         return self._region_call("moments_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
                                  lambda n, out, mem, off, stats: (n, C.c_uint32(mask), C.c_uint32(ddof), l_ptr, l_off, C.c_uint32(n_groups), out, mem,
                                                                   off, stats),
@@ -363,19 +373,12 @@ class EncodedRaster:
         start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.moment_ops(ops)
         ddof = self._ddof(ddof)
-        lab = np.asarray(labels)
-        if lab.dtype != np.uint16 or lab.shape != (stop - start,):
-            raise ValueError("moments_time_groups: the labels are %s %r, the instants uint16 %r" % (lab.dtype, lab.shape, (stop - start,)))
-        if n_groups is None:
-            named = lab[lab != L.GROUP_NONE]
-            n_groups = int(named.max()) + 1 if named.size else 1
-        n_groups = self._n_groups(n_groups, "moments_time_groups")
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            return self._moments_none(names, (n_groups, rows, cols))
+        lab, n_groups = self._group_labels(labels, stop - start, n_groups, "moments_time_groups")
+        shape = (n_groups, bottom - top, right - left)
+        if start == stop or shape[1] * shape[2] == 0:
+            return self._nothing("moments_time", names, shape)
         out, _, _, _ = self.moments_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups, ddof)
-        n = n_groups * rows * cols
-        return {name: out[i * n:(i + 1) * n].reshape(n_groups, rows, cols) for i, name in enumerate(names)}
+        return self._cut(out, names, shape)
 
     @staticmethod
     def spell_ops(ops):
@@ -408,10 +411,6 @@ class EncodedRaster:
                                  lambda n, out, mem, off, stats: (C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), n, C.c_uint32(mask), out, mem,
                                                                   off, stats), out_device_ptr=out_device_ptr, out_offset=out_offset)
 
-    @staticmethod
-    def _spells_none(names, rows, cols):
-        return {n: np.full((rows, cols), 0 if n in ("count", "longest") else L.SPELL_NONE, dtype=np.uint32) for n in names}
-
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, window=None):
         """{statistic: ndarray [rows, cols] uint32} of the hits of [lower, upper] over the instants [start, stop) of the whole
         raster, or of `window` = (top, bottom, left, right); instants are counted from `start`.  Without instants: zeros for count
@@ -419,11 +418,11 @@ class EncodedRaster:
         start, stop, top, bottom, left, right = self._window_args(start, stop, window)
         mask, names = self.spell_ops(ops)
         self._spell_bounds(lower, upper, 1)
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            return self._spells_none(names, rows, cols)
+        shape = (bottom - top, right - left)
+        if start == stop or shape[0] * shape[1] == 0:
+            return self._nothing("spells", names, shape)
         out, _, _, _ = self.spells_flat([[start, stop, top, bottom, left, right]], lower, upper, mask)
-        return {n: out[i * rows * cols:(i + 1) * rows * cols].reshape(rows, cols) for i, n in enumerate(names)}
+        return self._cut(out, names, shape)
 
     @staticmethod
     def _probs(probs, method):
@@ -547,7 +546,7 @@ class EncodedRaster:
         if nt == 0:
             return {n: np.empty(0, dtype=np.float64) for n in names}
         out, _, _, _ = self.reduce_space_flat([[start, stop, top, bottom, left, right]], bits, None if mask is None else [mask])
-        return {n: out[i * nt:(i + 1) * nt] for i, n in enumerate(names)}
+        return self._cut(out, names, (nt,))
 
     @staticmethod
     def _label_args(q, labels, what):
@@ -584,9 +583,7 @@ class EncodedRaster:
         in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
         leaves."""
         mask, names = self.reduce_ops(ops)
-        n_zones = int(n_zones)
-        if not 1 <= n_zones <= 65535:
-            raise ValueError("zonal: n_zones %d outside 1 .. 65535" % n_zones)
+        n_zones = self._n_groups(n_zones, "zonal", "n_zones")
         q = self._cubes(cubes)
         l_ptr, l_off, l_mem, keep, _ = self._label_args(q, labels, "zonal")
         return self._region_call("zonal", q, lambda: self._extent(q, 0) * (len(names) * n_zones), np.float64,
@@ -603,17 +600,12 @@ class EncodedRaster:
         lab = np.asarray(labels)
         if lab.dtype != np.uint16 or lab.shape != (bottom - top, right - left):
             raise ValueError("zonal: the labels are %s %r, the window uint16 %r" % (lab.dtype, lab.shape, (bottom - top, right - left)))
-        if n_zones is None:
-            named = lab[lab != L.ZONE_NONE]
-            n_zones = int(named.max()) + 1 if named.size else 1
-        n_zones = int(n_zones)
-        if not 1 <= n_zones <= 65535:
-            raise ValueError("zonal: n_zones %d outside 1 .. 65535" % n_zones)
+        n_zones = self._n_groups(n_zones, "zonal", "n_zones", lab, L.ZONE_NONE)
         nt = stop - start
         if nt == 0:
             return {n: np.empty((n_zones, 0), dtype=np.float64) for n in names}
         out, _, _, _ = self.zonal_flat([[start, stop, top, bottom, left, right]], bits, [lab], n_zones)
-        return {n: out[i * n_zones * nt:(i + 1) * n_zones * nt].reshape(n_zones, nt) for i, n in enumerate(names)}
+        return self._cut(out, names, (n_zones, nt))
 
     @staticmethod
     def _edges(edges):
@@ -656,44 +648,35 @@ class EncodedRaster:
         out, _, _, _ = self.histogram_flat([[start, stop, top, bottom, left, right]], e, None if mask is None else [mask])
         return out[:nt * bins].reshape(nt, bins)
 
-    def search_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
-        """search of dataset-level cubes through dcdf_raster_search_batch: returns (triples uint32[hits, 3] in raster coordinates
-        -- or None when they stay on the device --, offsets, counts, kernel ms)."""
+    def _search(self, entry, cubes, bounds, out_device_ptr, cap):
+        """dcdf_<entry> over the cubes [n, 6]; bounds(n) = the (lower, upper) arrays of the entry's type.  Returns (triples uint32[hits,
+        3] in raster coordinates -- or None when they stay on the device --, offsets, counts, kernel ms)."""
         q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        lo = np.ascontiguousarray(np.asarray(lower, dtype=np.int64))
-        hi = np.ascontiguousarray(np.asarray(upper, dtype=np.int64))
+        lo, hi = (np.ascontiguousarray(b) for b in bounds(len(q)))
         counts = np.zeros(len(q), dtype=np.uint64)
         offs = np.zeros(len(q), dtype=np.uint64)
         if cap is None:
             cap = int(np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).sum())
         ms = C.c_float()
         trip = None if out_device_ptr else np.empty((max(cap, 1), 3), dtype=np.uint32)
-        L.check(L.lib().dcdf_raster_search_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
-                                                 C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)),
-                                                 C.c_void_p(out_device_ptr or trip.ctypes.data), C.c_size_t(cap),
-                                                 L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.c_void_p(counts.ctypes.data),
-                                                 C.c_void_p(offs.ctypes.data), C.byref(ms)), "raster_search_batch")
+        L.check(getattr(L.lib(), "dcdf_" + entry)(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
+                                                 C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)), C.c_void_p(out_device_ptr or trip.ctypes.data),
+                                                 C.c_size_t(cap), L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.c_void_p(counts.ctypes.data),
+                                                 C.c_void_p(offs.ctypes.data), C.byref(ms)), entry)
         return trip, offs, counts, ms.value
+
+    def search_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
+        """search of dataset-level cubes through dcdf_raster_search_batch: returns (triples uint32[hits, 3] in raster coordinates
+        -- or None when they stay on the device --, offsets, counts, kernel ms)."""
+        return self._search("raster_search_batch", cubes, lambda n: (np.asarray(lower, dtype=np.int64), np.asarray(upper, dtype=np.int64)),
+                            out_device_ptr, cap)
 
     def search_values_flat(self, cubes, lower, upper, out_device_ptr=None, cap=None):
         """Value search of dataset-level cubes through dcdf_raster_search_values_batch: real-valued [lower, upper] per cube,
         translated on the device per piece with the piece's chunk's encoding and fractional bits.  Returns what search_flat
         returns (triples uint32[hits, 3] in raster coordinates or None, offsets, counts, kernel ms)."""
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
-        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (len(q),)))
-        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (len(q),)))
-        counts = np.zeros(len(q), dtype=np.uint64)
-        offs = np.zeros(len(q), dtype=np.uint64)
-        if cap is None:
-            cap = int(np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).sum())
-        ms = C.c_float()
-        trip = None if out_device_ptr else np.empty((max(cap, 1), 3), dtype=np.uint32)
-        L.check(L.lib().dcdf_raster_search_values_batch(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
-                                                        C.c_void_p(hi.ctypes.data), C.c_size_t(len(q)),
-                                                        C.c_void_p(out_device_ptr or trip.ctypes.data), C.c_size_t(cap),
-                                                        L.MEM_DEVICE if out_device_ptr else L.MEM_HOST, C.c_void_p(counts.ctypes.data),
-                                                        C.c_void_p(offs.ctypes.data), C.byref(ms)), "raster_search_values_batch")
-        return trip, offs, counts, ms.value
+        return self._search("raster_search_values_batch", cubes,
+                            lambda n: (np.broadcast_to(np.asarray(b, dtype=np.float64), (n,)) for b in (lower, upper)), out_device_ptr, cap)
 
     def get_flat(self, points, dtype=np.int64, out_device_ptr=None):
         """Dataset-level points [n, 3] of (instant, row, col) through dcdf_raster_get_batch (Superchunk::get, superchunk.rs:313-352),

@@ -7,6 +7,11 @@
 // apart from group_step -- per group, the plain scan of its sub-series --, bit for bit, and nothing outside the cell's elements
 // is touched.  The values make the order of a sum observable.  Prints "ok cuts <count>".
 //
+// With "--gather": the label gather of the grouped calls (gather_time_labels) over a batch of five cubes -- with cells, without
+// instants, with zero rows, with reversed bounds, with cells --, each cube's labels at its own offset of an exactly sized array,
+// against a naive loop; the labels of a cube without cells lie outside the array and must not be read.  Null labels yield nothing.
+// Prints "ok gather".
+//
 // With the name of a file of cases: prints every list of plan_reduce_time_groups as the entry point would upload it.
 //   case:  T R C tile cs  step(64 | 32)  slab_cap  n_groups
 //          n_leaves, then per leaf: row0 col0 enc fbits elided bulk_ok
@@ -112,6 +117,36 @@ static uint64_t check_cuts() {
     return n;
 }
 
+// ---- the label gather ------------------------------------------------------------------------------------------------------------
+static void check_gather() {
+    //                       start end top bottom left right
+    const dcdf_cube cubes[5] = {{2, 7, 0, 3, 1, 4}, {4, 4, 0, 3, 0, 3}, {1, 5, 2, 2, 0, 3}, {9, 6, 5, 1, 8, 2}, {0, 1, 0, 1, 0, 1}};
+    const uint64_t offset[5] = {4, 9, 1000000, 0, 3};  // cube 3's three labels, cube 4's one, cube 0's five; cube 2's are nowhere
+    std::vector<uint16_t> labels(9);
+    for (size_t i = 0; i < labels.size(); i++) labels[i] = (uint16_t)(100 + 7 * i);
+    labels[8] = GROUP_NONE;
+    // the naive loop: the cubes that have cells, their |end - start| labels each, in batch order
+    std::vector<uint64_t> want_off(5, 0);
+    std::vector<uint16_t> want;
+    for (size_t q = 0; q < 5; q++) {
+        const dcdf_cube& c = cubes[q];
+        const uint64_t nt = c.start < c.end ? c.end - c.start : c.start - c.end, rows = c.top < c.bottom ? c.bottom - c.top : c.top - c.bottom,
+                       cols = c.left < c.right ? c.right - c.left : c.left - c.right;
+        if (nt * rows * cols == 0) continue;
+        want_off[q] = want.size();
+        for (uint64_t i = 0; i < nt; i++) want.push_back(labels[offset[q] + i]);
+    }
+    CHECK(want.size() == 9 && want_off[3] == 5 && want_off[4] == 8);
+    std::vector<uint64_t> loff(3, 77);  // (what an earlier call left)
+    std::vector<uint16_t> lab(2, 5);
+    gather_time_labels(cubes, 5, labels.data(), offset, loff, lab);
+    CHECK(loff == want_off && lab == want);
+    gather_time_labels(cubes, 5, nullptr, nullptr, loff, lab);
+    CHECK(loff == std::vector<uint64_t>(5, 0) && lab.empty());
+    gather_time_labels(cubes, 0, labels.data(), offset, loff, lab);
+    CHECK(loff.empty() && lab.empty());
+}
+
 // ---- the plan --------------------------------------------------------------------------------------------------------------------
 static void put(const char* tag, std::initializer_list<uint64_t> v) {
     std::printf("%s", tag);
@@ -172,6 +207,11 @@ static int dump_plans(const char* path) {
 }
 
 int main(int argc, char** argv) {
+    if (argc == 2 && !std::strcmp(argv[1], "--gather")) {
+        check_gather();
+        std::printf("ok gather\n");
+        return 0;
+    }
     if (argc == 2) return dump_plans(argv[1]);
     if (argc != 1) return 2;
     std::printf("ok cuts %" PRIu64 "\n", check_cuts());

@@ -252,6 +252,46 @@ def test_both_output_forms(rasters):
         assert (g[~inside] == -77.25).all() and (~inside).sum() >= 3 * len(cubes)  # nothing is written outside a cube's planes
 
 
+def test_batch_with_cubes_that_write_nothing(rasters):
+    """[cube with cells, cube without instants, cube without cells, cube with cells], every cube with a label array of its own: the
+    labels of the two that write nothing are the caller's alone, so the last cube's lie elsewhere on the device than on the host."""
+    from dcdf_amd.encoder import DeviceBuffer
+    a, R = rasters("f32")
+    cubes = [CUBES[1], [6, 6, 0, 30, 0, 30], [2, 9, 40, 40, 3, 50], [19, 1, 66, 2, 69, 4]]
+    i = np.arange(20)
+    labels = [(i[:16] % 3).astype(np.uint16), np.zeros(0, dtype=np.uint16), np.full(7, 1, dtype=np.uint16), (2 - i[:18] // 7).astype(np.uint16)]
+    labels[3][[0, 11]] = NONE
+    ops = ALL
+    nb = np.array([RT.norm(c) for c in cubes], dtype=np.int64)
+    for n_groups in (None, 3):
+        if n_groups is None:
+            call = lambda **kw: R.moments_time_flat(cubes, ops, 1, **kw)
+        else:
+            call = lambda **kw: R.moments_time_groups_flat(cubes, ops, labels, n_groups, 1, **kw)
+        flat, off, _, stats = call()
+        for q in (0, 3):
+            c = cubes[q]
+            want = MM.moments_time(sub(a, c), 1) if n_groups is None else MM.moments_time_groups(sub(a, c), labels[q], n_groups, 1)
+            check(flat, off, q, ops, c, want, n_groups)
+        vol = (4 * (n_groups or 1) * (nb[:, 3] - nb[:, 2]) * (nb[:, 5] - nb[:, 4]) * (nb[:, 1] > nb[:, 0])).astype(np.uint64)
+        assert vol[1] == 0 and vol[2] == 0 and vol[0] and vol[3]
+        np.testing.assert_array_equal(off, np.concatenate([[0], np.cumsum(vol)[:-1]]).astype(np.uint64))
+        doff = np.concatenate([[5], 5 + np.cumsum(vol + 3)[:-1]]).astype(np.uint64)
+        total = int(doff[-1] + vol[-1]) + 7
+        buf = DeviceBuffer(total * 8)
+        buf.write(0, np.full(total, -77.25, dtype=np.float64))
+        ms, dvstats = call(out_device_ptr=buf.ptr, out_offset=doff)
+        g = buf.read(0, total * 8, np.float64)
+        buf.free()
+        np.testing.assert_array_equal(dvstats, stats)
+        inside = np.zeros(total, dtype=bool)
+        for q in range(len(cubes)):
+            o, n = int(doff[q]), int(vol[q])
+            inside[o:o + n] = True
+            assert_same(g[o:o + n], flat[int(off[q]):int(off[q]) + n])
+        assert (g[~inside] == -77.25).all() and (~inside).sum() >= 3 * len(cubes)  # nothing is written outside a cube's planes
+
+
 def test_small_fold_slabs(rasters, monkeypatch):
     """The fallback walk's slab capped at two instants of the raster (the cap is read on every call): pieces cut in time inside a
     segment, same bits."""

@@ -207,8 +207,8 @@ class FakeRaster:
     def __init__(self, a):
         from dcdf_amd.raster import EncodedRaster
         self.a, self.shape, self.calls = a, a.shape, []
-        for name in ("_cubes", "_extent", "_planes", "_window_args", "_n_groups", "_moments_none", "_ddof", "_host_arrays", "_ops", "moment_ops",
-                     "moments_time_flat", "moments_time", "moments_time_groups_flat", "moments_time_groups"):
+        for name in ("_cubes", "_extent", "_planes", "_window_args", "_n_groups", "_group_labels", "_time_labels", "_nothing", "_cut", "_ddof",
+                     "_host_arrays", "_ops", "moment_ops", "moments_time_flat", "moments_time", "moments_time_groups_flat", "moments_time_groups"):
             f = EncodedRaster.__dict__[name]
             setattr(self, name, f.__func__ if isinstance(f, staticmethod) else f.__get__(self))
 

@@ -1,5 +1,5 @@
 """Grouped reduce over time without a GPU: the model, the Python wrappers' argument checks, and tests/sim/group_check.cpp -- a
-stand-alone program built with AddressSanitizer and UBSan -- for the merge-on-change step and the planner.  The plan's records are
+stand-alone program built with AddressSanitizer and UBSan -- for the merge-on-change step, the label gather and the planner.  The plan's records are
 painted as tests/test_raster_plan_host.py paints reduce_time's: every record says what it reads (leaf, instants, a rectangle) and
 where group 0's cell of it lies in the cube's arrays."""
 import os
@@ -60,8 +60,8 @@ class FakeRaster:
     def __init__(self, a):
         from dcdf_amd.raster import EncodedRaster
         self.a, self.shape, self.calls = a, a.shape, []
-        for name in ("_cubes", "_extent", "_planes", "_window_args", "_n_groups", "_groups_none", "_host_arrays", "reduce_ops",
-                     "reduce_time_groups_flat", "reduce_time_groups"):
+        for name in ("_cubes", "_extent", "_planes", "_window_args", "_n_groups", "_group_labels", "_time_labels", "_nothing", "_cut",
+                     "_host_arrays", "reduce_ops", "reduce_time_groups_flat", "reduce_time_groups"):
             f = EncodedRaster.__dict__[name]
             setattr(self, name, f.__func__ if isinstance(f, staticmethod) else f.__get__(self))
 
@@ -170,6 +170,12 @@ def test_merge_on_change_equals_the_model_at_every_cut(exe):
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     full = 1 + sum(3 ** n * 2 ** (n - 1) for n in range(1, 9))
     assert out.stdout.split()[:2] == ["ok", "cuts"] and int(out.stdout.split()[2]) > full
+
+
+def test_label_gather_in_the_sanitized_program(exe):
+    """gather_time_labels over five cubes -- two of them without cells, their labels outside the array -- and without labels."""
+    out = subprocess.run([exe, "--gather"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.split() == ["ok", "gather"], (out.stdout + out.stderr)[-3000:]
 
 
 WIDTHS = dict(unit=16, cfold=14, wfold=14, item=8, slab=4, range=6, mean=3)
