@@ -1291,6 +1291,14 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
 
     for (uint32_t inst = i_begin; inst < i_end && status == ST_OK; inst++) {
         const bool have_s = inst > 0;
+        // The snapshot side of the tree top (smin / smax of heights 3..H) cannot change while the block's snapshot stands: it is
+        // built by the first instant this workgroup compares with that snapshot -- the one right behind it, or the first of a
+        // continuation part, whose snapshot another workgroup encoded -- and only read by the block's other instants.
+#ifndef K2R_NO_SNAP_ONCE
+        const bool s_build = inst == s_idx + 1 || (cont && inst == i_begin);
+#else
+        const bool s_build = true;
+#endif
         // ================= phase 1: stream the tile in 4x4 sub-blocks; thread-local counts ==============
         // Nothing but four per-height-2 summaries survives this phase in registers: cells are re-read on
         // demand at emission, and only under visited subtrees (sparse for logs).
@@ -1446,8 +1454,10 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             if (store) {
                 sh.tmin[B] = mn3;
                 sh.tmax[B] = mx3;
-                sh.smin[B] = smn3t;
-                sh.smax[B] = smx3t;
+                if (s_build) {  // (the same values as the general form's below: the block's other instants read either's)
+                    sh.smin[B] = smn3t;
+                    sh.smax[B] = smx3t;
+                }
                 sh.diff[B] = dref - s_base;
                 sh.eq[B] = Zb == 0 ? 1u : 0u;
                 sh.lq[B][0] = 0;
@@ -1747,8 +1757,10 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
                 // needs a third byte; otherwise the exact classes_pass is requested (bit 60 of the top pack)
                 const int32_t lo_b = mn3 - smx3, hi_b = mx3 - smn3;
                 wide = (lo_b < -32768 || hi_b > 32767) ? 1u : 0u;
-                sh.smin[tid] = smn3;
-                sh.smax[tid] = smx3;
+                if (s_build) {  // (the same values as lean_block_out's: the block's other instants read either's)
+                    sh.smin[tid] = smn3;
+                    sh.smax[tid] = smx3;
+                }
                 sh.diff[tid] = df2_0;
                 sh.eq[tid] = eq3 ? 1u : 0u;
             }
@@ -1783,8 +1795,10 @@ K2R_HD void encode_chunk(EX& ex, const TileArgs& ta, TileResult* res, uint64_t* 
             sh.tmin[a] = min4(sh.tmin[c], sh.tmin[c + 1], sh.tmin[c + 2], sh.tmin[c + 3]);
             sh.tmax[a] = max4(sh.tmax[c], sh.tmax[c + 1], sh.tmax[c + 2], sh.tmax[c + 3]);
             if (have_s) {
-                sh.smin[a] = min4(sh.smin[c], sh.smin[c + 1], sh.smin[c + 2], sh.smin[c + 3]);
-                sh.smax[a] = max4(sh.smax[c], sh.smax[c + 1], sh.smax[c + 2], sh.smax[c + 3]);
+                if (s_build) {  // (from height 3 as phase 1 left it, in either form; kept for the block's other instants)
+                    sh.smin[a] = min4(sh.smin[c], sh.smin[c + 1], sh.smin[c + 2], sh.smin[c + 3]);
+                    sh.smax[a] = max4(sh.smax[c], sh.smax[c + 1], sh.smax[c + 2], sh.smax[c + 3]);
+                }
                 const int32_t d0 = sh.diff[c];
                 sh.diff[a] = d0;
                 sh.eq[a] = (sh.eq[c] & sh.eq[c + 1] & sh.eq[c + 2] & sh.eq[c + 3]) && d0 == sh.diff[c + 1] && d0 == sh.diff[c + 2] &&
