@@ -27,6 +27,7 @@ import numpy as np
 
 from . import _lib
 from . import chunk as _chunk
+from . import raster as _raster
 from .chunk import Chunk, Cube
 from .superchunk import Superchunk
 
@@ -382,11 +383,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         values window() returns widened to float64, NaN cells skipped; the sum is sequential in instant order.  Through
         raster().reduce_time: the encoded bytes are read once on the GPU and only the planes are written
         (dcdf_raster_reduce_time_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            from .raster import EncodedRaster
-            return EncodedRaster._nothing("reduce_time", EncodedRaster.reduce_ops(ops)[1], (bottom - top, right - left))
-        return self.raster().reduce_time(ops, start, stop, window=(top, bottom, left, right))
+        return Variable._statistic(self, _raster._ReduceTime, (ops,), (), start, stop, top, bottom, left, right)
 
     @staticmethod
     def _dense_labels(labels, shape, what, noun, extent, none):
@@ -404,6 +401,27 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         dense[inside] = inv.astype(np.uint16)
         return ids, dense
 
+    def _statistic(self, stat, own, arrays, start, stop, top, bottom, left, right, labels=None):
+        """The Variable form of every region statistic (stat: its description in raster.py, own / arrays: its arguments as
+        EncodedRaster._whole takes them): the region, checked; then raster()'s whole-raster form -- or, without instants (possibly
+        none stored yet: nothing to open), the own checks and the statistic's fill.  labels: the ids of a grouped call, made the
+        raster's dense labels here; it returns (ids, arrays), the fill too where no id is in a group or zone.  (Called through the
+        class: the methods also serve objects that borrow them.)"""
+        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
+        nt, rows, cols = stop - start, bottom - top, right - left
+        window = (top, bottom, left, right)
+        if labels is None:
+            if nt == 0:
+                S = stat.unread(own, arrays, nt, rows, cols)
+                return S.nothing(S.shape(nt, rows, cols))
+            return self.raster()._whole(stat, own, arrays, start, stop, window)
+        S = stat(*own)
+        ids, dense = Variable._dense_labels(labels, S.labelled(nt, rows, cols), S.name, S.noun, S.extent, S.none)
+        S.n = ids.size
+        if nt == 0 or S.n == 0:
+            return ids, S.nothing(S.shape(nt, rows, cols))
+        return ids, self.raster()._whole(stat, own, (dense, S.n), start, stop, window)
+
     def reduce_time_groups(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """reduce_time per group of instants -- monthly means from daily data (labels = np.arange(T) // 30), a climatology (labels =
         np.arange(T) % 12): `labels` is any integer array [stop - start] of group ids, negative = no group.  Returns (ids, {name:
@@ -411,14 +429,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         array is reduce_time over the instants labelled ids[i] (the sum sequential in instant order; a cell without a value in the
         group gets NaN, NaN, +0.0, 0, NaN).  More than 65535 distinct ids: ValueError.  Through raster().reduce_time_groups: the
         encoded bytes are read once on the GPU whatever the number of groups (dcdf_raster_reduce_time_groups_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from . import _lib
-        from .raster import EncodedRaster
-        names = EncodedRaster.reduce_ops(ops)[1]
-        ids, dense = Variable._dense_labels(labels, (stop - start,), "reduce_time_groups", "group", "instants", _lib.GROUP_NONE)
-        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
-            return ids, EncodedRaster._nothing("reduce_time", names, (ids.size, bottom - top, right - left))
-        return ids, self.raster().reduce_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size)
+        return Variable._statistic(self, _raster._ReduceTimeGroups, (ops,), (), start, stop, top, bottom, left, right, labels)
 
     def moments_time(self, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
         """Per-cell count, mean, variance and standard deviation over the instants [start, stop) of the window [top, bottom) x
@@ -429,13 +440,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         cell has var exactly 0 and mean exactly its value; a cell without a value gets 0, NaN, NaN, NaN.  Through
         raster().moments_time: the encoded bytes are read once on the GPU and only the planes are written
         (dcdf_raster_moments_time_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from .raster import EncodedRaster
-        names = EncodedRaster.moment_ops(ops)[1]
-        ddof = EncodedRaster._ddof(ddof)
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            return EncodedRaster._nothing("moments_time", names, (bottom - top, right - left))
-        return self.raster().moments_time(ops, start, stop, window=(top, bottom, left, right), ddof=ddof)
+        return Variable._statistic(self, _raster._MomentsTime, (ops, ddof), (), start, stop, top, bottom, left, right)
 
     def moments_time_groups(self, labels, ops=("mean", "std"), start=0, stop=None, top=0, bottom=None, left=0, right=None, ddof=0):
         """moments_time per group of instants -- mean and std per month of the year for standardised anomalies (labels =
@@ -444,15 +449,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         plane i of every array is moments_time over the instants labelled ids[i], in order (a cell without a value in the group
         gets 0, NaN, NaN, NaN).  More than 65535 distinct ids: ValueError.  Through raster().moments_time_groups: the encoded
         bytes are read once on the GPU whatever the number of groups (dcdf_raster_moments_time_groups_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from . import _lib
-        from .raster import EncodedRaster
-        names = EncodedRaster.moment_ops(ops)[1]
-        ddof = EncodedRaster._ddof(ddof)
-        ids, dense = Variable._dense_labels(labels, (stop - start,), "moments_time_groups", "group", "instants", _lib.GROUP_NONE)
-        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no group)
-            return ids, EncodedRaster._nothing("moments_time", names, (ids.size, bottom - top, right - left))
-        return ids, self.raster().moments_time_groups(ops, dense, start, stop, window=(top, bottom, left, right), n_groups=ids.size, ddof=ddof)
+        return Variable._statistic(self, _raster._MomentsTimeGroups, (ops, ddof), (), start, stop, top, bottom, left, right, labels)
 
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
@@ -461,12 +458,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         rule: NaN never hits, +-inf is unbounded); count = the hits, longest = the longest unbroken run of hits, longest_start =
         where the first such run began, first / last = the first / last hit; SPELL_NONE (0xffffffff) where nothing hit.  Through
         raster().spells: the encoded bytes are read once on the GPU and only the planes are written (dcdf_raster_spells_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from .raster import EncodedRaster
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            EncodedRaster._spell_bounds(lower, upper, 1)
-            return EncodedRaster._nothing("spells", EncodedRaster.spell_ops(ops)[1], (bottom - top, right - left))
-        return self.raster().spells(lower, upper, ops, start, stop, window=(top, bottom, left, right))
+        return Variable._statistic(self, _raster._Spells, (ops,), (lower, upper), start, stop, top, bottom, left, right)
 
     def quantile_time(self, probs, start=0, stop=None, top=0, bottom=None, left=0, right=None, method="linear"):
         """Per-cell quantiles over the instants [start, stop) of the window [top, bottom) x [left, right): ndarray [n_probs, rows,
@@ -474,13 +466,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         -- numpy.nanquantile(window, probs, axis=0) for method "linear"; "lower", "higher" and "nearest" pick a value of the series
         itself.  Exact; NaN where a cell has no value.  Through raster().quantile_time: the cube is decoded band by band into a
         bounded device buffer and only the planes are written (dcdf_raster_quantile_time_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            from .raster import EncodedRaster
-            p, _, scalar = EncodedRaster._probs(probs, method)
-            out = np.full((p.size, bottom - top, right - left), np.nan)
-            return out[0] if scalar else out
-        return self.raster().quantile_time(probs, start, stop, window=(top, bottom, left, right), method=method)
+        return Variable._statistic(self, _raster._QuantileTime, (probs, method), (), start, stop, top, bottom, left, right)
 
     def reduce_space(self, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
         """Per-instant statistics over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
@@ -488,11 +474,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         the names of `ops`, over the values window() returns widened to float64, NaN cells skipped; the sum is the exact sum
         rounded once (math.fsum).  Through raster().reduce_space: the encoded bytes are read once on the GPU and only the series
         are written (dcdf_raster_reduce_space_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            from .raster import EncodedRaster
-            return {n: np.empty(0, dtype=np.float64) for n in EncodedRaster.reduce_ops(ops)[1]}
-        return self.raster().reduce_space(ops, start, stop, window=(top, bottom, left, right), mask=mask)
+        return Variable._statistic(self, _raster._ReduceSpace, (ops,), (mask,), start, stop, top, bottom, left, right)
 
     def zonal(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-zone, per-instant statistics over the window [top, bottom) x [left, right): `labels` is any integer array [rows,
@@ -501,14 +483,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         reduce_space's for the zone's cells (the sum exact, rounded once; a zone whose cells are all NaN gets NaN, NaN, +0.0, 0,
         NaN).  More than 65535 distinct ids: ValueError.  Through raster().zonal: the encoded bytes are read once on the GPU
         whatever the number of zones (dcdf_raster_zonal_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from . import _lib
-        from .raster import EncodedRaster
-        names = EncodedRaster.reduce_ops(ops)[1]
-        ids, dense = Variable._dense_labels(labels, (bottom - top, right - left), "zonal", "zone", "window", _lib.ZONE_NONE)
-        if start == stop or ids.size == 0:  # (no instants, possibly none stored yet: nothing to open; or no zone)
-            return ids, EncodedRaster._nothing("reduce_time", names, (ids.size, stop - start))
-        return ids, self.raster().zonal(ops, dense, start, stop, window=(top, bottom, left, right), n_zones=ids.size)
+        return Variable._statistic(self, _raster._Zonal, (ops,), (), start, stop, top, bottom, left, right, labels)
 
     def histogram(self, edges, start=0, stop=None, top=0, bottom=None, left=0, right=None, mask=None):
         """Per-instant value histogram over the cells of the window [top, bottom) x [left, right) -- those whose `mask` entry
@@ -516,14 +491,7 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         number of values window() returns, widened to float64, in every bin of `edges` (bins + 1 increasing values; edges[b] <= x
         < edges[b + 1], the last bin closed, NaN cells and values outside the edges counted nowhere).  Through raster().histogram:
         the encoded bytes are read once on the GPU and only the counts are written (dcdf_raster_histogram_batch)."""
-        stop, bottom, right = self._region(start, stop, top, bottom, left, right)
-        from .raster import EncodedRaster
-        e = EncodedRaster._edges(edges)
-        if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
-            raise ValueError("histogram: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
-        if start == stop:  # (no instants, possibly none stored yet: nothing to open)
-            return np.zeros((0, e.size - 1), dtype=np.uint64)
-        return self.raster().histogram(e, start, stop, window=(top, bottom, left, right), mask=mask)
+        return Variable._statistic(self, _raster._Histogram, (edges,), (mask,), start, stop, top, bottom, left, right)
 
     def search(self, start, stop, top, bottom, left, right, lower, upper):
         """(instant, row, col) of the cells with lower <= stored value <= upper (mmarray.rs:206; span.rs:231-270): not in
@@ -600,7 +568,6 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         cached = self.__dict__.get("_raster_cache")
         if cached is not None:
             return cached
-        from .raster import EncodedRaster, RasterTile
         T, R, Cc = self.shape
         if T == 0:
             raise ValueError("raster(): the variable holds no instants yet")
@@ -610,9 +577,9 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
             if a0 != 0 or (n != self.chunk_size and i != len(segs) - 1) or n > self.chunk_size:
                 raise ValueError("raster(): segment %d holds %d instants, not chunk_size %d" % (i, n, self.chunk_size))
         leaf, grid = leaf_grid(self._resolver.objects, [s[0] for s in segs], self._k2_levels, self._round is not None)
-        tiles = [RasterTile(None if lf.cid is None else self._resolver.node(lf.cid), lf.row0, lf.col0, lf.values, lf.minmax, lf.encoding,
+        tiles = [_raster.RasterTile(None if lf.cid is None else self._resolver.node(lf.cid), lf.row0, lf.col0, lf.values, lf.minmax, lf.encoding,
                             lf.fractional_bits, lf.exact) for g in grid for lf in g]
-        r = EncodedRaster.from_tiles((T, R, Cc), tiles, leaf, self.chunk_size)
+        r = _raster.EncodedRaster.from_tiles((T, R, Cc), tiles, leaf, self.chunk_size)
         self.__dict__["_raster_cache"] = r
         return r
 

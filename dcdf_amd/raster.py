@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .chunk import _ENC
 
 # One leaf of a raster over stored Superchunks (dcdf_raster_tile): chunk = an opened dcdf_amd.Chunk, or None for an elided leaf
 # whose value per instant is `values`; (row0, col0) = where the leaf starts inside its chunk; minmax = [instants, 2] stored
@@ -135,7 +136,6 @@ class EncodedRaster:
         """fill_window of dataset-level cubes [n, 6] through dcdf_raster_fill_window_batch.  Host form: returns (flat array of
         dtype, offsets uint64[n], kernel ms): window q is flat[offsets[q]:] shaped (t, r, c).  Device form (out_device_ptr +
         out_offset in elements): the windows are written there, returns kernel ms."""
-        from .chunk import _ENC
         q = self._cubes(cubes)
         dtype = np.dtype(dtype)
         res = self._region_call("fill_window", q, lambda: self._extent(q, 0) * self._extent(q, 2) * self._extent(q, 4), dtype,
@@ -148,7 +148,6 @@ class EncodedRaster:
         bit, decoded block by block (meant for whole tiles and long time ranges).  Host form: returns (flat array of dtype,
         offsets uint64[n], kernel ms, stats); device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).
         stats = uint64[3]: cells written by the bulk kernel, by the fallback walk, by the elided fill."""
-        from .chunk import _ENC
         q = self._cubes(cubes)
         dtype = np.dtype(dtype)
         return self._region_call("decode", q, lambda: self._extent(q, 0) * self._extent(q, 2) * self._extent(q, 4), dtype,
@@ -157,15 +156,32 @@ class EncodedRaster:
 
     def decode(self, start=0, stop=None, dtype=np.int64):
         """The instants [start, stop) of the whole raster, decompressed: ndarray [stop - start, rows, cols] of dtype."""
-        T, R, Cc = self.shape
-        stop = T if stop is None else int(stop)
-        start = int(start)
-        if not 0 <= start <= stop <= T:
-            raise ValueError("instants [%d, %d) outside [0, %d)" % (start, stop, T))
+        start, stop, _, R, _, Cc = self._window_args(start, stop, None)
         if start == stop:
             return np.empty((0, R, Cc), dtype=np.dtype(dtype))
         out, _, _, _ = self.decode_flat([[start, stop, 0, R, 0, Cc]], dtype)
         return out[:(stop - start) * R * Cc].reshape(stop - start, R, Cc)
+
+    # ---- the region statistics: what each one is stands once, in its description below this class; these are the drivers ---------
+    def _flat(self, S, cubes, *arrays, out_device_ptr=None, out_offset=None):
+        """The flat form of every region statistic.  S: its description, holding the call's own arguments; arrays: what it takes
+        per cube (labels, masks, bounds), staged against the cubes by S.flat.  Returns what _region_call returns, in either form."""
+        q = S.flat(cubes, *arrays)
+        return self._region_call(S.name, q, lambda: S.count(q), S.dtype, S.args, zeroed=S.zeroed, out_device_ptr=out_device_ptr,
+                                 out_offset=out_offset)
+
+    def _whole(self, stat, own, arrays, start, stop, window):
+        """The whole-raster form of every region statistic: the instants and the window (_window_args), the statistic's own
+        arguments (stat(*own)), its arrays against the window (window()); then its fill where there is nothing to read -- no
+        instant, or for a statistic over time no cell --, else the flat form over one cube, cut into the result's arrays."""
+        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
+        S = stat(*own)
+        nt, rows, cols = stop - start, bottom - top, right - left
+        arrays = S.window(nt, rows, cols, *arrays)
+        shape = S.shape(nt, rows, cols)
+        if nt == 0 or (S.over_time and rows * cols == 0):
+            return S.nothing(shape)
+        return S.cut(self._flat(S, [[start, stop, top, bottom, left, right]], *arrays)[0], shape)
 
     @staticmethod
     def _ops(ops, table, what):
@@ -188,10 +204,6 @@ class EncodedRaster:
         iterable of "min" / "max" / "sum" / "count" / "mean"."""
         return EncodedRaster._ops(ops, L.REDUCE_OPS, "reduce_time")
 
-    def _planes(self, q, n):
-        """elements of n [rows, cols] planes per cube (a cube without instants writes nothing)"""
-        return np.where(q[:, 1] == q[:, 0], 0, self._extent(q, 2) * self._extent(q, 4) * n)
-
     def reduce_time_flat(self, cubes, ops, out_device_ptr=None, out_offset=None):
         """Per-cell statistics over time of dataset-level cubes [n, 6] through dcdf_raster_reduce_time_batch: cube q yields one
         [rows, cols] float64 plane per statistic of `ops` (reduce_ops), in the order min, max, sum, count, mean, over the values
@@ -199,78 +211,12 @@ class EncodedRaster:
         float64 array, offsets uint64[n], kernel ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device
         form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk
         kernel, by the fallback walk, from elided leaves."""
-        mask, names = self.reduce_ops(ops)
-        q = self._cubes(cubes)
-        return self._region_call("reduce_time", q, lambda: self._planes(q, len(names)), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), out, mem, off, stats), out_device_ptr=out_device_ptr,
-                                 out_offset=out_offset)
+        return self._flat(_ReduceTime(ops), cubes, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def reduce_time(self, ops, start=0, stop=None, window=None):
         """{statistic: ndarray [rows, cols] float64} over the instants [start, stop) of the whole raster, or of `window` =
         (top, bottom, left, right).  Without instants: NaN planes, count 0 and sum 0."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        mask, names = self.reduce_ops(ops)
-        shape = (bottom - top, right - left)
-        if start == stop or shape[0] * shape[1] == 0:
-            return self._nothing("reduce_time", names, shape)
-        out, _, _, _ = self.reduce_time_flat([[start, stop, top, bottom, left, right]], mask)
-        return self._cut(out, names, shape)
-
-    # what a statistic holds where nothing was read -- no instant, no cell, no group or zone --, typed as its arrays are
-    _NOTHING = {
-        "reduce_time": dict(min=np.float64("nan"), max=np.float64("nan"), sum=np.float64(0), count=np.float64(0), mean=np.float64("nan")),
-        "moments_time": dict(count=np.float64(0), mean=np.float64("nan"), var=np.float64("nan"), std=np.float64("nan")),
-        "spells": dict(count=np.uint32(0), longest=np.uint32(0), longest_start=np.uint32(L.SPELL_NONE), first=np.uint32(L.SPELL_NONE),
-                       last=np.uint32(L.SPELL_NONE)),
-    }
-
-    @staticmethod
-    def _nothing(what, names, shape):
-        """{name: array of `shape`} of the statistics `names` of reduce_time / moments_time / spells over nothing"""
-        fill = EncodedRaster._NOTHING[what]
-        return {n: np.full(shape, fill[n], dtype=fill[n].dtype) for n in names}
-
-    @staticmethod
-    def _cut(out, names, shape):
-        """one cube's flat result as {name: array of `shape`}, the arrays one after the other in the order of `names`"""
-        n = int(np.prod(shape, dtype=np.int64))
-        return {name: out[i * n:(i + 1) * n].reshape(shape) for i, name in enumerate(names)}
-
-    @staticmethod
-    def _n_groups(n, what="reduce_time_groups", noun="n_groups", lab=None, none=L.GROUP_NONE):
-        """n_groups / n_zones, 1 .. 65535; None: the largest label of `lab`, `none` apart, plus 1 (at least 1)"""
-        if n is None:
-            named = lab[lab != none]
-            n = int(named.max()) + 1 if named.size else 1
-        n = int(n)
-        if not 1 <= n <= 65535:
-            raise ValueError("%s: %s %d outside 1 .. 65535" % (what, noun, n))
-        return n
-
-    def _group_labels(self, labels, nt, n_groups, what):
-        """(labels, n_groups) of a whole-raster grouped method over nt instants: uint16 [nt]; n_groups by _n_groups"""
-        lab = np.asarray(labels)
-        if lab.dtype != np.uint16 or lab.shape != (nt,):
-            raise ValueError("%s: the labels are %s %r, the instants uint16 %r" % (what, lab.dtype, lab.shape, (nt,)))
-        return lab, self._n_groups(n_groups, what, lab=lab)
-
-    def _time_labels(self, q, labels, what):
-        """The label arguments of the grouped calls over time for the cubes q -- one uint16 array [instants] per cube, on the host --:
-        (pointer, offsets, what must stay alive over the call)."""
-        labels = list(labels)
-        if len(labels) != len(q):
-            raise ValueError("%s: %d label arrays for %d cubes" % (what, len(labels), len(q)))
-        nt = self._extent(q, 0)
-        parts = []
-        for i, m in enumerate(labels):
-            m = np.asarray(m)
-            if m.dtype != np.uint16:
-                raise ValueError("%s: labels %d are %s, not uint16" % (what, i, m.dtype))
-            if m.shape != (int(nt[i]),):
-                raise ValueError("%s: labels %d have shape %r, their cube %d instants" % (what, i, m.shape, int(nt[i])))
-            parts.append(m)
-        l_ptr, l_off, _, keep = self._host_arrays(parts, np.uint16)
-        return l_ptr, l_off, keep
+        return self._whole(_ReduceTime, (ops,), (), start, stop, window)
 
     def reduce_time_groups_flat(self, cubes, ops, labels, n_groups, out_device_ptr=None, out_offset=None):
         """reduce_time_flat's statistics per cell and group of instants, of dataset-level cubes [n, 6] through
@@ -282,27 +228,14 @@ class EncodedRaster:
         form: returns (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's part is flat[offsets[q]:] shaped
         (statistics, n_groups, r, c).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats =
         uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided leaves."""
-        mask, names = self.reduce_ops(ops)
-        n_groups = self._n_groups(n_groups)
-        q = self._cubes(cubes)
-        l_ptr, l_off, keep = self._time_labels(q, labels, "reduce_time_groups")
-        return self._region_call("reduce_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), l_ptr, l_off, C.c_uint32(n_groups), out, mem, off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_ReduceTimeGroups(ops), cubes, labels, n_groups, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def reduce_time_groups(self, ops, labels, start=0, stop=None, window=None, n_groups=None):
         """{statistic: ndarray [n_groups, rows, cols] float64}: reduce_time over the instants [start, stop) of the whole raster, or
         of `window` = (top, bottom, left, right), separately for every group of `labels` -- uint16 [stop - start], GROUP_NONE and
         labels >= n_groups are in no group.  n_groups defaults to the largest label present, GROUP_NONE apart, plus 1 (at least
         1).  Without instants or cells: NaN planes, count 0 and sum 0, of that shape."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        mask, names = self.reduce_ops(ops)
-        lab, n_groups = self._group_labels(labels, stop - start, n_groups, "reduce_time_groups")
-        shape = (n_groups, bottom - top, right - left)
-        if start == stop or shape[1] * shape[2] == 0:
-            return self._nothing("reduce_time", names, shape)
-        out, _, _, _ = self.reduce_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups)
-        return self._cut(out, names, shape)
+        return self._whole(_ReduceTimeGroups, (ops,), (labels, n_groups), start, stop, window)
 
     @staticmethod
     def moment_ops(ops):
@@ -312,12 +245,6 @@ class EncodedRaster:
         if mask >= 16:
             raise ValueError("moments_time: ops %r is not a set of %s" % (ops, ", ".join(L.MOMENT_OPS)))
         return mask, names
-
-    @staticmethod
-    def _ddof(ddof):
-        if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or ddof not in (0, 1):
-            raise ValueError("moments_time: ddof %r is neither 0 nor 1" % (ddof,))
-        return int(ddof)
 
     def moments_time_flat(self, cubes, ops, ddof=0, out_device_ptr=None, out_offset=None):
         """Per-cell count, mean, variance and standard deviation over time of dataset-level cubes [n, 6] through
@@ -329,24 +256,12 @@ class EncodedRaster:
         kernel ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset
         in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from
         elided leaves."""
-        mask, names = self.moment_ops(ops)
-        ddof = self._ddof(ddof)
-        q = self._cubes(cubes)
-        return self._region_call("moments_time", q, lambda: self._planes(q, len(names)), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), C.c_uint32(ddof), out, mem, off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_MomentsTime(ops, ddof), cubes, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def moments_time(self, ops=("mean", "std"), start=0, stop=None, window=None, ddof=0):
         """{statistic: ndarray [rows, cols] float64} of moments_time_flat over the instants [start, stop) of the whole raster, or
         of `window` = (top, bottom, left, right).  Without instants or cells: count 0, NaN elsewhere."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        mask, names = self.moment_ops(ops)
-        ddof = self._ddof(ddof)
-        shape = (bottom - top, right - left)
-        if start == stop or shape[0] * shape[1] == 0:
-            return self._nothing("moments_time", names, shape)
-        out, _, _, _ = self.moments_time_flat([[start, stop, top, bottom, left, right]], mask, ddof)
-        return self._cut(out, names, shape)
+        return self._whole(_MomentsTime, (ops, ddof), (), start, stop, window)
 
     def moments_time_groups_flat(self, cubes, ops, labels, n_groups, ddof=0, out_device_ptr=None, out_offset=None):
         """moments_time_flat's statistics per cell and group of instants through dcdf_raster_moments_time_groups_batch: one walk of
@@ -355,45 +270,20 @@ class EncodedRaster:
         [n_groups, rows, cols] float64 array per statistic of `ops`, in the order count, mean, var, std: group g is moments_time of
         the instants labelled g, in order (its K is the group's first value); a group without a value gets 0, NaN, NaN, NaN.
         Returns what moments_time_flat returns, cube q's part shaped (statistics, n_groups, r, c)."""
-        mask, names = self.moment_ops(ops)
-        ddof = self._ddof(ddof)
-        n_groups = self._n_groups(n_groups, "moments_time_groups")
-        q = self._cubes(cubes)
-        l_ptr, l_off, keep = self._time_labels(q, labels, "moments_time_groups")
-        return self._region_call("moments_time_groups", q, lambda: self._planes(q, len(names) * n_groups), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), C.c_uint32(ddof), l_ptr, l_off, C.c_uint32(n_groups), out, mem,
-                                                                  off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_MomentsTimeGroups(ops, ddof), cubes, labels, n_groups, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def moments_time_groups(self, ops, labels, start=0, stop=None, window=None, n_groups=None, ddof=0):
         """{statistic: ndarray [n_groups, rows, cols] float64}: moments_time over the instants [start, stop) of the whole raster, or
         of `window`, separately for every group of `labels` -- uint16 [stop - start], GROUP_NONE and labels >= n_groups are in no
         group.  n_groups defaults to the largest label present, GROUP_NONE apart, plus 1 (at least 1).  With one group and all
         labels 0 it is moments_time bit for bit.  Without instants or cells: count 0, NaN elsewhere, of that shape."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        mask, names = self.moment_ops(ops)
-        ddof = self._ddof(ddof)
-        lab, n_groups = self._group_labels(labels, stop - start, n_groups, "moments_time_groups")
-        shape = (n_groups, bottom - top, right - left)
-        if start == stop or shape[1] * shape[2] == 0:
-            return self._nothing("moments_time", names, shape)
-        out, _, _, _ = self.moments_time_groups_flat([[start, stop, top, bottom, left, right]], mask, [lab], n_groups, ddof)
-        return self._cut(out, names, shape)
+        return self._whole(_MomentsTimeGroups, (ops, ddof), (labels, n_groups), start, stop, window)
 
     @staticmethod
     def spell_ops(ops):
         """ops of spells / spells_flat as (bitmask, names in plane order): a DCDF_SPELL_* bitmask, one name or an iterable of
         "count" / "longest" / "longest_start" / "first" / "last"."""
         return EncodedRaster._ops(ops, L.SPELL_OPS, "spells")
-
-    @staticmethod
-    def _spell_bounds(lower, upper, n):
-        """One (lower, upper) pair per cube as float64 arrays; a scalar is shared by all cubes.  NaN is refused."""
-        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,)))
-        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,)))
-        if np.isnan(lo).any() or np.isnan(hi).any():
-            raise ValueError("spells: a NaN bound")
-        return lo, hi
 
     def spells_flat(self, cubes, lower, upper, ops, out_device_ptr=None, out_offset=None):
         """Per-cell spell statistics of dataset-level cubes [n, 6] through dcdf_raster_spells_batch: instant i of a cell (counted
@@ -404,44 +294,13 @@ class EncodedRaster:
         ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset in
         elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
         leaves."""
-        mask, names = self.spell_ops(ops)
-        q = self._cubes(cubes)
-        lo, hi = self._spell_bounds(lower, upper, len(q))
-        return self._region_call("spells", q, lambda: self._planes(q, len(names)), np.uint32,
-                                 lambda n, out, mem, off, stats: (C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), n, C.c_uint32(mask), out, mem,
-                                                                  off, stats), out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_Spells(ops), cubes, lower, upper, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, window=None):
         """{statistic: ndarray [rows, cols] uint32} of the hits of [lower, upper] over the instants [start, stop) of the whole
         raster, or of `window` = (top, bottom, left, right); instants are counted from `start`.  Without instants: zeros for count
         and longest, SPELL_NONE for the others."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        mask, names = self.spell_ops(ops)
-        self._spell_bounds(lower, upper, 1)
-        shape = (bottom - top, right - left)
-        if start == stop or shape[0] * shape[1] == 0:
-            return self._nothing("spells", names, shape)
-        out, _, _, _ = self.spells_flat([[start, stop, top, bottom, left, right]], lower, upper, mask)
-        return self._cut(out, names, shape)
-
-    @staticmethod
-    def _probs(probs, method):
-        """probs / method of quantile_time as (float64 array [n], method code, probs was a scalar): 1 .. 16 probabilities in [0, 1],
-        method one of "lower", "higher", "nearest", "linear" (or its DCDF_QUANTILE_* code)."""
-        p = np.asarray(probs, dtype=np.float64)
-        scalar = p.ndim == 0
-        p = np.ascontiguousarray(p.reshape(-1))
-        if not 1 <= p.size <= L.QUANTILE_MAX_PROBS:
-            raise ValueError("quantile_time: %d probabilities, not 1 .. %d" % (p.size, L.QUANTILE_MAX_PROBS))
-        if not ((p >= 0) & (p <= 1)).all():  # (a NaN fails both)
-            raise ValueError("quantile_time: probabilities must lie in [0, 1]")
-        if isinstance(method, str):
-            if method not in L.QUANTILE_METHODS:
-                raise ValueError("quantile_time: unknown method %r (one of %s)" % (method, ", ".join(L.QUANTILE_METHODS)))
-            method = L.QUANTILE_METHODS[method]
-        if int(method) not in L.QUANTILE_METHODS.values():
-            raise ValueError("quantile_time: unknown method %r" % (method,))
-        return p, int(method), scalar
+        return self._whole(_Spells, (ops,), (lower, upper), start, stop, window)
 
     def quantile_time_flat(self, cubes, probs, method="linear", out_device_ptr=None, out_offset=None):
         """Per-cell quantiles over time of dataset-level cubes [n, 6] through dcdf_raster_quantile_time_batch: cube q yields one
@@ -452,25 +311,13 @@ class EncodedRaster:
         on the device.  Host form: returns (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's planes are
         flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms,
         stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided leaves."""
-        p, code, _ = self._probs(probs, method)
-        q = self._cubes(cubes)
-        return self._region_call("quantile_time", q, lambda: self._planes(q, p.size), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_void_p(p.ctypes.data), C.c_uint32(p.size), C.c_int32(code), out, mem, off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_QuantileTime(probs, method), cubes, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def quantile_time(self, probs, start=0, stop=None, window=None, method="linear"):
         """ndarray [n_probs, rows, cols] float64 ([rows, cols] for a scalar `probs`): the quantiles of every cell's series over the
         instants [start, stop) of the whole raster, or of `window` = (top, bottom, left, right) (quantile_time_flat's rule).  Without
         instants or cells: NaN planes of that shape."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        p, code, scalar = self._probs(probs, method)
-        rows, cols = bottom - top, right - left
-        if start == stop or rows * cols == 0:
-            out = np.full((p.size, rows, cols), np.nan)
-        else:
-            flat, _, _, _ = self.quantile_time_flat([[start, stop, top, bottom, left, right]], p, code)
-            out = flat[:p.size * rows * cols].reshape(p.size, rows, cols)
-        return out[0] if scalar else out
+        return self._whole(_QuantileTime, (probs, method), (), start, stop, window)
 
     @staticmethod
     def _device_arrays(q, arrays, what, noun):
@@ -527,26 +374,13 @@ class EncodedRaster:
         returns (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's series are flat[offsets[q]:] shaped (series,
         instants).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells
         read by the bulk kernel, by the fallback walk, from elided leaves."""
-        mask, names = self.reduce_ops(ops)
-        q = self._cubes(cubes)
-        m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "reduce_space")
-        return self._region_call("reduce_space", q, lambda: self._extent(q, 0) * len(names), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), m_ptr, m_off, m_mem, out, mem, off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_ReduceSpace(ops), cubes, masks, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def reduce_space(self, ops, start=0, stop=None, window=None, mask=None):
         """{statistic: ndarray [stop - start] float64} over the cells of the whole raster, or of `window` = (top, bottom, left,
         right), at every instant of [start, stop); mask: [rows, cols] of the window, non-zero = the cell is selected.  Without
         instants: empty arrays."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        bits, names = self.reduce_ops(ops)
-        if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
-            raise ValueError("reduce_space: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
-        nt = stop - start
-        if nt == 0:
-            return {n: np.empty(0, dtype=np.float64) for n in names}
-        out, _, _, _ = self.reduce_space_flat([[start, stop, top, bottom, left, right]], bits, None if mask is None else [mask])
-        return self._cut(out, names, (nt,))
+        return self._whole(_ReduceSpace, (ops,), (mask,), start, stop, window)
 
     @staticmethod
     def _label_args(q, labels, what):
@@ -582,40 +416,14 @@ class EncodedRaster:
         ms, stats): cube q's part is flat[offsets[q]:] shaped (series, n_zones, instants).  Device form (out_device_ptr + out_offset
         in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided
         leaves."""
-        mask, names = self.reduce_ops(ops)
-        n_zones = self._n_groups(n_zones, "zonal", "n_zones")
-        q = self._cubes(cubes)
-        l_ptr, l_off, l_mem, keep, _ = self._label_args(q, labels, "zonal")
-        return self._region_call("zonal", q, lambda: self._extent(q, 0) * (len(names) * n_zones), np.float64,
-                                 lambda n, out, mem, off, stats: (n, C.c_uint32(mask), l_ptr, l_off, l_mem, C.c_uint32(n_zones), out, mem, off, stats),
-                                 out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_Zonal(ops), cubes, labels, n_zones, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def zonal(self, ops, labels, start=0, stop=None, window=None, n_zones=None):
         """{statistic: ndarray [n_zones, stop - start] float64} per zone of `labels` -- uint16 [rows, cols] of the whole raster, or
         of `window` = (top, bottom, left, right); ZONE_NONE and labels >= n_zones are in no zone -- at every instant of [start,
         stop).  n_zones defaults to the largest label present, ZONE_NONE apart, plus 1 (at least 1).  Without instants: empty
         matrices."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        bits, names = self.reduce_ops(ops)
-        lab = np.asarray(labels)
-        if lab.dtype != np.uint16 or lab.shape != (bottom - top, right - left):
-            raise ValueError("zonal: the labels are %s %r, the window uint16 %r" % (lab.dtype, lab.shape, (bottom - top, right - left)))
-        n_zones = self._n_groups(n_zones, "zonal", "n_zones", lab, L.ZONE_NONE)
-        nt = stop - start
-        if nt == 0:
-            return {n: np.empty((n_zones, 0), dtype=np.float64) for n in names}
-        out, _, _, _ = self.zonal_flat([[start, stop, top, bottom, left, right]], bits, [lab], n_zones)
-        return self._cut(out, names, (n_zones, nt))
-
-    @staticmethod
-    def _edges(edges):
-        """Histogram edges as float64 [bins + 1]: 1 .. 256 bins, no NaN, strictly increasing (-inf first and +inf last are fine)."""
-        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
-        if e.ndim != 1 or not 2 <= e.size <= L.HIST_MAX_BINS + 1:
-            raise ValueError("histogram: edges must be 2 .. %d increasing values" % (L.HIST_MAX_BINS + 1))
-        if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
-            raise ValueError("histogram: edges must be strictly increasing, without NaN")
-        return e
+        return self._whole(_Zonal, (ops,), (labels, n_zones), start, stop, window)
 
     def histogram_flat(self, cubes, edges, masks=None, out_device_ptr=None, out_offset=None):
         """Per-instant value histograms over the selected cells of dataset-level cubes [n, 6] through dcdf_raster_histogram_batch:
@@ -625,38 +433,23 @@ class EncodedRaster:
         Host form: returns (flat uint64 array, offsets uint64[n], kernel ms, stats): cube q is flat[offsets[q]:] shaped (instants,
         bins).  Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by
         the bulk kernel, by the fallback walk, from elided leaves."""
-        e = self._edges(edges)
-        bins = e.size - 1
-        q = self._cubes(cubes)
-        m_ptr, m_off, m_mem, keep = self._mask_args(q, masks, "histogram")
-        return self._region_call("histogram", q, lambda: self._extent(q, 0) * bins, np.uint64,
-                                 lambda n, out, mem, off, stats: (n, C.c_void_p(e.ctypes.data), C.c_uint32(bins), m_ptr, m_off, m_mem, out, mem, off, stats),
-                                 zeroed=True, out_device_ptr=out_device_ptr, out_offset=out_offset)
+        return self._flat(_Histogram(edges), cubes, masks, out_device_ptr=out_device_ptr, out_offset=out_offset)
 
     def histogram(self, edges, start=0, stop=None, window=None, mask=None):
         """ndarray [stop - start, bins] uint64: per instant of [start, stop), how many cells of the whole raster, or of `window` =
         (top, bottom, left, right), fall into every bin of `edges` (histogram_flat's rule); mask: [rows, cols] of the window,
         non-zero = the cell is selected.  Without instants: shape (0, bins)."""
-        start, stop, top, bottom, left, right = self._window_args(start, stop, window)
-        e = self._edges(edges)
-        bins = e.size - 1
-        if mask is not None and np.asarray(mask).shape != (bottom - top, right - left):
-            raise ValueError("histogram: the mask has shape %r, the window %r" % (np.asarray(mask).shape, (bottom - top, right - left)))
-        nt = stop - start
-        if nt == 0:
-            return np.zeros((0, bins), dtype=np.uint64)
-        out, _, _, _ = self.histogram_flat([[start, stop, top, bottom, left, right]], e, None if mask is None else [mask])
-        return out[:nt * bins].reshape(nt, bins)
+        return self._whole(_Histogram, (edges,), (mask,), start, stop, window)
 
     def _search(self, entry, cubes, bounds, out_device_ptr, cap):
         """dcdf_<entry> over the cubes [n, 6]; bounds(n) = the (lower, upper) arrays of the entry's type.  Returns (triples uint32[hits,
         3] in raster coordinates -- or None when they stay on the device --, offsets, counts, kernel ms)."""
-        q = np.ascontiguousarray(np.asarray(cubes, dtype=np.uint32).reshape(-1, 6))
+        q = self._cubes(cubes)
         lo, hi = (np.ascontiguousarray(b) for b in bounds(len(q)))
         counts = np.zeros(len(q), dtype=np.uint64)
         offs = np.zeros(len(q), dtype=np.uint64)
         if cap is None:
-            cap = int(np.abs((q[:, 1].astype(np.int64) - q[:, 0]) * (q[:, 3].astype(np.int64) - q[:, 2]) * (q[:, 5].astype(np.int64) - q[:, 4])).sum())
+            cap = int((self._extent(q, 0) * self._extent(q, 2) * self._extent(q, 4)).sum())
         ms = C.c_float()
         trip = None if out_device_ptr else np.empty((max(cap, 1), 3), dtype=np.uint32)
         L.check(getattr(L.lib(), "dcdf_" + entry)(self._handle(), q.ctypes.data_as(C.POINTER(L.Cube)), C.c_void_p(lo.ctypes.data),
@@ -682,7 +475,6 @@ class EncodedRaster:
         """Dataset-level points [n, 3] of (instant, row, col) through dcdf_raster_get_batch (Superchunk::get, superchunk.rs:313-352),
         typed as fill_windows_flat.  Host form: returns (values of dtype [n], kernel ms); device form (out_device_ptr): value i is
         written at element i there, returns kernel ms."""
-        from .chunk import _ENC
         p = np.ascontiguousarray(np.asarray(points, dtype=np.uint32).reshape(-1, 3))
         dtype = np.dtype(dtype)
         ms = C.c_float()
@@ -697,24 +489,23 @@ class EncodedRaster:
         superchunk.rs:356-400).  Host form: returns (flat array of dtype, offsets uint64[n], kernel ms): series i is
         flat[offsets[i]:offsets[i] + |end - start|].  Device form (out_device_ptr; out_offset in elements, None = one after the
         other): returns kernel ms."""
-        from .chunk import _ENC
         q = np.ascontiguousarray(np.asarray(cells, dtype=np.uint32).reshape(-1, 4))
         dtype = np.dtype(dtype)
         ms = C.c_float()
+        out = None
         if out_device_ptr is None:
-            ln = np.abs(q[:, 1].astype(np.int64) - q[:, 0]).astype(np.uint64)
+            ln = self._extent(q, 0).astype(np.uint64)
             off = np.zeros(len(q), dtype=np.uint64)
             if len(q) > 1:
                 off[1:] = np.cumsum(ln)[:-1]
             out = np.empty(max(1, int(ln.sum())), dtype=dtype)
-            L.check(L.lib().dcdf_raster_fill_cell_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(out.ctypes.data),
-                                                        _ENC[dtype], L.MEM_HOST, C.c_void_p(off.ctypes.data), C.byref(ms)), "raster_fill_cell_batch")
-            return out[:int(ln.sum())], off, ms.value
-        off = None if out_offset is None else np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
-        L.check(L.lib().dcdf_raster_fill_cell_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(out_device_ptr),
-                                                    _ENC[dtype], L.MEM_DEVICE, None if off is None else C.c_void_p(off.ctypes.data), C.byref(ms)),
-                "raster_fill_cell_batch")
-        return ms.value
+        else:
+            off = None if out_offset is None else np.ascontiguousarray(np.asarray(out_offset, dtype=np.uint64))
+        L.check(L.lib().dcdf_raster_fill_cell_batch(self._handle(), C.c_void_p(q.ctypes.data), C.c_size_t(len(q)),
+                                                    C.c_void_p(out_device_ptr if out is None else out.ctypes.data), _ENC[dtype],
+                                                    L.MEM_DEVICE if out is None else L.MEM_HOST, None if off is None else C.c_void_p(off.ctypes.data),
+                                                    C.byref(ms)), "raster_fill_cell_batch")
+        return ms.value if out is None else (out[:int(ln.sum())], off, ms.value)
 
     @staticmethod
     def chunk_grid(shape, tile=256, chunk_size=32):
@@ -829,3 +620,286 @@ class EncodedRaster:
                 org = np.array(self._origin(int(sub[k, 1])), dtype=np.int64)
                 res[int(sub[k, 0])].append(trip[int(soff[k]):int(soff[k]) + int(counts[k])].astype(np.int64) + org)
         return [np.concatenate(r) if r else np.zeros((0, 3), dtype=np.int64) for r in res]
+
+
+# ---- the region statistics, one description each ---------------------------------------------------------------------------------
+def _planes(q, n):
+    """elements of n [rows, cols] planes per cube (a cube without instants writes nothing)"""
+    return np.where(q[:, 1] == q[:, 0], 0, EncodedRaster._extent(q, 2) * EncodedRaster._extent(q, 4) * n)
+
+
+class _ReduceTime:
+    """reduce_time, and what a region statistic's description holds; the others override what differs.  An instance is one call:
+    __init__ checks and normalises the statistic's own arguments that need no cube, in their order (every form begins with them).
+    The drivers -- EncodedRaster._flat, EncodedRaster._whole, Variable._statistic -- do the rest from these:
+      name, dtype, zeroed     the entry dcdf_raster_<name>_batch, its output's dtype, whether the output must start as zeros
+      names, fill             the result's arrays in plane order and {name: its value where nothing was read}; names None: one dense
+                              array, `fill` its value
+      over_time               a statistic over time: without cells there is nothing to read either (else: only without instants)
+      flat(cubes, *arrays)    the flat form's arrays per cube (labels, masks, bounds) staged against the cubes; returns the cubes
+      count(q)                elements per cube
+      args(n, out, mem, off, stats)  the C arguments between the cubes and the kernel ms, in the entry's own order (_region_call)
+      window(nt, rows, cols, *arrays)  the whole-raster form's arrays against the window; returns flat()'s arrays for that one cube
+      shape(nt, rows, cols)   of every array of the whole-raster result
+      unread(own, arrays, nt, rows, cols)  the description as Variable makes it without instants, where no raster can be built"""
+    name, dtype, zeroed, over_time = "reduce_time", np.float64, False, True
+    fill = dict(min=np.nan, max=np.nan, sum=0.0, count=0.0, mean=np.nan)
+
+    def __init__(self, ops):
+        self.mask, self.names = EncodedRaster.reduce_ops(ops)
+
+    def flat(self, cubes):
+        return EncodedRaster._cubes(cubes)
+
+    def count(self, q):
+        return _planes(q, len(self.names))
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), out, mem, off, stats
+
+    def window(self, nt, rows, cols):
+        return ()
+
+    def shape(self, nt, rows, cols):
+        return rows, cols
+
+    @classmethod
+    def unread(cls, own, arrays, nt, rows, cols):
+        S = cls(*own)
+        S.window(nt, rows, cols, *arrays)
+        return S
+
+    def nothing(self, shape):
+        """the result of `shape` where nothing was read -- no instant, no cell, no group or zone --, typed as its arrays are"""
+        if self.names is None:
+            return np.full(shape, self.fill, dtype=self.dtype)
+        return {n: np.full(shape, self.fill[n], dtype=self.dtype) for n in self.names}
+
+    def cut(self, out, shape):
+        """one cube's flat result as arrays of `shape`, one after the other in the order of `names`"""
+        n = int(np.prod(shape, dtype=np.int64))
+        if self.names is None:
+            return out[:n].reshape(shape)
+        return {name: out[i * n:(i + 1) * n].reshape(shape) for i, name in enumerate(self.names)}
+
+
+class _MomentsTime(_ReduceTime):
+    name = "moments_time"
+    fill = dict(count=0.0, mean=np.nan, var=np.nan, std=np.nan)
+
+    def __init__(self, ops, ddof):
+        self.mask, self.names = EncodedRaster.moment_ops(ops)
+        if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or ddof not in (0, 1):
+            raise ValueError("moments_time: ddof %r is neither 0 nor 1" % (ddof,))
+        self.ddof = int(ddof)
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), C.c_uint32(self.ddof), out, mem, off, stats
+
+
+class _Grouped:
+    """A statistic per group of instants or zone of cells: (labels, n) are its arrays, uint16 labels, `none` and every label >= n in
+    no group.  noun, extent: "group" of "instants", or "zone" of the "window"; labelled(nt, rows, cols): the shape the labels have."""
+
+    def groups(self, n, lab=None):
+        """n_groups / n_zones, 1 .. 65535; None: the largest label of `lab`, `none` apart, plus 1 (at least 1)"""
+        if n is None:
+            named = lab[lab != self.none]
+            n = int(named.max()) + 1 if named.size else 1
+        n = int(n)
+        if not 1 <= n <= 65535:
+            raise ValueError("%s: n_%ss %d outside 1 .. 65535" % (self.name, self.noun, n))
+        return n
+
+    def window(self, nt, rows, cols, labels, n):
+        lab, shape = np.asarray(labels), self.labelled(nt, rows, cols)
+        if lab.dtype != np.uint16 or lab.shape != shape:
+            raise ValueError("%s: the labels are %s %r, the %s uint16 %r" % (self.name, lab.dtype, lab.shape, self.extent, shape))
+        self.n = self.groups(n, lab)
+        return [lab], self.n
+
+
+class _TimeGroups(_Grouped):
+    noun, extent, none = "group", "instants", L.GROUP_NONE
+
+    def flat(self, cubes, labels, n_groups):
+        """labels: one uint16 array [instants] per cube, on the host"""
+        self.n = self.groups(n_groups)
+        q, labels = EncodedRaster._cubes(cubes), list(labels)
+        if len(labels) != len(q):
+            raise ValueError("%s: %d label arrays for %d cubes" % (self.name, len(labels), len(q)))
+        nt = EncodedRaster._extent(q, 0)
+        parts = []
+        for i, m in enumerate(labels):
+            m = np.asarray(m)
+            if m.dtype != np.uint16:
+                raise ValueError("%s: labels %d are %s, not uint16" % (self.name, i, m.dtype))
+            if m.shape != (int(nt[i]),):
+                raise ValueError("%s: labels %d have shape %r, their cube %d instants" % (self.name, i, m.shape, int(nt[i])))
+            parts.append(m)
+        self.labels = EncodedRaster._host_arrays(parts, np.uint16)
+        return q
+
+    def count(self, q):
+        return _planes(q, len(self.names) * self.n)
+
+    def labelled(self, nt, rows, cols):
+        return (nt,)
+
+    def shape(self, nt, rows, cols):
+        return self.n, rows, cols
+
+
+class _ReduceTimeGroups(_TimeGroups, _ReduceTime):
+    name = "reduce_time_groups"  # (its statistics are reduce_time's, and so named in their messages)
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), self.labels[0], self.labels[1], C.c_uint32(self.n), out, mem, off, stats
+
+
+class _MomentsTimeGroups(_TimeGroups, _MomentsTime):
+    name = "moments_time_groups"  # (its statistics and ddof are moments_time's, and so named in their messages)
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), C.c_uint32(self.ddof), self.labels[0], self.labels[1], C.c_uint32(self.n), out, mem, off, stats
+
+
+class _Spells(_ReduceTime):
+    name, dtype = "spells", np.uint32
+    fill = dict(count=0, longest=0, longest_start=L.SPELL_NONE, first=L.SPELL_NONE, last=L.SPELL_NONE)
+
+    def __init__(self, ops):
+        self.mask, self.names = EncodedRaster.spell_ops(ops)
+
+    @staticmethod
+    def bounds(lower, upper, n):
+        """One (lower, upper) pair per cube as float64 arrays; a scalar is shared by all cubes.  NaN is refused."""
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,)))
+        if np.isnan(lo).any() or np.isnan(hi).any():
+            raise ValueError("spells: a NaN bound")
+        return lo, hi
+
+    def flat(self, cubes, lower, upper):
+        q = EncodedRaster._cubes(cubes)
+        self.lo, self.hi = self.bounds(lower, upper, len(q))
+        return q
+
+    def args(self, n, out, mem, off, stats):
+        return C.c_void_p(self.lo.ctypes.data), C.c_void_p(self.hi.ctypes.data), n, C.c_uint32(self.mask), out, mem, off, stats
+
+    def window(self, nt, rows, cols, lower, upper):
+        self.bounds(lower, upper, 1)
+        return lower, upper
+
+    @classmethod
+    def unread(cls, own, arrays, nt, rows, cols):  # (Variable.spells without instants looks at the bounds first)
+        cls.bounds(*arrays, 1)
+        return cls(*own)
+
+
+class _QuantileTime(_ReduceTime):
+    name, names, fill = "quantile_time", None, np.nan
+
+    def __init__(self, probs, method):
+        """1 .. 16 probabilities in [0, 1]; method one of "lower", "higher", "nearest", "linear" (or its DCDF_QUANTILE_* code)"""
+        p = np.asarray(probs, dtype=np.float64)
+        self.scalar = p.ndim == 0
+        self.p = p = np.ascontiguousarray(p.reshape(-1))
+        if not 1 <= p.size <= L.QUANTILE_MAX_PROBS:
+            raise ValueError("quantile_time: %d probabilities, not 1 .. %d" % (p.size, L.QUANTILE_MAX_PROBS))
+        if not ((p >= 0) & (p <= 1)).all():  # (a NaN fails both)
+            raise ValueError("quantile_time: probabilities must lie in [0, 1]")
+        if isinstance(method, str):
+            if method not in L.QUANTILE_METHODS:
+                raise ValueError("quantile_time: unknown method %r (one of %s)" % (method, ", ".join(L.QUANTILE_METHODS)))
+            method = L.QUANTILE_METHODS[method]
+        if int(method) not in L.QUANTILE_METHODS.values():
+            raise ValueError("quantile_time: unknown method %r" % (method,))
+        self.method = int(method)
+
+    def count(self, q):
+        return _planes(q, self.p.size)
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_void_p(self.p.ctypes.data), C.c_uint32(self.p.size), C.c_int32(self.method), out, mem, off, stats
+
+    def shape(self, nt, rows, cols):  # (a scalar `probs` has no axis of its own)
+        return (rows, cols) if self.scalar else (self.p.size, rows, cols)
+
+
+class _Masked:
+    """A statistic over the selected cells of every instant: the masks are its arrays (EncodedRaster._mask_args)."""
+    over_time = False
+
+    def flat(self, cubes, masks=None):
+        q = EncodedRaster._cubes(cubes)
+        self.masks = EncodedRaster._mask_args(q, masks, self.name)
+        return q
+
+    def window(self, nt, rows, cols, mask):
+        if mask is not None and np.asarray(mask).shape != (rows, cols):
+            raise ValueError("%s: the mask has shape %r, the window %r" % (self.name, np.asarray(mask).shape, (rows, cols)))
+        return (None if mask is None else [mask],)
+
+
+class _ReduceSpace(_Masked, _ReduceTime):
+    name = "reduce_space"  # (its statistics are reduce_time's, and so named in their messages)
+
+    def count(self, q):
+        return EncodedRaster._extent(q, 0) * len(self.names)
+
+    def args(self, n, out, mem, off, stats):
+        return (n, C.c_uint32(self.mask)) + self.masks[:3] + (out, mem, off, stats)
+
+    def shape(self, nt, rows, cols):
+        return (nt,)
+
+    @classmethod
+    def unread(cls, own, arrays, nt, rows, cols):  # (Variable.reduce_space without instants does not look at its mask)
+        return cls(*own)
+
+
+class _Zonal(_Grouped, _ReduceTime):
+    name, over_time = "zonal", False  # (its statistics are reduce_time's, and so named in their messages)
+    noun, extent, none = "zone", "window", L.ZONE_NONE
+
+    def flat(self, cubes, labels, n_zones):
+        self.n = self.groups(n_zones)
+        q = EncodedRaster._cubes(cubes)
+        self.labels = EncodedRaster._label_args(q, labels, "zonal")
+        return q
+
+    def count(self, q):
+        return EncodedRaster._extent(q, 0) * (len(self.names) * self.n)
+
+    def args(self, n, out, mem, off, stats):
+        return (n, C.c_uint32(self.mask)) + self.labels[:3] + (C.c_uint32(self.n), out, mem, off, stats)
+
+    def labelled(self, nt, rows, cols):
+        return rows, cols
+
+    def shape(self, nt, rows, cols):
+        return self.n, nt
+
+
+class _Histogram(_Masked, _ReduceTime):
+    name, dtype, zeroed, names, fill = "histogram", np.uint64, True, None, 0
+
+    def __init__(self, edges):
+        """edges as float64 [bins + 1]: 1 .. 256 bins, no NaN, strictly increasing (-inf first and +inf last are fine)"""
+        self.edges = e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
+        if e.ndim != 1 or not 2 <= e.size <= L.HIST_MAX_BINS + 1:
+            raise ValueError("histogram: edges must be 2 .. %d increasing values" % (L.HIST_MAX_BINS + 1))
+        if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+            raise ValueError("histogram: edges must be strictly increasing, without NaN")
+        self.bins = e.size - 1
+
+    def count(self, q):
+        return EncodedRaster._extent(q, 0) * self.bins
+
+    def args(self, n, out, mem, off, stats):
+        return (n, C.c_void_p(self.edges.ctypes.data), C.c_uint32(self.bins)) + self.masks[:3] + (out, mem, off, stats)
+
+    def shape(self, nt, rows, cols):
+        return nt, self.bins

@@ -8,6 +8,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from dcdf_amd import dataset
+from dcdf_amd.raster import EncodedRaster
+
 import group_model as GM
 import reduce_model as M
 import test_raster_plan_host as PH
@@ -54,18 +57,13 @@ def test_symbol_declared_and_listed():
     assert "dcdf_raster_reduce_time_groups_batch" in _lib.SYMBOLS and _lib.GROUP_NONE == 0xffff == GM.NONE
 
 
-class FakeRaster:
+class FakeRaster(EncodedRaster):
     """EncodedRaster's wrappers over a _region_call that answers from the model: what they pass down and how they shape the result."""
 
     def __init__(self, a):
-        from dcdf_amd.raster import EncodedRaster
-        self.a, self.shape, self.calls = a, a.shape, []
-        for name in ("_cubes", "_extent", "_planes", "_window_args", "_n_groups", "_group_labels", "_time_labels", "_nothing", "_cut",
-                     "_host_arrays", "reduce_ops", "reduce_time_groups_flat", "reduce_time_groups"):
-            f = EncodedRaster.__dict__[name]
-            setattr(self, name, f.__func__ if isinstance(f, staticmethod) else f.__get__(self))
+        self.a, self.shape, self.calls, self._native = a, a.shape, [], None
 
-    def _region_call(self, name, q, counts, dtype, args, out_device_ptr=None, out_offset=None):
+    def _region_call(self, name, q, counts, dtype, args, zeroed=False, stats=True, out_device_ptr=None, out_offset=None):
         import ctypes as C
         own = args(len(q), None, 0, None, None)
         assert name == "reduce_time_groups" and dtype == np.float64 and len(own) == 9
@@ -116,11 +114,7 @@ def test_wrappers_lay_out_groups_and_refuse_bad_labels():
 
 
 def test_variable_maps_ids_and_refuses_too_many():
-    from dcdf_amd import dataset
-
-    class FakeVar:
-        reduce_time_groups = dataset.Variable.reduce_time_groups
-
+    class FakeVar(dataset.Variable):
         def __init__(self, a):
             self.a, self.R = a, FakeRaster(a)
 
