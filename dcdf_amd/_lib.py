@@ -67,6 +67,7 @@ SYMBOLS = [
     "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs", "dcdf_raster_quantile_time_batch", "dcdf_quantile_select_host",
     "dcdf_raster_reduce_time_groups_batch",
     "dcdf_raster_moments_time_batch", "dcdf_raster_moments_time_groups_batch", "dcdf_moments_host",
+    "dcdf_regress_host",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -78,6 +79,8 @@ ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
 GROUP_NONE = 0xffff  # DCDF_GROUP_NONE: the label of an instant of no group (dcdf_raster_reduce_time_groups_batch)
 # dcdf_raster_moments_time_batch / dcdf_raster_moments_time_groups_batch: the statistics (DCDF_MOMENT_*), in plane order
 MOMENT_OPS = {"count": 1, "mean": 2, "var": 4, "std": 8}
+# dcdf_regress_host: the statistics (DCDF_REGRESS_*), in the order of its output
+REGRESS_OPS = {"count": 1, "slope": 2, "intercept": 4, "corr": 8}
 # dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
 QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
 QUANTILE_MAX_PROBS = 16
@@ -135,6 +138,8 @@ def lib():
                                                             C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.dcdf_moments_host.restype = C.c_int
         L.dcdf_moments_host.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.dcdf_regress_host.restype = C.c_int
+        L.dcdf_regress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.dcdf_raster_quantile_time_batch.restype = C.c_int
@@ -188,6 +193,22 @@ def moments_host(x, ddof=0, state=None, finish=True):
     out = np.empty(4, dtype=np.float64) if finish else None
     check(lib().dcdf_moments_host(x.ctypes.data if x.size else None, x.size, ddof, st.ctypes.data, None if out is None else out.ctypes.data),
           "moments_host")
+    return st, out
+
+
+def regress_host(x, e, state=None, finish=True):
+    """dcdf_regress_host (host only, no GPU): continues the state (c, K, sy, syy, se, see, sey) of the regression over time --
+    None: the initial one -- over the float64 pairs (x, e), NaN x skipped, with the contract's step (k2r_regress.h).  Returns (state
+    float64[7], (count, slope, intercept, corr) float64[4] or None without `finish`)."""
+    import numpy as np
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+    e = np.ascontiguousarray(np.asarray(e, dtype=np.float64).ravel())
+    st = np.array([0.0, np.nan, 0.0, 0.0, 0.0, 0.0, 0.0]) if state is None else np.array(state, dtype=np.float64)
+    if st.shape != (7,) or e.size != x.size:
+        raise ValueError("regress_host: the state is (c, K, sy, syy, se, see, sey), x and e are as long")
+    out = np.empty(4, dtype=np.float64) if finish else None
+    check(lib().dcdf_regress_host(x.ctypes.data if x.size else None, e.ctypes.data if e.size else None, x.size, st.ctypes.data,
+                                  None if out is None else out.ctypes.data), "regress_host")
     return st, out
 
 

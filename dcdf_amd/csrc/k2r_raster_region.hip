@@ -7,6 +7,7 @@
 
 #include "k2r_moment.h"
 #include "k2r_raster_host.h"
+#include "k2r_regress.h"
 
 using namespace k2r;
 
@@ -590,6 +591,23 @@ extern "C" int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, doubl
     if (out) {
         double o[4];
         moment_finish(s, ddof, o);
+        for (int i = 0; i < 4; i++) out[i] = o[i];
+    }
+    return DCDF_OK;
+}
+// the regression's step and finish on the host (k2r_regress.h; no HIP call): continues state = (c, K, sy, syy, se, see, sey) over the
+// pairs (x[i], e[i]) and finishes into out; a value of e that is not finite is refused before the state is touched
+extern "C" int dcdf_regress_host(const double* x, const double* e, size_t n, double state[7], double out[4]) {
+    if (!state || ((!x || !e) && n > 0)) return DCDF_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (!regress_finite(e[i])) return DCDF_ERR_BAD_ARG;
+    RegressState s{state[0], state[1], state[2], state[3], state[4], state[5], state[6]};
+    for (size_t i = 0; i < n; i++) regress_step(s, x[i], e[i]);
+    const double st[7] = {s.c, s.K, s.sy, s.syy, s.se, s.see, s.sey};
+    for (int i = 0; i < 7; i++) state[i] = st[i];
+    if (out) {
+        double o[4];
+        regress_finish(s, o);
         for (int i = 0; i < 4; i++) out[i] = o[i];
     }
     return DCDF_OK;

@@ -327,6 +327,33 @@ int dcdf_raster_moments_time_groups_batch(const dcdf_raster* r, const dcdf_cube*
  * (COUNT, MEAN, VAR, STD) with ddof.  A series starts from (0, NaN, 0, 0).  DCDF_ERR_BAD_ARG: NULL state, NULL x with n > 0,
  * ddof > 1. */
 int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, double state[4], double out[4]);
+/* Regression over time, the contract and its host form: the least-squares line of a series x[i] against a per-instant regressor
+ * e[i] -- a trend when the regressor is the instant index, a regression / correlation against an index series otherwise.  (The
+ * raster calls that would run it per cell of a cube are not part of this library yet)
+ * The state is seven doubles (c, K, sy, syy, se, see, sey), at first (0, NaN, +0.0, +0.0, +0.0, +0.0, +0.0).  For i ascending every
+ * pair with a non-NaN x[i] does
+ *     if (c == 0) K = x;  d = x - K;
+ *     sy = sy + d;  syy = syy + d * d;  se = se + e;  see = see + e * e;  sey = sey + e * d;  c = c + 1
+ * -- each one IEEE double operation, nothing contracted into an fma; a NaN x changes nothing.
+ * Finishing: n = c, me = se / n, my = sy / n, See = max(see - se * me, +0.0), Syy = max(syy - sy * my, +0.0), Sey = sey - se * my;
+ *     COUNT = c;  SLOPE = Sey / See when c >= 2 and See > 0, else NaN;  INTERCEPT = (K + my) - SLOPE * me, NaN when SLOPE is;
+ *     CORR = Sey / sqrt(See * Syy), the root correctly rounded, clamped to [-1, 1], when additionally Syy > 0, else NaN.
+ * Every NaN is the one quiet NaN.  The state is continued whole, so the result depends on no cut of the series.  A constant series
+ * has SLOPE exactly +0.0, INTERCEPT its value and CORR NaN; one valid pair gives NaN but for COUNT; for integer values with
+ * |x| < 2^53 a constant added to every value changes no bit of SLOPE or CORR, because every d is exact.
+ * THE REGRESSOR ENTERS AS GIVEN: nothing shifts it, and INTERCEPT is the fitted value at e = 0.  The values are shifted by K, the
+ * regressor is not, so accuracy needs a regressor near zero -- |e| of the order of its own spread.  With a the least |e| among the
+ * n valid pairs and rho = a / sqrt(See), the error of SLOPE * sqrt(See / Syy) and of CORR stays below
+ * 6 (1 + rho)^2 (n + 2)^2 2^-53 (derived in DESIGN.md section 4n): 6 (n + 2)^2 2^-53 when 0 is among those values (a first
+ * value of 0 whose x is no NaN; 0.22 n^2 2^-53 was the worst seen); with the instant index offset by 20000 the error was
+ * 3.7e3 n^2 2^-53 already at n = 3.  A caller whose regressor is far from zero (years, time stamps) passes e[i] - e[0] and reads
+ * INTERCEPT as the fitted value at the first instant. */
+enum { DCDF_REGRESS_COUNT = 1, DCDF_REGRESS_SLOPE = 2, DCDF_REGRESS_INTERCEPT = 4, DCDF_REGRESS_CORR = 8 };
+/* The step and the finish above on the host -- no GPU call.  Continues state = (c, K, sy, syy, se, see, sey) over the pairs
+ * (x[i], e[i]), i in [0, n) in order, NaN x skipped, and leaves the new state there; when out is not NULL, finishes that state into
+ * out = (COUNT, SLOPE, INTERCEPT, CORR).  A series starts from (0, NaN, 0, 0, 0, 0, 0).
+ * DCDF_ERR_BAD_ARG: NULL state, NULL x or e with n > 0, a value of e that is not finite (the state is then untouched). */
+int dcdf_regress_host(const double* x, const double* e, size_t n, double state[7], double out[4]);
 /* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
  * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
  * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
