@@ -67,7 +67,7 @@ SYMBOLS = [
     "dcdf_raster_zonal_batch", "dcdf_zonal_fold_limbs", "dcdf_raster_quantile_time_batch", "dcdf_quantile_select_host",
     "dcdf_raster_reduce_time_groups_batch",
     "dcdf_raster_moments_time_batch", "dcdf_raster_moments_time_groups_batch", "dcdf_moments_host",
-    "dcdf_regress_host",
+    "dcdf_regress_host", "dcdf_raster_regress_time_batch", "dcdf_raster_regress_time_groups_batch",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -79,7 +79,8 @@ ZONE_NONE = 0xffff  # DCDF_ZONE_NONE: the label of no zone
 GROUP_NONE = 0xffff  # DCDF_GROUP_NONE: the label of an instant of no group (dcdf_raster_reduce_time_groups_batch)
 # dcdf_raster_moments_time_batch / dcdf_raster_moments_time_groups_batch: the statistics (DCDF_MOMENT_*), in plane order
 MOMENT_OPS = {"count": 1, "mean": 2, "var": 4, "std": 8}
-# dcdf_regress_host: the statistics (DCDF_REGRESS_*), in the order of its output
+# dcdf_regress_host / dcdf_raster_regress_time_batch / dcdf_raster_regress_time_groups_batch: the statistics (DCDF_REGRESS_*), in
+# plane order
 REGRESS_OPS = {"count": 1, "slope": 2, "intercept": 4, "corr": 8}
 # dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
 QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
@@ -140,6 +141,13 @@ def lib():
         L.dcdf_moments_host.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
         L.dcdf_regress_host.restype = C.c_int
         L.dcdf_regress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dcdf_raster_regress_time_batch.restype = C.c_int
+        L.dcdf_raster_regress_time_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_regress_time_groups_batch.restype = C.c_int
+        L.dcdf_raster_regress_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_float)]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.dcdf_raster_quantile_time_batch.restype = C.c_int

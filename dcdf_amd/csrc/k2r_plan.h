@@ -1,4 +1,4 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_time_groups, reduce_space, histogram, spells, zonal, quantile_time:
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_time_groups, reduce_space, histogram, spells, zonal, quantile_time, regress_time:
 // k2r_raster_region.hip)
 // turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
@@ -18,6 +18,7 @@
 #include "k2r_items.h"
 #include "k2r_quantile.h"
 #include "k2r_reduce.h"
+#include "k2r_regress.h"
 #include "k2r_space.h"
 #include "k2r_spell.h"
 #include "k2r_zonal.h"
@@ -693,6 +694,7 @@ struct QuantileBand {
 struct QuantilePlan {
     std::vector<QuantileCol> cols;
     std::vector<QuantileSeg> segs;
+    std::vector<uint32_t> col_cube;  // the cube of every column (the selection does not ask; plan_regress_time does)
     std::vector<BulkUnit> units;
     std::vector<WinItem> items;
     std::vector<ConstPiece> consts;
@@ -762,6 +764,7 @@ inline int plan_quantile_time(const PlanRaster& g, const dcdf_cube* cubes, size_
                         }
                         P.cols.push_back(QuantileCol{nt, r1 - r0, c1 - c0, (uint32_t)wc, seg0, nseg, used,
                                                      base[q] + (uint64_t)(r0 - c.top) * wc + (c0 - c.left), wr * wc});
+                        P.col_cube.push_back((uint32_t)q);
                         subs.push_back(dcdf_cube{c.start, c.end, r0, r1, c0, c1});
                         sbase.push_back(used);
                         used += need;
@@ -774,6 +777,59 @@ inline int plan_quantile_time(const PlanRaster& g, const dcdf_cube* cubes, size_
             }
     }
     return flush();
+}
+
+// ---- regression over time ----------------------------------------------------------------------------------------------------
+// The cubes are decoded exactly as for the quantiles -- plan_quantile_time's bands, columns, segment tables, units, items and
+// elided fills over a slab of cap_bytes --, and k_regress_stream reads every cell's series from the slab once.  What it needs
+// beside a column is made here per cube that has cells (k2r_regress.h): the records of the instants that belong to a group, sorted
+// by (label, instant) -- a counting sort, stable, so a group's instants stay in order --, and the CSR of the groups over them,
+// counted from the cube's first record.  labels == nullptr: the ungrouped call, one group (n_groups == 1) of every instant in
+// order.  regressor == nullptr: the instant index counted from the cube's first instant.  A regressor value that is not finite
+// anywhere in the array of a cube that has cells: DCDF_ERR_BAD_ARG.  base[q]: cube q's first output plane.
+struct RegressPlan {
+    QuantilePlan q;
+    std::vector<RegressCol> cols;  // q.cols with their cube's rec0, start0
+    std::vector<RegressRec> recs;
+    std::vector<uint32_t> start;   // n_groups + 1 per cube that has cells
+};
+inline int plan_regress_time(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, uint64_t cap_bytes, bool node_wise,
+                             uint32_t wanted, const double* regressor, const uint64_t* regressor_offset, const uint16_t* labels,
+                             const uint64_t* label_offset, uint32_t n_groups, RegressPlan& P) {
+    std::vector<uint32_t> rec0(nq, 0), start0(nq, 0), fill;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        const uint32_t nt = c.end - c.start;
+        const double* const e = regressor ? regressor + regressor_offset[q] : nullptr;
+        const uint16_t* const lab = labels ? labels + label_offset[q] : nullptr;
+        for (uint32_t t = 0; e && t < nt; t++)
+            if (!regress_finite(e[t])) return DCDF_ERR_BAD_ARG;
+        if (P.recs.size() + nt > 0x7ffffff0ull || P.start.size() + n_groups + 1ull > 0x7ffffff0ull) return DCDF_ERR_CAPACITY;
+        rec0[q] = (uint32_t)P.recs.size();
+        start0[q] = (uint32_t)P.start.size();
+        // the groups' sizes, then their first records, then every instant into its group's next place
+        P.start.resize(P.start.size() + n_groups + 1u, 0u);
+        uint32_t* const st = P.start.data() + start0[q];
+        for (uint32_t t = 0; t < nt; t++) {
+            const uint32_t l = lab ? lab[t] : 0u;
+            if (l != 0xffffu && l < n_groups) st[l + 1u]++;
+        }
+        for (uint32_t l = 0; l < n_groups; l++) st[l + 1u] += st[l];
+        P.recs.resize(P.recs.size() + st[n_groups]);
+        RegressRec* const rec = P.recs.data() + rec0[q];
+        fill.assign(st, st + n_groups);
+        for (uint32_t t = 0; t < nt; t++) {
+            const uint32_t l = lab ? lab[t] : 0u;
+            if (l == 0xffffu || l >= n_groups) continue;
+            rec[fill[l]++] = RegressRec{e ? e[t] : (double)t, t, (c.start + t) / g.cs - c.start / g.cs};
+        }
+    }
+    const int rc = plan_quantile_time(g, cubes, nq, base, cap_bytes, node_wise, wanted, P.q);
+    if (rc != DCDF_OK) return rc;
+    P.cols.reserve(P.q.cols.size());
+    for (size_t i = 0; i < P.q.cols.size(); i++) P.cols.push_back(RegressCol{P.q.cols[i], rec0[P.q.col_cube[i]], start0[P.q.col_cube[i]]});
+    return DCDF_OK;
 }
 
 #undef K2R_PLAN_INLINE

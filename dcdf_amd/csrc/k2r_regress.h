@@ -1,6 +1,7 @@
-// k2r_regress.h -- regression over time, the contract: the per-cell state, its step and its finish, as dcdf_regress_host
-// (k2r_raster_region.hip) runs them on the host.  Compiles for the host alone as well (g++).  No kernel runs them yet: the raster
-// entry points are not built.
+// k2r_regress.h -- regression over time: the per-cell state, its step and its finish, and the cell body that streams one cell's
+// series through them (regress_cell) -- what dcdf_regress_host (k2r_raster_region.hip), the planner (plan_regress_time,
+// k2r_plan.h), the stream kernel (k_regress_stream, k2r_regress.hip) and the host checks (tests/sim) share.  Compiles for the host
+// alone as well (g++).  DESIGN.md section 4n.
 //
 // The contract (include/dcdf_k2r.h): the least-squares line of a series x[t] against a per-instant regressor
 // e[t].  The state is seven doubles (c, K, sy, syy, se, see, sey), at first (0, NaN, +0.0, +0.0, +0.0, +0.0, +0.0).  In instant
@@ -20,6 +21,7 @@
 // rule --, so the result depends on no cut of a series' instants.
 #pragma once
 #include "k2r_moment.h"
+#include "k2r_quantile.h"
 
 namespace k2r {
 
@@ -81,5 +83,70 @@ K2R_HD K2R_FP_STRICT_FN void regress_finish(const RegressState& s, double (&out)
     for (int i = 1; i < 4; i++)  // (what an overflowed sum leaves: inf - inf)
         if (out[i] != out[i]) out[i] = __builtin_nan("");
 }
+
+// ---- the column stream ---------------------------------------------------------------------------------------------------------
+// The raster calls decode a cube band by band into plan_quantile_time's slab of stored integers (k2r_plan.h); a lane per cell
+// then reads its own series from there, once.  What a cell needs beside its column is the same for every cell of its cube:
+//   records   one RegressRec per instant that belongs to a group, sorted by (group, instant): t, the instant counted from the
+//             cube's first; seg, the entry of the column's segment table that widens it (segments cut time only: the index is the
+//             same in every column of the cube); e, the cube's regressor value there;
+//   start     a CSR over them, start[g] .. start[g + 1] the records of group g (the ungrouped call: one group, every instant).
+struct RegressRec {
+    double e;
+    uint32_t t, seg;
+};
+static_assert(sizeof(RegressRec) == 16, "RegressRec");
+// A column of the stream kernel: the selection kernel's, and where its cube's records and CSR begin
+struct RegressCol {
+    QuantileCol q;
+    uint32_t rec0, start0;
+};
+constexpr uint32_t REGRESS_AHEAD = 4;  // slab values read before the first of them enters the chain of dependent additions
+
+// One cell from end to end, as the kernel runs it: recs / start / segs are the cube's records, its CSR and the column's segment
+// table; read(t) is the cell's stored integer at instant t, put(i, v) takes element v of plane i = (place of the statistic among
+// those of `ops`) * n_groups + g.  Every plane gets its value exactly once: a group without a record finishes the initial state (0,
+// NaN, NaN, NaN).  The reads of a batch depend on no state, so they are all issued before the batch's first step.
+template <class Read, class Put>
+K2R_HD void regress_cell(const RegressRec* recs, const uint32_t* start, uint32_t n_groups, const QuantileSeg* segs, uint32_t ops, Read&& read,
+                         Put&& put) {
+    for (uint32_t g = 0; g < n_groups; g++) {
+        RegressState s = regress_init();
+        uint32_t i = start[g];
+        const uint32_t i1 = start[g + 1u];
+        for (; i1 - i >= REGRESS_AHEAD; i += REGRESS_AHEAD) {
+            RegressRec r[REGRESS_AHEAD];
+            QuantileSeg G[REGRESS_AHEAD];
+            int64_t n[REGRESS_AHEAD];
+#pragma unroll
+            for (uint32_t k = 0; k < REGRESS_AHEAD; k++) r[k] = recs[i + k];
+#pragma unroll
+            for (uint32_t k = 0; k < REGRESS_AHEAD; k++) n[k] = read(r[k].t);
+#pragma unroll
+            for (uint32_t k = 0; k < REGRESS_AHEAD; k++) G[k] = segs[r[k].seg];
+#pragma unroll
+            for (uint32_t k = 0; k < REGRESS_AHEAD; k++) regress_step(s, reduce_widen(G[k].enc, G[k].fbits, n[k]), r[k].e);
+        }
+        for (; i < i1; i++) {
+            const QuantileSeg G = segs[recs[i].seg];
+            regress_step(s, reduce_widen(G.enc, G.fbits, read(recs[i].t)), recs[i].e);
+        }
+        double o[4];
+        regress_finish(s, o);
+        uint32_t plane = g;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++)
+            if (ops >> k & 1u) {
+                put(plane, o[k]);
+                plane += n_groups;
+            }
+    }
+}
+
+#if defined(__HIPCC__)
+// k_regress_stream over n columns on the null stream (asynchronous); max_cells: of the largest of them.  Returns a DCDF code.
+int launch_regress_stream(const RegressCol* d_cols, uint32_t n, uint64_t max_cells, const QuantileSeg* d_segs, const RegressRec* d_recs,
+                          const uint32_t* d_start, uint32_t n_groups, const int64_t* d_slab, uint32_t ops, double* d_dst);
+#endif
 
 }  // namespace k2r

@@ -405,8 +405,8 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         """The Variable form of every region statistic (stat: its description in raster.py, own / arrays: its arguments as
         EncodedRaster._whole takes them): the region, checked; then raster()'s whole-raster form -- or, without instants (possibly
         none stored yet: nothing to open), the own checks and the statistic's fill.  labels: the ids of a grouped call, made the
-        raster's dense labels here; it returns (ids, arrays), the fill too where no id is in a group or zone.  (Called through the
-        class: the methods also serve objects that borrow them.)"""
+        raster's dense labels here, `arrays` following them; it returns (ids, arrays), the fill too where no id is in a group or
+        zone.  (Called through the class: the methods also serve objects that borrow them.)"""
         stop, bottom, right = self._region(start, stop, top, bottom, left, right)
         nt, rows, cols = stop - start, bottom - top, right - left
         window = (top, bottom, left, right)
@@ -419,8 +419,9 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         ids, dense = Variable._dense_labels(labels, S.labelled(nt, rows, cols), S.name, S.noun, S.extent, S.none)
         S.n = ids.size
         if nt == 0 or S.n == 0:
+            S.beside(nt, *arrays)
             return ids, S.nothing(S.shape(nt, rows, cols))
-        return ids, self.raster()._whole(stat, own, (dense, S.n), start, stop, window)
+        return ids, self.raster()._whole(stat, own, (dense, S.n) + tuple(arrays), start, stop, window)
 
     def reduce_time_groups(self, labels, ops=("mean",), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """reduce_time per group of instants -- monthly means from daily data (labels = np.arange(T) // 30), a climatology (labels =
@@ -450,6 +451,30 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         gets 0, NaN, NaN, NaN).  More than 65535 distinct ids: ValueError.  Through raster().moments_time_groups: the encoded
         bytes are read once on the GPU whatever the number of groups (dcdf_raster_moments_time_groups_batch)."""
         return Variable._statistic(self, _raster._MomentsTimeGroups, (ops, ddof), (), start, stop, top, bottom, left, right, labels)
+
+    def regress_time(self, ops=("slope",), regressor=None, start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """Per-cell least-squares line over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
+        [rows, cols] float64} for the names of `ops` ("count", "slope", "intercept", "corr", or a DCDF_REGRESS_* bitmask), of the
+        values window() returns widened to float64, NaN cells skipped, against `regressor` -- None: the instant index, slope then
+        being the trend per instant; else real numbers [stop - start], finite: an index series, the time coordinate.  The
+        regressor is taken less its first value, so `intercept` is the fitted value at the first instant of [start, stop); for the
+        instant index this changes nothing.  corr is the Pearson correlation of the series with the regressor.  A cell with fewer
+        than two values, or a regressor without spread over the cell's values, gets NaN but for count; a constant cell has slope
+        exactly 0, intercept its value and corr NaN.  Through raster().regress_time: the cube is decoded band by band into a
+        bounded device buffer, every series is read there once and only the planes are written
+        (dcdf_raster_regress_time_batch)."""
+        return Variable._statistic(self, _raster._RegressTime, (ops,), (regressor,), start, stop, top, bottom, left, right)
+
+    def regress_time_groups(self, labels, ops=("slope",), regressor=None, start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """regress_time per group of instants -- a trend per season (labels = season_of(instants)): `labels` is any integer array
+        [stop - start] of group ids, negative = no group.  Returns (ids, {name: ndarray [len(ids), rows, cols] float64}) as
+        moments_time_groups does: ids are the distinct non-negative ids ascending, plane i of every array is regress_time over the
+        instants labelled ids[i], in order, each with its own regressor value (a cell without a value in the group gets 0, NaN,
+        NaN, NaN).  The regressor is taken less its first value for every group alike: `intercept` is the group's fitted value at
+        the first instant of [start, stop); for the instant index this changes nothing.  More than 65535 distinct ids: ValueError.
+        Through raster().regress_time_groups: the cube is decoded once on the GPU whatever the number of groups
+        (dcdf_raster_regress_time_groups_batch)."""
+        return Variable._statistic(self, _raster._RegressTimeGroups, (ops,), (regressor,), start, stop, top, bottom, left, right, labels)
 
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray

@@ -320,6 +320,56 @@ class EncodedRaster:
         return self._whole(_QuantileTime, (probs, method), (), start, stop, window)
 
     @staticmethod
+    def regress_ops(ops):
+        """ops of regress_time / regress_time_groups as (bitmask, names in plane order): a DCDF_REGRESS_* bitmask, one name or an
+        iterable of "count" / "slope" / "intercept" / "corr"."""
+        mask, names = EncodedRaster._ops(ops, L.REGRESS_OPS, "regress_time")
+        if mask >= 16:
+            raise ValueError("regress_time: ops %r is not a set of %s" % (ops, ", ".join(L.REGRESS_OPS)))
+        return mask, names
+
+    def regress_time_flat(self, cubes, ops, regressors=None, out_device_ptr=None, out_offset=None):
+        """Per-cell least-squares line over time of dataset-level cubes [n, 6] through dcdf_raster_regress_time_batch: cube q yields
+        one [rows, cols] float64 plane per statistic of `ops` (regress_ops), in the order count, slope, intercept, corr, of the
+        values decode_flat returns for it in the leaves' own dtype, NaN skipped, against a per-instant regressor.  regressors: None
+        -- the instant index counted from each cube's first instant, 0, 1, 2, ... -- or one float64 array [instants] per
+        (normalised) cube, finite.  It enters AS GIVEN (include/dcdf_k2r.h): intercept is the fitted value where the regressor is 0,
+        and the sums keep their accuracy only for a regressor near zero, so subtract a far-off regressor's first value before the
+        call (regress_time does).  The sums are taken of x - K, K the cell's first value, sequentially in instant order; a cell
+        with fewer than two values, or whose regressor values are all equal, gets NaN but for count; a constant cell has slope
+        exactly 0, intercept its value and corr NaN.  Host form: returns (flat float64 array, offsets uint64[n], kernel ms, stats):
+        cube q's planes are flat[offsets[q]:] shaped (planes, r, c).  Device form (out_device_ptr + out_offset in elements):
+        returns (kernel ms, stats).  stats = uint64[3]: cells read by the bulk kernel, by the fallback walk, from elided leaves."""
+        return self._flat(_RegressTime(ops), cubes, regressors, out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def regress_time(self, ops=("slope",), regressor=None, start=0, stop=None, window=None):
+        """{statistic: ndarray [rows, cols] float64} of regress_time_flat over the instants [start, stop) of the whole raster, or of
+        `window` = (top, bottom, left, right) -- a trend map with regressor=None (per instant), the regression on / correlation
+        with an index series otherwise: `regressor` is float64 [stop - start], finite.  What is passed on is regressor -
+        regressor[0], so `intercept` is the fitted value at the first instant of [start, stop), whatever the regressor's own zero
+        (years, time stamps); for the instant index this changes nothing.  Without instants or cells: count 0, NaN elsewhere."""
+        return self._whole(_RegressTime, (ops,), (regressor,), start, stop, window)
+
+    def regress_time_groups_flat(self, cubes, ops, labels, n_groups, regressors=None, out_device_ptr=None, out_offset=None):
+        """regress_time_flat's statistics per cell and group of instants through dcdf_raster_regress_time_groups_batch: the cube is
+        decoded once whatever the number of groups.  labels and n_groups are reduce_time_groups_flat's: one uint16 array [instants]
+        per (normalised) cube, GROUP_NONE (0xffff) and every other value >= n_groups in no group; regressors regress_time_flat's,
+        as given.  Cube q yields one [n_groups, rows, cols] float64 array per statistic of `ops`, in the order count, slope,
+        intercept, corr: group g is regress_time_flat of the instants labelled g, in order, each with its own regressor value; a
+        group without a value gets 0, NaN, NaN, NaN.  Returns what regress_time_flat returns, cube q's part shaped (statistics,
+        n_groups, r, c)."""
+        return self._flat(_RegressTimeGroups(ops), cubes, labels, n_groups, regressors, out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def regress_time_groups(self, ops, labels, regressor=None, start=0, stop=None, window=None, n_groups=None):
+        """{statistic: ndarray [n_groups, rows, cols] float64}: regress_time over the instants [start, stop) of the whole raster, or
+        of `window`, separately for every group of `labels` -- uint16 [stop - start], GROUP_NONE and labels >= n_groups are in no
+        group; a trend per season, say.  n_groups defaults to the largest label present, GROUP_NONE apart, plus 1 (at least 1).
+        What is passed on is regressor - regressor[0] for every group alike, so `intercept` is the group's fitted value at the first
+        instant of [start, stop); for the instant index (None) this changes nothing.  With one group and all labels 0 it is
+        regress_time bit for bit.  Without instants or cells: count 0, NaN elsewhere, of that shape."""
+        return self._whole(_RegressTimeGroups, (ops,), (labels, n_groups, regressor), start, stop, window)
+
+    @staticmethod
     def _device_arrays(q, arrays, what, noun):
         """One array per cube (masks, labels) already on the device, given as (device pointer, offsets uint64[n]): (pointer, offsets,
         memory kind, what must stay alive over the call); None when `arrays` is not of that form."""
@@ -711,6 +761,10 @@ class _Grouped:
             raise ValueError("%s: n_%ss %d outside 1 .. 65535" % (self.name, self.noun, n))
         return n
 
+    def beside(self, nt):
+        """the arrays a grouped statistic takes behind (labels, n), checked against nt instants: window()'s tail.  None here."""
+        return ()
+
     def window(self, nt, rows, cols, labels, n):
         lab, shape = np.asarray(labels), self.labelled(nt, rows, cols)
         if lab.dtype != np.uint16 or lab.shape != shape:
@@ -903,3 +957,68 @@ class _Histogram(_Masked, _ReduceTime):
 
     def shape(self, nt, rows, cols):
         return nt, self.bins
+
+
+class _RegressTime(_ReduceTime):
+    """The regressors are its arrays: the flat forms pass them as given, the whole-raster forms less their first value."""
+    name = "regress_time"
+    fill = dict(count=0.0, slope=np.nan, intercept=np.nan, corr=np.nan)
+
+    def __init__(self, ops):
+        self.mask, self.names = EncodedRaster.regress_ops(ops)
+
+    def regressor(self, u, nt, which=""):
+        """one regressor as float64 [nt]: real numbers (floats or integers) of that shape, every one finite"""
+        u = np.asarray(u)
+        if u.dtype.kind not in "fiu" or u.shape != (nt,):
+            raise ValueError("%s: the regressor%s is %s %r, the instants real numbers %r" % (self.name, which, u.dtype, u.shape, (nt,)))
+        u = u.astype(np.float64)
+        if not np.isfinite(u).all():
+            raise ValueError("%s: the regressor%s has a value that is not finite" % (self.name, which))
+        return u
+
+    def regressors(self, q, regs):
+        """the flat form's: None -- the instant index of every cube --, or one regressor per cube, staged as given"""
+        self.regs = None, None
+        if regs is not None:
+            regs = list(regs)
+            if len(regs) != len(q):
+                raise ValueError("%s: %d regressors for %d cubes" % (self.name, len(regs), len(q)))
+            nt = EncodedRaster._extent(q, 0)
+            self.regs = EncodedRaster._host_arrays([self.regressor(u, int(nt[i]), " %d" % i) for i, u in enumerate(regs)], np.float64)
+
+    def shifted(self, nt, u):
+        """the whole-raster form's regressor for flat(): less its first value, one float64 subtraction each; None stays None"""
+        if u is None:
+            return None
+        u = self.regressor(u, nt)
+        return [u - u[0] if nt else u]
+
+    def flat(self, cubes, regressors=None):
+        q = EncodedRaster._cubes(cubes)
+        self.regressors(q, regressors)
+        return q
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), self.regs[0], self.regs[1], out, mem, off, stats
+
+    def window(self, nt, rows, cols, regressor=None):
+        return (self.shifted(nt, regressor),)
+
+
+class _RegressTimeGroups(_TimeGroups, _RegressTime):
+    name = "regress_time_groups"  # (its statistics are regress_time's, and so named in their messages)
+
+    def flat(self, cubes, labels, n_groups, regressors=None):
+        q = _TimeGroups.flat(self, cubes, labels, n_groups)
+        self.regressors(q, regressors)
+        return q
+
+    def args(self, n, out, mem, off, stats):
+        return n, C.c_uint32(self.mask), self.regs[0], self.regs[1], self.labels[0], self.labels[1], C.c_uint32(self.n), out, mem, off, stats
+
+    def beside(self, nt, regressor=None):
+        return (self.shifted(nt, regressor),)
+
+    def window(self, nt, rows, cols, labels, n, regressor=None):
+        return tuple(_TimeGroups.window(self, nt, rows, cols, labels, n)) + self.beside(nt, regressor)

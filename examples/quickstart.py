@@ -64,4 +64,9 @@ q = R.quantile_time([0.5, 0.9], 8, 24)  # float64 [2, 256, 256]: the median and 
 srt, h = np.sort(a[8:24], axis=0).astype(np.float64), 15 * 0.9
 assert (q[0] == (srt[7] + srt[8]) / 2).all() and (q[1] == srt[int(h)] + (srt[int(h) + 1] - srt[int(h)]) * (h - int(h))).all()
 assert (R.quantile_time(0.9, 8, 24, method="higher") == np.quantile(a[8:24], 0.9, axis=0, method="higher")).all()
+trend = R.regress_time(("slope", "intercept", "corr"))  # per cell, the least-squares line against the instant index: a trend map
+fit = np.polyfit(np.arange(32.0), a.reshape(32, -1).astype(np.float64), 1)
+assert np.allclose(trend["slope"].ravel(), fit[0]) and np.allclose(trend["intercept"].ravel(), fit[1])
+years = 1990.0 + np.arange(32)  # any regressor: taken less its first value, so the intercept is the fitted value at years[0]
+assert np.allclose(R.regress_time(("intercept",), years)["intercept"], trend["intercept"]) and (np.abs(trend["corr"]) <= 1).all()
 print("readme example ok")

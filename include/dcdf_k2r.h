@@ -328,8 +328,8 @@ int dcdf_raster_moments_time_groups_batch(const dcdf_raster* r, const dcdf_cube*
  * ddof > 1. */
 int dcdf_moments_host(const double* x, size_t n, uint32_t ddof, double state[4], double out[4]);
 /* Regression over time, the contract and its host form: the least-squares line of a series x[i] against a per-instant regressor
- * e[i] -- a trend when the regressor is the instant index, a regression / correlation against an index series otherwise.  (The
- * raster calls that would run it per cell of a cube are not part of this library yet)
+ * e[i] -- a trend when the regressor is the instant index, a regression / correlation against an index series otherwise.  The
+ * raster calls below run it per cell of a cube, x[i] being reduce_time's x[t].
  * The state is seven doubles (c, K, sy, syy, se, see, sey), at first (0, NaN, +0.0, +0.0, +0.0, +0.0, +0.0).  For i ascending every
  * pair with a non-NaN x[i] does
  *     if (c == 0) K = x;  d = x - K;
@@ -354,6 +354,34 @@ enum { DCDF_REGRESS_COUNT = 1, DCDF_REGRESS_SLOPE = 2, DCDF_REGRESS_INTERCEPT = 
  * out = (COUNT, SLOPE, INTERCEPT, CORR).  A series starts from (0, NaN, 0, 0, 0, 0, 0).
  * DCDF_ERR_BAD_ARG: NULL state, NULL x or e with n > 0, a value of e that is not finite (the state is then untouched). */
 int dcdf_regress_host(const double* x, const double* e, size_t n, double state[7], double out[4]);
+/* The regression above per cell (row, col) of each cube -- a trend map, the correlation of every cell with an index series --, whole
+ * or, in the grouped call, separately for every group of a per-instant label array.  The cube is decoded band by band into the
+ * bounded device slab of dcdf_raster_quantile_time_batch and every cell's series is read from there once; the cube never reaches
+ * the host.  The calls take plain and tiled rasters, elided leaves included.  Cubes, out_mem, out_offset, stats and kernel_ms are
+ * exactly dcdf_raster_reduce_time_batch's; labels, label_offset, n_groups and DCDF_GROUP_NONE exactly
+ * dcdf_raster_reduce_time_groups_batch's.  ops is a non-empty set of DCDF_REGRESS_*.
+ *   regressor   in HOST memory: instant i of cube q, counted from the cube's first instant after normalisation, has the regressor
+ *               value regressor[regressor_offset[q] + i] (offsets in elements, as label_offset); it enters as given (above).  NULL,
+ *               together with a NULL regressor_offset: the instant index i itself, 0, 1, 2, ... as doubles.  A value that is not
+ *               finite anywhere in the array of a cube that has cells is DCDF_ERR_BAD_ARG before anything is launched.
+ * Per cell -- and group g, over the instants labelled g in ascending order, each with its own regressor value -- the pairs
+ * (x[t], e[t]) go through the step above from the initial state, then the finish.  Cube q writes popcount(ops) planes in the order
+ * COUNT, SLOPE, INTERCEPT, CORR from out + out_offset[q] (elements), each dense [rows][cols] float64 -- in the grouped call
+ * [n_groups][rows][cols].  A cell or group without a value gets 0, NaN, NaN, NaN.  Every element of the planes is written exactly
+ * once, nothing outside them is; a cube without instants, rows or columns writes nothing.  The grouped call with n_groups == 1 and
+ * all labels 0 is the plain call bit for bit, and the result depends on no cut of the work (K2R_QUANTILE_SLAB_BYTES, the slab's cap,
+ * changes no bit).
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 8, one of regressor / regressor_offset NULL and the other not, a regressor value that
+ * is not finite, (grouped) n_groups 0 or above 65535 and NULL labels / label_offset with nq > 0, NULL r / cubes / out / out_offset,
+ * an unknown out_mem (nq == 0 is fine, stats and kernel_ms may be NULL); DCDF_ERR_BOUNDS: a cube outside the raster;
+ * DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+int dcdf_raster_regress_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const double* regressor,
+                                   const uint64_t* regressor_offset, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                                   float* kernel_ms);
+int dcdf_raster_regress_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, const double* regressor,
+                                          const uint64_t* regressor_offset, const uint16_t* labels, const uint64_t* label_offset,
+                                          uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                                          float* kernel_ms);
 /* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
  * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
  * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
