@@ -68,6 +68,7 @@ SYMBOLS = [
     "dcdf_raster_reduce_time_groups_batch",
     "dcdf_raster_moments_time_batch", "dcdf_raster_moments_time_groups_batch", "dcdf_moments_host",
     "dcdf_regress_host", "dcdf_raster_regress_time_batch", "dcdf_raster_regress_time_groups_batch",
+    "dcdf_raster_rolling_time_batch", "dcdf_raster_rolling_time_groups_batch",
 ]
 # dcdf_raster_reduce_time_batch: the statistics, in plane order
 REDUCE_OPS = {"min": 1, "max": 2, "sum": 4, "count": 8, "mean": 16}
@@ -82,6 +83,11 @@ MOMENT_OPS = {"count": 1, "mean": 2, "var": 4, "std": 8}
 # dcdf_regress_host / dcdf_raster_regress_time_batch / dcdf_raster_regress_time_groups_batch: the statistics (DCDF_REGRESS_*), in
 # plane order
 REGRESS_OPS = {"count": 1, "slope": 2, "intercept": 4, "corr": 8}
+# dcdf_raster_rolling_time_batch / dcdf_raster_rolling_time_groups_batch: the statistics (DCDF_ROLLING_*), in plane order; the
+# kinds; the widest window
+ROLLING_OPS = {"max": 1, "argmax": 2, "min": 4, "argmin": 8, "count": 16}
+ROLLING_SUM, ROLLING_MEAN = 0, 1
+ROLLING_MAX_WINDOW = 65535
 # dcdf_raster_quantile_time_batch: DCDF_QUANTILE_*, and the most probabilities of one call
 QUANTILE_METHODS = {"lower": 0, "higher": 1, "nearest": 2, "linear": 3}
 QUANTILE_MAX_PROBS = 16
@@ -147,6 +153,13 @@ def lib():
         L.dcdf_raster_regress_time_groups_batch.restype = C.c_int
         L.dcdf_raster_regress_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_float)]
+        L.dcdf_raster_rolling_time_batch.restype = C.c_int
+        L.dcdf_raster_rolling_time_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.dcdf_raster_rolling_time_groups_batch.restype = C.c_int
+        L.dcdf_raster_rolling_time_groups_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
+                                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                             C.POINTER(C.c_float)]
         L.dcdf_zonal_fold_limbs.restype = C.c_int
         L.dcdf_zonal_fold_limbs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]

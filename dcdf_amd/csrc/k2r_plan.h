@@ -1,4 +1,4 @@
-// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_time_groups, reduce_space, histogram, spells, zonal, quantile_time, regress_time:
+// k2r_plan.h -- how the region calls of a raster (decode, reduce_time, reduce_time_groups, reduce_space, histogram, spells, zonal, quantile_time, regress_time, rolling_time:
 // k2r_raster_region.hip)
 // turn a batch of cubes into device work.  Host code only, no HIP header: tests/sim/plan_check.cpp runs it on a CPU.
 //
@@ -19,6 +19,7 @@
 #include "k2r_quantile.h"
 #include "k2r_reduce.h"
 #include "k2r_regress.h"
+#include "k2r_rolling.h"
 #include "k2r_space.h"
 #include "k2r_spell.h"
 #include "k2r_zonal.h"
@@ -829,6 +830,63 @@ inline int plan_regress_time(const PlanRaster& g, const dcdf_cube* cubes, size_t
     if (rc != DCDF_OK) return rc;
     P.cols.reserve(P.q.cols.size());
     for (size_t i = 0; i < P.q.cols.size(); i++) P.cols.push_back(RegressCol{P.q.cols[i], rec0[P.q.col_cube[i]], start0[P.q.col_cube[i]]});
+    return DCDF_OK;
+}
+
+// ---- rolling windows over time --------------------------------------------------------------------------------------------------
+// The cubes are decoded exactly as for the quantiles and the regression -- plan_quantile_time's bands, columns, segment tables,
+// units, items and elided fills over a slab of cap_bytes --, and k_rolling_stream reads every cell's series from the slab.  What it
+// needs beside a column is made here per cube that has cells (k2r_rolling.h): seg_of, the segment-table entry of EVERY instant of
+// the cube (a window reaches back over instants of any label); ends, the instants i >= window - 1 that belong to a group, sorted
+// by (label, instant) -- a counting sort, stable, so a group's instants stay ascending --; and the CSR of the groups over them,
+// counted from the cube's first.  labels == nullptr: the plain call, one group (n_groups == 1) of every window.  The call's own
+// arguments are refused before anything is made.  base[q]: cube q's first output plane.
+struct RollingPlan {
+    QuantilePlan q;
+    std::vector<RollingCol> cols;  // q.cols with their cube's end0, start0, seg_of0
+    std::vector<uint32_t> ends;
+    std::vector<uint32_t> start;   // n_groups + 1 per cube that has cells
+    std::vector<uint32_t> seg_of;  // its instants per cube that has cells
+};
+inline int plan_rolling_time(const PlanRaster& g, const dcdf_cube* cubes, size_t nq, const uint64_t* base, uint64_t cap_bytes, bool node_wise,
+                             uint32_t wanted, uint32_t ops, uint32_t window, uint32_t min_count, int32_t kind, const uint16_t* labels,
+                             const uint64_t* label_offset, uint32_t n_groups, RollingPlan& P) {
+    if (!rolling_args_ok(ops, window, min_count, kind) || n_groups < 1u || n_groups > 65535u) return DCDF_ERR_BAD_ARG;
+    std::vector<uint32_t> end0(nq, 0), start0(nq, 0), seg_of0(nq, 0), fill;
+    for (size_t q = 0; q < nq; q++) {
+        const dcdf_cube c = norm_cube(cubes[q]);
+        if (cube_cells(c) == 0) continue;
+        const uint32_t nt = c.end - c.start;
+        const uint16_t* const lab = labels ? labels + label_offset[q] : nullptr;
+        if (P.ends.size() + nt > 0x7ffffff0ull || P.start.size() + n_groups + 1ull > 0x7ffffff0ull) return DCDF_ERR_CAPACITY;
+        end0[q] = (uint32_t)P.ends.size();
+        start0[q] = (uint32_t)P.start.size();
+        seg_of0[q] = (uint32_t)P.seg_of.size();
+        for (uint32_t t = 0; t < nt; t++) P.seg_of.push_back((c.start + t) / g.cs - c.start / g.cs);
+        // the groups' sizes, then their first windows, then every window's end into its group's next place
+        P.start.resize(P.start.size() + n_groups + 1u, 0u);
+        uint32_t* const st = P.start.data() + start0[q];
+        for (uint32_t t = window - 1u; t < nt; t++) {
+            const uint32_t l = lab ? lab[t] : 0u;
+            if (l != 0xffffu && l < n_groups) st[l + 1u]++;
+        }
+        for (uint32_t l = 0; l < n_groups; l++) st[l + 1u] += st[l];
+        P.ends.resize(P.ends.size() + st[n_groups]);
+        uint32_t* const end = P.ends.data() + end0[q];
+        fill.assign(st, st + n_groups);
+        for (uint32_t t = window - 1u; t < nt; t++) {
+            const uint32_t l = lab ? lab[t] : 0u;
+            if (l == 0xffffu || l >= n_groups) continue;
+            end[fill[l]++] = t;
+        }
+    }
+    const int rc = plan_quantile_time(g, cubes, nq, base, cap_bytes, node_wise, wanted, P.q);
+    if (rc != DCDF_OK) return rc;
+    P.cols.reserve(P.q.cols.size());
+    for (size_t i = 0; i < P.q.cols.size(); i++) {
+        const uint32_t q = P.q.col_cube[i];
+        P.cols.push_back(RollingCol{P.q.cols[i], end0[q], start0[q], seg_of0[q], 0u});
+    }
     return DCDF_OK;
 }
 

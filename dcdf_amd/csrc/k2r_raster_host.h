@@ -1,6 +1,6 @@
 // k2r_raster_host.h -- the raster handle and what its two translation units share: k2r_raster.hip (constructors, fill_window,
 // search, get / fill_cell) and k2r_raster_region.hip (the region calls: decode, reduce_time, reduce_time_groups, moments_time, moments_time_groups, spells, quantile_time,
-// regress_time, regress_time_groups, reduce_space, histogram, zonal).  Host code only.
+// regress_time, regress_time_groups, rolling_time, rolling_time_groups, reduce_space, histogram, zonal).  Host code only.
 #pragma once
 #include "k2r_plan.h"
 #include "k2r_query_host.h"

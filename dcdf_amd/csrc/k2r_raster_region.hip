@@ -1,5 +1,5 @@
 // k2r_raster_region.hip -- C ABI, query side: the calls that read whole regions of a raster -- decode, reduce over time (plain and grouped), moments
-// over time (plain and grouped), spell statistics, quantiles over time, regression over time (plain and grouped), reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
+// over time (plain and grouped), spell statistics, quantiles over time, regression over time (plain and grouped), rolling windows over time (plain and grouped), reduce over space, histogram, zonal statistics -- with their fold / finish kernels.  The plan of every call is host code of its own (k2r_plan.h); here
 // are the arguments, the uploads and the launches.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include "k2r_moment.h"
 #include "k2r_raster_host.h"
 #include "k2r_regress.h"
+#include "k2r_rolling.h"
 
 using namespace k2r;
 
@@ -733,6 +734,67 @@ extern "C" int dcdf_raster_regress_time_groups_batch(const dcdf_raster* r, const
     const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
     if (rc != DCDF_OK || nq == 0) return rc;
     return regress_batch(r, cubes, nq, ops, regressor, regressor_offset, labels, label_offset, n_groups, out, out_mem, out_offset, stats, kernel_ms);
+}
+// ---- rolling windows over time: per cell, the extremes of the sums or means of every w consecutive instants (k2r_rolling.h) -------
+// The plan is plan_rolling_time's (k2r_plan.h): the quantiles' bands over the same slab and cap, and per cube its instant table,
+// the ordered ends of its groups' windows and their CSR.  A band: the three launches of decode as above, then k_rolling_stream
+// (k2r_rolling.hip) over its columns, which writes every element of the planes.  labels == nullptr: the plain call.
+static int rolling_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t window, uint32_t min_count, int32_t kind,
+                         const uint16_t* labels, const uint64_t* label_offset, uint32_t n_groups, double* out, int out_mem,
+                         const uint64_t* out_offset, uint64_t stats[3], float* kernel_ms) {
+    const PlaneLayout L(cubes, nq, popc32(ops) * n_groups, 0);
+    WindowOut W(L.planes.data(), nq, out, out_offset, sizeof(double), out_mem == DCDF_MEM_DEVICE);
+    RollingPlan P;
+    int rc = plan_rolling_time(r->plan(), cubes, nq, W.base.data(), quantile_slab_bytes(), r->all_node, bulk_wanted_units(), ops, window,
+                               min_count, kind, labels, label_offset, n_groups, P);
+    if (rc != DCDF_OK) return rc;
+    DevBuf d_cols, d_segs, d_ends, d_start, d_seg_of, d_slab;
+    RegionRun R;  // (units: the bulk units, cfolds: the elided fills, walk.items: the walk's items)
+    rc = R.begin(W, stats, P.q.stats);
+    if (rc != DCDF_OK || R.nothing) return rc;
+    double* const d_dst = (double*)W.dst();
+    K2R_HIP(d_slab.alloc_pooled(P.q.slab_max * sizeof(int64_t)));
+    K2R_HIP(upload(d_cols, P.cols));
+    K2R_HIP(upload(d_segs, P.q.segs));
+    K2R_HIP(upload(d_start, P.start));
+    K2R_HIP(upload(d_seg_of, P.seg_of));
+    rc = upload_some(d_ends, P.ends);  // (none when no window ends in a group)
+    if (rc == DCDF_OK) rc = upload_some(R.units, P.q.units);
+    if (rc == DCDF_OK) rc = upload_some(R.cfolds, P.q.consts);
+    if (rc == DCDF_OK) rc = upload_some(R.walk.items, P.q.items);
+    if (rc == DCDF_OK) rc = R.start();
+    if (rc != DCDF_OK) return rc;
+    for (const QuantileBand& b : P.q.bands) {
+        rc = launch_raster_fill_const(r, R.cfolds.as<ConstPiece>() + b.const0, (uint32_t)(b.const1 - b.const0), d_slab.p, DCDF_I64);
+        if (rc == DCDF_OK)
+            rc = launch_bulk_decode(r->d_refs.as<ChunkRef>(), R.units.as<BulkUnit>() + b.unit0, (uint32_t)(b.unit1 - b.unit0), d_slab.p, DCDF_I64);
+        if (rc == DCDF_OK && b.item1 > b.item0)
+            rc = launch_window_items_dev(r->d_refs, R.walk.items.as<WinItem>() + b.item0, (uint32_t)(b.item1 - b.item0), d_slab.p, DCDF_I64, nullptr,
+                                         nullptr, r->all_node, r->all_narrow);
+        if (rc == DCDF_OK)
+            rc = launch_rolling_stream(d_cols.as<RollingCol>() + b.col0, (uint32_t)(b.col1 - b.col0), b.max_cells, d_segs.as<QuantileSeg>(),
+                                       d_ends.as<uint32_t>(), d_start.as<uint32_t>(), d_seg_of.as<uint32_t>(), n_groups, d_slab.as<int64_t>(), ops,
+                                       window, min_count, kind, d_dst);
+        if (rc != DCDF_OK) return rc;
+    }
+    return R.end(W, true, kernel_ms);
+}
+extern "C" int dcdf_raster_rolling_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t window,
+                                              uint32_t min_count, int32_t kind, double* out, int out_mem, const uint64_t* out_offset,
+                                              uint64_t stats[3], float* kernel_ms) {
+    const bool own = rolling_args_ok(ops, window, min_count, kind);
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return rolling_batch(r, cubes, nq, ops, window, min_count, kind, nullptr, nullptr, 1, out, out_mem, out_offset, stats, kernel_ms);
+}
+extern "C" int dcdf_raster_rolling_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t window,
+                                                     uint32_t min_count, int32_t kind, const uint16_t* labels, const uint64_t* label_offset,
+                                                     uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                                                     float* kernel_ms) {
+    const bool own = rolling_args_ok(ops, window, min_count, kind) && n_groups >= 1 && n_groups <= 65535 && (nq == 0 || (labels && label_offset));
+    const int rc = region_begin(r, cubes, nq, out, out_offset, out_mem, own, ANY_FLOATS, stats, kernel_ms);
+    if (rc != DCDF_OK || nq == 0) return rc;
+    return rolling_batch(r, cubes, nq, ops, window, min_count, kind, labels, label_offset, n_groups, out, out_mem, out_offset, stats, kernel_ms);
 }
 // ---- reduce over space: per-instant min / max / sum / count / mean of the selected cells of a cube (k2r_space.h) ------------
 // The plan is plan_reduce_space's (k2r_plan.h): records of the pieces in a pooled scratch array, in blocks [slot][instant] that

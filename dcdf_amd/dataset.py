@@ -476,6 +476,31 @@ class Variable:  # py-dcdf __init__.py:246-336 over dataset.rs:642-986
         (dcdf_raster_regress_time_groups_batch)."""
         return Variable._statistic(self, _raster._RegressTimeGroups, (ops,), (regressor,), start, stop, top, bottom, left, right, labels)
 
+    def rolling_time(self, window, ops=("max",), min_count=None, mean=False, start=0, stop=None, top=0, bottom=None, left=0, right=None):
+        """Per-cell extremes of the sums of every `window` consecutive instants of [start, stop) over the window [top, bottom) x
+        [left, right) of cells: {name: ndarray [rows, cols] float64} for the names of `ops` ("max", "argmax", "min", "argmin",
+        "count", or a DCDF_ROLLING_* bitmask), of the values window() returns widened to float64 -- the greatest 5-day total
+        (window=5), the lowest 7-day mean (window=7, ops="min", mean=True).  A sum ends at instant i, counted from `start`, covers
+        [i - window + 1, i], exists for i >= window - 1 and counts when at least min_count (None: window) of its values are not
+        NaN; it is exact and rounded once.  argmax / argmin: the last instant of the earliest window whose exact sum is the
+        greatest / least; count: the windows that counted.  A cell without one gets NaN but for count.  Through
+        raster().rolling_time: the cube is decoded band by band into a bounded device buffer and only the planes are written
+        (dcdf_raster_rolling_time_batch)."""
+        return Variable._statistic(self, _raster._RollingTime, (ops, window, min_count, mean), (), start, stop, top, bottom, left, right)
+
+    def rolling_time_groups(self, labels, window, ops=("max",), min_count=None, mean=False, start=0, stop=None, top=0, bottom=None, left=0,
+                            right=None):
+        """rolling_time per group of instants -- Rx5day of every year (labels = year_of(instants), window=5): `labels` is any integer
+        array [stop - start] of group ids, negative = no group.  A window belongs to the group of its LAST instant and reaches back
+        over instants of any id (the wettest five days of a year may begin in the previous December).  Returns (ids, {name: ndarray
+        [len(ids), rows, cols] float64}) as moments_time_groups does: ids are the distinct non-negative ids ascending, plane i of
+        every array is the fold over the windows that end on an instant labelled ids[i], argmax / argmin still counted from
+        `start` (a group without a window that counts gets NaN but for count).  More than 65535 distinct ids: ValueError.  Through
+        raster().rolling_time_groups: the cube is decoded once on the GPU whatever the number of groups
+        (dcdf_raster_rolling_time_groups_batch)."""
+        return Variable._statistic(self, _raster._RollingTimeGroups, (ops, window, min_count, mean), (), start, stop, top, bottom, left, right,
+                                   labels)
+
     def spells(self, lower, upper, ops=("count", "longest"), start=0, stop=None, top=0, bottom=None, left=0, right=None):
         """Per-cell spell statistics over the instants [start, stop) of the window [top, bottom) x [left, right): {name: ndarray
         [rows, cols] uint32} for the names of `ops` ("count", "longest", "longest_start", "first", "last", or a DCDF_SPELL_*

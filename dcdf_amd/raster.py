@@ -370,6 +370,56 @@ class EncodedRaster:
         return self._whole(_RegressTimeGroups, (ops,), (labels, n_groups, regressor), start, stop, window)
 
     @staticmethod
+    def rolling_ops(ops):
+        """ops of rolling_time / rolling_time_groups as (bitmask, names in plane order): a DCDF_ROLLING_* bitmask, one name or an
+        iterable of "max" / "argmax" / "min" / "argmin" / "count"."""
+        return EncodedRaster._ops(ops, L.ROLLING_OPS, "rolling_time")
+
+    def rolling_time_flat(self, cubes, ops, window, min_count=None, mean=False, out_device_ptr=None, out_offset=None):
+        """Per-cell extremes of the sums of every `window` consecutive instants of dataset-level cubes [n, 6] through
+        dcdf_raster_rolling_time_batch: cube q yields one [rows, cols] float64 plane per statistic of `ops` (rolling_ops), in the
+        order max, argmax, min, argmin, count, over the values decode_flat returns for it in the leaves' own dtype.  The window
+        that ENDS at instant i, counted from the cube's first, covers [i - window + 1, i] and exists for i >= window - 1; it is valid
+        when it holds at least min_count (None: window) values that are not NaN, and its sum is their EXACT sum.  max / min: the
+        greatest / least sum over the valid windows, rounded once; mean=True: divided by window (min_count must then be window).
+        argmax / argmin: the last instant of the earliest window whose exact sum is the greatest / least -- sums that only round to
+        the same double are no tie.  count: the valid windows.  A cell without one gets NaN, NaN, NaN, NaN, 0.  Host form: returns
+        (flat float64 array, offsets uint64[n], kernel ms, stats): cube q's planes are flat[offsets[q]:] shaped (planes, r, c).
+        Device form (out_device_ptr + out_offset in elements): returns (kernel ms, stats).  stats = uint64[3]: cells read by the
+        bulk kernel, by the fallback walk, from elided leaves."""
+        return self._flat(_RollingTime(ops, window, min_count, mean), cubes, out_device_ptr=out_device_ptr, out_offset=out_offset)
+
+    def rolling_time(self, ops, window, min_count=None, mean=False, start=0, stop=None, region=None):
+        """{statistic: ndarray [rows, cols] float64} of rolling_time_flat over the instants [start, stop) of the whole raster, or of
+        `region` = (top, bottom, left, right) -- `window` is the number of instants a sum takes, 1 .. 65535: the greatest 5-day
+        total and the instant it ended on are rolling_time(("max", "argmax"), 5), the lowest 7-day mean rolling_time("min", 7,
+        mean=True).  Instants are counted from `start`, whose first window - 1 instants end no window: pass an earlier start for
+        windows that reach back.  Without instants or cells: count 0, NaN elsewhere."""
+        return self._whole(_RollingTime, (ops, window, min_count, mean), (), start, stop, region)
+
+    def rolling_time_groups_flat(self, cubes, ops, labels, n_groups, window, min_count=None, mean=False, out_device_ptr=None, out_offset=None):
+        """rolling_time_flat's statistics per cell and group of instants through dcdf_raster_rolling_time_groups_batch: the cube is
+        decoded once whatever the number of groups.  labels and n_groups are reduce_time_groups_flat's: one uint16 array [instants]
+        per (normalised) cube, GROUP_NONE (0xffff) and every other value >= n_groups in no group.  A window belongs to the group of
+        its LAST instant and reaches back over instants of any label or none (the wettest five days of a year may begin in the
+        previous December).  Cube q yields one [n_groups, rows, cols] float64 array per statistic of `ops`, in the order max,
+        argmax, min, argmin, count: group g is the fold over the valid windows whose last instant is labelled g, argmax / argmin
+        still counted from the cube's first instant; a group without a valid window gets NaN, NaN, NaN, NaN, 0.  Consecutive
+        instants of a group slide the window; every other window is summed again from its `window` values, so a scattered
+        labelling (i % 7) reads that many values per window.  Returns what rolling_time_flat returns, cube q's part shaped
+        (statistics, n_groups, r, c)."""
+        return self._flat(_RollingTimeGroups(ops, window, min_count, mean), cubes, labels, n_groups, out_device_ptr=out_device_ptr,
+                          out_offset=out_offset)
+
+    def rolling_time_groups(self, ops, labels, window, min_count=None, mean=False, start=0, stop=None, region=None, n_groups=None):
+        """{statistic: ndarray [n_groups, rows, cols] float64}: rolling_time over the instants [start, stop) of the whole raster, or
+        of `region`, for every group of `labels` -- uint16 [stop - start], GROUP_NONE and labels >= n_groups are in no group; a
+        window belongs to the group of its last instant: Rx5day per year, say.  n_groups defaults to the largest label present,
+        GROUP_NONE apart, plus 1 (at least 1).  With one group and all labels 0 it is rolling_time bit for bit.  Without instants
+        or cells: count 0, NaN elsewhere, of that shape."""
+        return self._whole(_RollingTimeGroups, (ops, window, min_count, mean), (labels, n_groups), start, stop, region)
+
+    @staticmethod
     def _device_arrays(q, arrays, what, noun):
         """One array per cube (masks, labels) already on the device, given as (device pointer, offsets uint64[n]): (pointer, offsets,
         memory kind, what must stay alive over the call); None when `arrays` is not of that form."""
@@ -1022,3 +1072,37 @@ class _RegressTimeGroups(_TimeGroups, _RegressTime):
 
     def window(self, nt, rows, cols, labels, n, regressor=None):
         return tuple(_TimeGroups.window(self, nt, rows, cols, labels, n)) + self.beside(nt, regressor)
+
+
+class _RollingTime(_ReduceTime):
+    """The window, min_count and the kind are its own arguments; it takes no arrays."""
+    name = "rolling_time"
+    fill = dict(max=np.nan, argmax=np.nan, min=np.nan, argmin=np.nan, count=0.0)
+
+    def __init__(self, ops, window, min_count, mean):
+        """window 1 .. 65535 instants; min_count 1 .. window (None: window); mean: the sums divided by window, whole windows only"""
+        self.mask, self.names = EncodedRaster.rolling_ops(ops)
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= L.ROLLING_MAX_WINDOW:
+            raise ValueError("rolling_time: window %r outside 1 .. %d" % (window, L.ROLLING_MAX_WINDOW))
+        self.w = int(window)
+        if min_count is None:
+            min_count = self.w
+        if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= min_count <= self.w:
+            raise ValueError("rolling_time: min_count %r outside 1 .. window %d" % (min_count, self.w))
+        self.min_count = int(min_count)
+        if mean and self.min_count != self.w:
+            raise ValueError("rolling_time: the mean takes whole windows, min_count %d is not window %d" % (self.min_count, self.w))
+        self.kind = L.ROLLING_MEAN if mean else L.ROLLING_SUM
+
+    def own(self):
+        return C.c_uint32(self.mask), C.c_uint32(self.w), C.c_uint32(self.min_count), C.c_int32(self.kind)
+
+    def args(self, n, out, mem, off, stats):
+        return (n,) + self.own() + (out, mem, off, stats)
+
+
+class _RollingTimeGroups(_TimeGroups, _RollingTime):
+    name = "rolling_time_groups"  # (its statistics, window and min_count are rolling_time's, and so named in their messages)
+
+    def args(self, n, out, mem, off, stats):
+        return (n,) + self.own() + (self.labels[0], self.labels[1], C.c_uint32(self.n), out, mem, off, stats)

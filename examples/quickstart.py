@@ -69,4 +69,10 @@ fit = np.polyfit(np.arange(32.0), a.reshape(32, -1).astype(np.float64), 1)
 assert np.allclose(trend["slope"].ravel(), fit[0]) and np.allclose(trend["intercept"].ravel(), fit[1])
 years = 1990.0 + np.arange(32)  # any regressor: taken less its first value, so the intercept is the fitted value at years[0]
 assert np.allclose(R.regress_time(("intercept",), years)["intercept"], trend["intercept"]) and (np.abs(trend["corr"]) <= 1).all()
+rx5 = R.rolling_time(("max", "argmax"), 5)  # per cell, the greatest sum of 5 consecutive instants and the instant it ended on: Rx5day
+s5 = np.lib.stride_tricks.sliding_window_view(a.astype(np.float64), 5, axis=0).sum(-1)  # [28, 256, 256]: the windows that end at 4 .. 31
+assert (rx5["max"] == s5.max(0)).all() and (rx5["argmax"] == s5.argmax(0) + 4).all()
+low = R.rolling_time_groups(("min",), (np.arange(32) // 16).astype(np.uint16), 7, mean=True)  # the lowest 7-instant mean per half; a window is its last instant's
+s7 = np.lib.stride_tricks.sliding_window_view(a.astype(np.float64), 7, axis=0).sum(-1)  # windows that end at 6 .. 31
+assert (low["min"][0] == s7[:10].min(0) / 7.0).all() and (low["min"][1] == s7[10:].min(0) / 7.0).all()
 print("readme example ok")

@@ -382,6 +382,52 @@ int dcdf_raster_regress_time_groups_batch(const dcdf_raster* r, const dcdf_cube*
                                           const uint64_t* regressor_offset, const uint16_t* labels, const uint64_t* label_offset,
                                           uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
                                           float* kernel_ms);
+/* Rolling windows over time: per cell (row, col) of each cube, the greatest and least sum (or mean) of every `window` consecutive
+ * instants, when they occurred and how many windows counted -- the greatest 5-day total of a year (Rx5day), the wettest or driest
+ * 30-day period and when it began, the lowest 7-day mean flow --, whole or, in the grouped call, for every group of a per-instant
+ * label array.  The cube is decoded band by band into the bounded device slab of dcdf_raster_quantile_time_batch and every cell's
+ * series is read from there; the cube never reaches the host.  The calls take plain and tiled rasters, elided leaves included.
+ * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's; labels, label_offset, n_groups and
+ * DCDF_GROUP_NONE exactly dcdf_raster_reduce_time_groups_batch's.  DESIGN.md section 4o.
+ *   values      x[i] is reduce_time's x[t] (reduce_widen of the stored integer with its own segment's encoding and fractional
+ *               bits), instants i = 0 .. nt - 1 counted from the cube's first instant after normalisation.
+ *   window      w, 1 .. 65535.  The window that ENDS at instant i covers [i - w + 1, i] and exists only for i >= w - 1: the cube's
+ *               first w - 1 instants end no window (a caller who wants windows that reach back before `start` passes an earlier
+ *               start).  c_i is the number of non-NaN values in it, S_i their EXACT real sum; NaN values contribute nothing.
+ *   min_count   1 .. w: the window is valid iff c_i >= min_count.
+ *   kind        DCDF_ROLLING_SUM or DCDF_ROLLING_MEAN.  MEAN requires min_count == window: a mean over a varying count is not an
+ *               order on the sums.
+ *   ops         a non-empty set of DCDF_ROLLING_*; cube q writes popcount(ops) planes in the order MAX, ARGMAX, MIN, ARGMIN, COUNT
+ *               from out + out_offset[q] (elements), each dense [rows][cols] float64 -- in the grouped call [n_groups][rows][cols],
+ *               the layout (statistics, groups, rows, cols) of dcdf_raster_moments_time_groups_batch.
+ * MAX / MIN: the greatest / least S_i over the valid windows, rounded ONCE to the nearest double, ties to even; a sum of 0 is +0.0.
+ * For MEAN that double is divided by (double)w, one IEEE division.  ARGMAX / ARGMIN: the LEAST i -- the window's last instant --
+ * whose exact S_i is the greatest / least: the comparison is on the exact sums (192-bit integers at the 2^-63 scale), not on the
+ * rounded doubles, so two sums that round to the same double but differ are not a tie.  COUNT: the number of valid windows.  With
+ * no valid window (window > nt included): the one quiet NaN in the four others, +0.0 in COUNT.
+ * Groups: a window belongs to the group of its LAST instant, labels[label_offset[q] + i], and reaches back over instants of any
+ * label or none -- the Rx5day of a year may begin in the previous December.  Group g is the fold over the valid windows with label
+ * g; ARGMAX / ARGMIN are still counted from the cube's first instant.  n_groups == 1 with all labels 0 is the plain call bit for
+ * bit.
+ * Every element of the planes is written exactly once, nothing outside them is; a cube without instants, rows or columns writes
+ * nothing.  The sums are integers, so sliding a window and summing it again give the same bits: the result depends on no cut of
+ * the work (K2R_QUANTILE_SLAB_BYTES, the slab's cap, changes no bit).  Consequences: window == 1 with SUM gives reduce_time's MAX,
+ * MIN and COUNT bit for bit; a constant cell has ARGMAX == ARGMIN == w - 1.
+ * Known cost: a group's windows are walked in ascending order, a run of consecutive instants sliding, every other window summed
+ * again from its w values -- a labelling such as i % 7 reads O(w) values per window.
+ * DCDF_ERR_BAD_ARG: ops == 0 or a bit above 16, window outside 1 .. 65535, min_count outside 1 .. window, a kind other than the
+ * two, MEAN with min_count != window, (grouped) n_groups 0 or above 65535 and NULL labels / label_offset with nq > 0, NULL r /
+ * cubes / out / out_offset, an unknown out_mem (nq == 0 is fine, stats and kernel_ms may be NULL); DCDF_ERR_BOUNDS: a cube outside
+ * the raster; DCDF_ERR_UNSUPPORTED: k * k > 64 chunks. */
+enum { DCDF_ROLLING_MAX = 1, DCDF_ROLLING_ARGMAX = 2, DCDF_ROLLING_MIN = 4, DCDF_ROLLING_ARGMIN = 8, DCDF_ROLLING_COUNT = 16 };
+enum { DCDF_ROLLING_SUM = 0, DCDF_ROLLING_MEAN = 1 };
+int dcdf_raster_rolling_time_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t window,
+                                   uint32_t min_count, int32_t kind, double* out, int out_mem, const uint64_t* out_offset,
+                                   uint64_t stats[3], float* kernel_ms);
+int dcdf_raster_rolling_time_groups_batch(const dcdf_raster* r, const dcdf_cube* cubes, size_t nq, uint32_t ops, uint32_t window,
+                                          uint32_t min_count, int32_t kind, const uint16_t* labels, const uint64_t* label_offset,
+                                          uint32_t n_groups, double* out, int out_mem, const uint64_t* out_offset, uint64_t stats[3],
+                                          float* kernel_ms);
 /* Spell statistics over time: per cell (row, col) of each cube, on how many of its instants the value lay inside a range, and how
  * long and when the longest unbroken run of such instants was.  The call takes plain and tiled rasters, elided leaves included.
  * Cubes, out_mem, out_offset, stats and kernel_ms are exactly dcdf_raster_reduce_time_batch's: reversed bounds of a cube are
